@@ -13,9 +13,10 @@ the warm-up never shifts which steps are timed.
 value = QP solves / s over all ranks (weak scaling: every rank owns its own seeds; the only collective is one RCCL all-gather
 of the measured states and applied inputs at the end of the timed region).
 
-Secondary figures of the default run (labelled, after the timed region): the same loop from the state scaled to 0.3 of its distance from
-hover (round 2's headline regime: few active bounds), and the whole batch as one slice.  `--workload synthetic` times round 1's step.
-`--config 5` = BASELINE config 5's per-GPU shape: 1024 seeds per rank (8192 on 8 ranks), script x0, 30 steps.
+A plain run sets up, warms up, times the steps, writes the last timed step's outputs (`--dump-outputs DIR`) and prints the line.  `--full` adds
+the figures that take runs of their own (labelled, after the timed region): the same loop from the state scaled to 0.3 of its distance from
+hover (round 2's headline regime: few active bounds), the whole batch as one slice, and the CPU baseline.  `--workload synthetic` times
+round 1's step.  `--config 5` = BASELINE config 5's per-GPU shape: 1024 seeds per rank (8192 on 8 ranks), script x0, 30 steps.
 """
 import argparse
 import json
@@ -47,8 +48,13 @@ def parse():
     ap.add_argument("--config", type=int, default=None, choices=[5], help="5: BASELINE config 5's per-GPU shape (--batch 1024 --x0-scale 1.0 --steps 30)")
     ap.add_argument("--model", default="rocket")
     ap.add_argument("--workload", default="closed_loop", choices=["closed_loop", "synthetic"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary figures (synthetic step, single-slice roofline block)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the secondary figures and the CPU baseline "
+                    "(each takes runs of its own after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step (rank 0's instances) as DIR/<name>.npy, "
+                    "float64: success / status of every instance, the solution arrays of those whose last step succeeded (DIR/instances.npy), "
+                    "at most 64 MB in all (a seeded sample of the instances beyond that)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary figures (synthetic step, single-slice roofline block)")
     ap.add_argument("--slices", type=int, default=None, help="independent slices of the rank's batch, each with its own handle / HIP stream / host thread "
                     "(default: 1 for the persistent launch, 3 otherwise)")
     ap.add_argument("--qp-eps", type=float, default=None, help="interior-point tolerance before the polish (default: the library's 1e-6)")
@@ -62,9 +68,13 @@ def parse():
                     "rocket script's setting only; 0: one slsqp_cl_step per step for the whole slice")
     ap.add_argument("--round-budget-ms", type=float, default=8.0)
     ap.add_argument("--round-cut-frac", type=float, default=0.0, help="a round's unfinished chains also suspend once this fraction of its participants are done (0: off)")
-    ap.add_argument("--secondary-synthetic", action="store_true", help="also time round 1's synthetic step as a secondary figure")
+    ap.add_argument("--secondary-synthetic", action="store_true", help="with --full: also time round 1's synthetic step as a secondary figure")
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU work for the all-core leg of cpu_baseline")
     args = ap.parse_args()
+    if args.secondary_synthetic and not args.full:
+        ap.error("--secondary-synthetic needs --full")
+    if not args.full:      # a plain run: the headline only
+        args.no_cpu = args.no_secondary = True
     if args.config == 5:
         args.batch = 1024 if args.batch is None else args.batch
         args.x0_scale = 1.0 if args.x0_scale is None else args.x0_scale
@@ -375,6 +385,49 @@ def sample_qp_data(m, N, seeds, x0, cont, steps, every, local_rank, tune, Closed
     return {k: v[order] for k, v in data.items()}, taken
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_SEED = 0
+DUMP_STATUS_KEYS = ("success", "status", "scp_iterations")      # one entry per instance, every instance
+
+
+def last_step_outputs(dev, workload, m, N, n_var, n_dual):
+    """What a caller of the timed path receives from its last step, batch axis first: ClosedLoopMPC.step()'s arrays for the closed loop,
+    BatchedFastSLS.post_processing_solution()'s solution arrays for the synthetic step."""
+    import numpy as np
+    f64, i32 = np.float64, np.int32
+    if workload == "closed_loop":
+        spec = {"u0": ("u0", (m.nu,), f64), "x_next": ("x_meas", (m.nx,), f64), "nominal_x": ("nominal_x", (N + 1, m.nx), f64),
+                "nominal_u": ("nominal_u", (N, m.nu), f64), "backoff_x": ("backoff_x", (N + 1, m.nx), f64), "backoff_u": ("backoff_u", (N, m.nu), f64),
+                "success": ("scp_success", (), i32), "status": ("status", (), i32), "scp_iterations": ("scp_iterations", (), i32),
+                "primal_infeasibility": ("primal_infeasibility", (), f64)}
+    else:
+        spec = {"primal_vec": ("primal_vec", (n_var,), f64), "dual_vec": ("dual_vec", (n_dual,), f64), "success": ("success", (), i32),
+                "status": ("status", (), i32), "backoff": ("backoff", (N, m.ni), f64), "backoff_f": ("backoff_f", (m.ni_f,), f64),
+                "backoff_x": ("backoff_x", (N + 1, m.nx), f64), "backoff_u": ("backoff_u", (N, m.nu), f64)}
+    return {k: dev.get(name, shape, dtype) for k, (name, shape, dtype) in spec.items()}
+
+
+def dump_outputs(dirname, arrays):
+    """arrays: name -> (B, ...) -> dirname/<name>.npy in float64.  The status arrays (DUMP_STATUS_KEYS) keep every instance; the solution arrays keep
+    the instances whose last step succeeded, listed in dirname/instances.npy.  A failed step leaves no solution: its instance's buffers hold the
+    warm start shifted forward and a plant state under a stale input, which after enough failed steps overflow to inf / NaN.  Beyond
+    DUMP_LIMIT_BYTES in all, a seeded sample of those instances is kept."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    status = {k: v for k, v in arrays.items() if k in DUMP_STATUS_KEYS}
+    rows = np.flatnonzero(status["success"] != 0)
+    solved = {k: v[rows] for k, v in arrays.items() if k not in DUMP_STATUS_KEYS}
+    per_row = 8 + sum(v[0].nbytes for v in solved.values()) if rows.size else 8
+    room = DUMP_LIMIT_BYTES - sum(v.nbytes for v in status.values())
+    if rows.size * per_row > room:
+        pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows.size, size=max(1, room // per_row), replace=False))
+        rows, solved = rows[pick], {k: v[pick] for k, v in solved.items()}
+    solved["instances"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in {**status, **solved}.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v))
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -541,6 +594,8 @@ def main():
         workload = (f"{args.model} N={N} batch={B}/GPU synthetic instances (seeded perturbations of one nominal; 0-8 active inequalities), fast-SLS RTI step "
                     f"(update_dynamics + update_linear_cost + solve: 2 QP solves + 1 SLS sweep per instance), no linearisation")
         extra_cfg = {}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(dev, args.workload, m, N, n_var, N * (m.nx + m.ni) + m.ni_f))
     k_ms, k_launches, inst_sweeps, mx_retries = dev.kernel_timing()
     fact_stages, qp_solves = dev.factor_stages, dev.qp_solves
     qp_done = float(qp_solves)      # QP solves of the timed region that actually ran (device counter), this rank

@@ -643,9 +643,12 @@ struct ClQueue { int *slots; unsigned mask; unsigned *head, *tail; int *avail, *
 __device__ __forceinline__ int clq_pop(const ClQueue &q, int lane) {
     int v = -1;
     if (lane == 0) {
-        const int av = atomicSub(q.avail, 1);
-        if (av <= 0) atomicAdd(q.avail, 1);
-        else {
+        // a claim given back hides, while it lasts, an item published meanwhile: look again when the give-back leaves avail > 0, or this wave
+        // and the publisher of that item could both exit with the item stranded in the queue
+        bool claimed = true;
+        while (atomicSub(q.avail, 1) <= 0)
+            if (atomicAdd(q.avail, 1) + 1 <= 0) { claimed = false; break; }
+        if (claimed) {
             const unsigned t = atomicAdd(q.head, 1u);
             int *slot = q.slots + (t & q.mask);
             int got = 0;

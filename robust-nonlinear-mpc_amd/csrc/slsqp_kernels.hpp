@@ -606,6 +606,7 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
         if (lane < NX) {
             const double xv = a.x0val[(size_t)b * NX + lane];
             viol = fmax(xv - ub[NX + lane], -ub[NX + NZ + lane] - xv);
+            if (isnan(viol)) viol = INFINITY;      // a NaN state (a failed run whose plant overflowed) is outside every box; wave_max would drop the NaN
         }
         if (wla::wave_max(viol) > 1e-9) status = 2;
         // warm start: the previous solve of this instance ended with a certified active set -> polish from it first

@@ -991,10 +991,20 @@ def test_fastsls_converge_mode_vs_oracle(model):
 def test_one_infeasible_instance_does_not_fail_the_batch():
     """Instance 1 gets a measured state far outside its stage-0 box: the reference's QP is infeasible for it
     ({'success': False}, qp_jit.py:397-400); the other instances must be unaffected and identical to a clean batch."""
+    _one_bad_instance(100.0)
+
+
+def test_nan_measured_state_is_flagged_not_solved():
+    """A NaN measured state (a failed closed-loop run whose plant overflowed) is outside every box too: flagged like instance 1 above,
+    never "solved" into a NaN solution that counts as a successful MPC step."""
+    _one_bad_instance(np.nan)
+
+
+def _one_bad_instance(shift):
     insts = [make_instance("pendulum", s, 0.5) for s in range(4)]
     clean = run_gpu_fastsls(insts, rti_steps=1)
     bad = [make_instance("pendulum", s, 0.5) for s in range(4)]
-    bad[1].x0_arg = bad[1].x0_arg + 100.0
+    bad[1].x0_arg = bad[1].x0_arg + shift
     from problems import make_gpu_solver
     f = make_gpu_solver(bad)
     out = run_gpu_fastsls(bad, rti_steps=1, solver=f)

@@ -366,6 +366,70 @@ def test_bench_gpus_flag_launches_ranks_or_refuses(monkeypatch):
     assert e.value.code == 2 and len(calls) == 1
 
 
+def _bench_line_one_rank(monkeypatch, argv):
+    """bench.main() on one rank with the GPU slice replaced by a stand-in: (the JSON line, the stand-in batches it made)."""
+    import io, contextlib, json
+    import torch
+    import bench
+    monkeypatch.setattr(torch.cuda, "set_device", lambda d: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setattr(bench, "ClosedLoopSlices", _FakeSlices)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    _FakeSlices.instances = []
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        bench.main()
+    return json.loads(buf.getvalue().strip().splitlines()[-1]), list(_FakeSlices.instances)
+
+
+def test_bench_plain_run_times_only_the_headline_and_dumps_the_last_step(tmp_path, monkeypatch):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` makes the warm-up batch and the timed batch and nothing else (the secondary regime and the
+    CPU baseline's re-run sample come with --full only); --dump-outputs writes the arrays ClosedLoopMPC.step() returns, in float64, one row per instance."""
+    out = tmp_path / "dump"
+    line, made = _bench_line_one_rank(monkeypatch, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+    assert len(made) == 2 and len(made[0].seeds) == len(made[1].seeds) == 4096 and made[0].seeds.min() >= (1 << 20)
+    assert line["steps"] == 3 and line["warmup"] == 1 and abs(line["value"] * line["ms_per_step"] * 3e-3 - 2 * 4096 * 3) < 1e-6
+    assert line["cpu_baseline"] is None and "secondary" not in line and line["dtype"] == "f64" and line["unit"] == "QP solves/s"
+    names = {"u0", "x_next", "nominal_x", "nominal_u", "backoff_x", "backoff_u", "success", "status", "scp_iterations", "primal_infeasibility", "instances"}
+    assert {p.name for p in out.iterdir()} == {n + ".npy" for n in names}
+    for n in names:
+        a = np.load(out / (n + ".npy"))
+        assert a.dtype == np.float64 and a.shape[0] == 4096
+    assert np.load(out / "nominal_x.npy").shape == (4096, 21, 17) and np.all(np.load(out / "success.npy") == 1.0)
+    assert np.array_equal(np.load(out / "instances.npy"), np.arange(4096.0))
+    line_full, made_full = _bench_line_one_rank(monkeypatch, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert "secondary" in line_full and line_full["cpu_baseline"] is not None and len(made_full) > 2
+    with pytest.raises(SystemExit):
+        _bench_line_one_rank(monkeypatch, ["--steps", "3", "--secondary-synthetic"])
+
+
+def test_bench_dump_outputs_keeps_the_solved_instances_and_a_seeded_sample_beyond_the_size_limit(tmp_path, monkeypatch):
+    """success / status / scp_iterations keep every instance; the solution arrays keep the rows of the instances whose last step succeeded
+    (a failed instance's buffers are no solution and may hold inf / NaN), listed in instances.npy; beyond the size limit a seeded sample of them."""
+    import bench
+    B = 1000
+    ok = np.arange(B) % 4 != 1
+    a = np.arange(B * 6, dtype=np.float64).reshape(B, 6)
+    a[~ok] = np.nan
+    arrays = {"a": a, "success": ok.astype(np.int32), "status": np.where(ok, 0, 2).astype(np.int32), "scp_iterations": np.zeros(B, np.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    rows = np.flatnonzero(ok)
+    assert np.array_equal(np.load(tmp_path / "all" / "instances.npy"), rows.astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "all" / "a.npy")[:, 0], 6.0 * rows) and np.isfinite(np.load(tmp_path / "all" / "a.npy")).all()
+    for k in ("success", "status", "scp_iterations"):
+        v = np.load(tmp_path / "all" / (k + ".npy"))
+        assert v.dtype == np.float64 and v.shape == (B,) and np.array_equal(v, arrays[k])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40000)
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    kept = np.load(tmp_path / "x" / "instances.npy")
+    assert np.array_equal(kept, np.load(tmp_path / "y" / "instances.npy")) and np.all(np.diff(kept) > 0) and 0 < kept.size < rows.size
+    assert np.isin(kept, rows).all() and np.array_equal(np.load(tmp_path / "x" / "a.npy")[:, 0], 6 * kept)
+    assert np.load(tmp_path / "x" / "success.npy").shape == (B,)
+    assert sum(p.stat().st_size - 128 for p in (tmp_path / "x").iterdir()) <= 40000      # (128 B: the .npy header)
+
+
 def test_oracle_c_threaded_rti_batch_equals_the_python_driven_oracle():
     """bench.py's cpu_baseline runs the oracle's RTI step from C threads (so_rti_step_batch); it must be the same computation as
     OracleFastSLS.solve(rti_steps=1) driven from Python, instance by instance (bit-identical), for any thread count."""
@@ -463,8 +527,13 @@ def test_instance_queue_protocol_model_under_thread_sanitizer(tmp_path, B, steps
     workers that exit when the count is <= 0, an instance behind the mean keeps its worker) as a host model on std::atomic, one thread per wavefront,
     under ThreadSanitizer: every instance runs exactly `steps` steps in order, every hand-over carries the previous step's writes (release on push, acquire
     on pop), nothing is stranded when workers exit, no worker hangs -- with more workers than instances, fewer, and a single instance."""
+    import platform
+    import shutil
     import subprocess
     exe = tmp_path / "queue_model"
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=thread", "-pthread", "-o", str(exe), os.path.join(ROOT, "tests", "queue_model.cpp")])
-    r = subprocess.run([str(exe), str(B), str(steps), str(workers), str(keep)], capture_output=True, text=True, timeout=300)
+    cmd = [str(exe), str(B), str(steps), str(workers), str(keep)]
+    if shutil.which("setarch"):      # ThreadSanitizer's memory layout does not fit every address-space randomisation a kernel may use ("unexpected memory mapping")
+        cmd = ["setarch", platform.machine(), "-R"] + cmd
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.startswith("ok") and "ThreadSanitizer" not in r.stderr, (r.stdout, r.stderr[-2000:])
