@@ -49,7 +49,10 @@ enum {
     SLSQP_ST_SOLVED_IPM = 4,  /* interior-point tolerance met, polish rejected (solution accurate to opts.eps) */
     SLSQP_ST_MAX_ITER = 1,
     SLSQP_ST_INFEASIBLE = 2,  /* primal infeasible, seen before any work: the pinned x0 lies outside its own stage-0 box */
-    SLSQP_ST_NUMERICAL = 3,
+    SLSQP_ST_NUMERICAL = 3,   /* no finite answer: the interior point's residual went NaN / beyond 1e30, or the instance's data holds a NaN (q, box or
+                                 dynamics rows, A, B) or an infinite entry of q, a dynamics row, A or B (checked around every QP launch of slsqp_qp_solve /
+                                 slsqp_solve; the closed-loop entry points build their own data and rely on the certificate, which never accepts NaN).
+                                 An instance whose x0 is NaN is status 2 */
     SLSQP_ST_INFEASIBLE_CERT = 5 /* primal infeasible, certified by the interior point's multipliers (Farkas ray; the test OSQP applies for the
                                     reference, eps_prim_inf = 1e-4): E'nu + lambda_u - lambda_l ~ 0 with a negative support value */
 };

@@ -62,6 +62,7 @@ struct slsqp_handle {
     int *qp_diag = nullptr;     // QP_DIAG_SPAN builds only
     double *nom_st; int *nom_need_lin, *nom_status, *nom_iters;
     int *retry; int mx_retry, mx_retry_total;
+    int *databad, *runq;        // (B) 1 = the QP data of the instance holds a non-finite value (k_flag_nonfinite); the launch's run mask without those
     double *Kc, *Aclc;          // (B,N,nu,nx), (B,N,nx,nx): K_k and A_k + B_k K_k of the shared Riccati recursion (k_sweep_ric1 -> k_sweep_prop)
     double *lin_stage, *lin_tape;   // (B,N,3,nx) intermediate RK4 stage points of the linearisation (k_lin_val -> k_lin_tan); (B,N,4,NT_MAX) its transcendental values
     double call_id;             // counts fast-SLS calls (validity of the interior-point iterate copies, QpArgs::call_id)
@@ -165,7 +166,7 @@ extern "C" slsqp_handle *slsqp_create(const slsqp_dims *d, int batch, int device
     rc |= dalloc(h->owned, &h->status, B); rc |= dalloc(h->owned, &h->iters, B); rc |= dalloc(h->owned, &h->itnum, B); rc |= dalloc(h->owned, &h->has_prev, B); rc |= dalloc(h->owned, &h->conv, B);
     rc |= dalloc(h->owned, &h->alive, B); rc |= dalloc(h->owned, &h->mask, B); rc |= dalloc(h->owned, &h->success, B); rc |= dalloc(h->owned, &h->infeas, B); rc |= dalloc(h->owned, &h->counter, (size_t)4);
     rc |= dalloc(h->owned, &h->scp_active, B); rc |= dalloc(h->owned, &h->scp_success, B); rc |= dalloc(h->owned, &h->scp_iters, B); rc |= dalloc(h->owned, &h->pending_reset, B); rc |= dalloc(h->owned, &h->scp_dmax, B);
-    rc |= dalloc(h->owned, &h->retry, B); h->mx_retry = 0; h->mx_retry_total = 0;
+    rc |= dalloc(h->owned, &h->retry, B); h->mx_retry = 0; h->mx_retry_total = 0; rc |= dalloc(h->owned, &h->databad, B); rc |= dalloc(h->owned, &h->runq, B);
     rc |= dalloc(h->owned, &h->nom_st, B * 12); rc |= dalloc(h->owned, &h->nom_need_lin, B); rc |= dalloc(h->owned, &h->nom_status, B); rc |= dalloc(h->owned, &h->nom_iters, B);
     rc |= dalloc(h->owned, &h->mapA, (size_t)N * nx * nx); rc |= dalloc(h->owned, &h->mapB, (size_t)N * nx * nu);
     rc |= dalloc(h->owned, &h->inst_launches, (size_t)8); rc |= dalloc(h->owned, &h->chain_times, B * 4);
@@ -914,6 +915,45 @@ static void harvest_kernel_events(slsqp_handle *h) {
     h->n_kev = 0;
 }
 
+// Non-finite QP data of an instance, checked by passes of their own around a QP launch (folded into the QP kernels' setup, the check cost them
+// registers and 7 % of the closed-loop step): a NaN in q, in a box row or in a dynamics row, or +-inf in q or in a dynamics row (c).  +-inf in a box
+// row is no bound, like 1e20.  A NaN or +-inf in A or B as well.  Such an instance cannot certify (its solve is NaN, and the look and the certificate keep NaN), so it ends
+// unsolved and takes no part in the launch (its previous primal / dual stay); k_apply_nonfinite then records it as status 3, with the qp_stats of a flagged instance.  With a
+// NaN or infinite |q|inf every tolerance max(1,|q|inf) would be meaningless.
+__global__ __launch_bounds__(64) void k_flag_nonfinite(int n, int mb, int NX, int SR, int Ndyn, int nAB, const double *q, const double *ubg, const double *lbg,
+                                                        const double *A, const double *Bm, int nA, const int *run, int *bad, int *runq, int *alive, int *infeas) {
+    const int b = blockIdx.x;
+    int f = 0;
+    for (int e = threadIdx.x; e < n; e += 64) f |= !(fabs(q[(size_t)b * n + e]) < INFINITY);
+    for (int e = threadIdx.x; e < nAB; e += 64) f |= !(fabs(e < nA ? A[(size_t)b * nA + e] : Bm[(size_t)b * (nAB - nA) + e - nA]) < INFINITY);
+    for (int r = threadIdx.x; r < mb; r += 64) {
+        const double u = ubg[(size_t)b * mb + r], l = lbg[(size_t)b * mb + r];
+        if (r < Ndyn && r % SR < NX) f |= !(fabs(u) < INFINITY) | !(fabs(l) < INFINITY);
+        else f |= (u != u) | (l != l);
+    }
+    f = __syncthreads_or(f);
+    if (threadIdx.x == 0) {
+        bad[b] = f; runq[b] = (run ? run[b] : 1) && !f;
+        if (f && alive) { alive[b] = 0; infeas[b] = 1; }      // (the fused chain: the instance takes no part, its call fails)
+    }
+}
+__global__ void k_apply_nonfinite(int B, const int *bad, const int *run, int *status, int *qpstat, int stat_slot) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B || !bad[b] || (run && !run[b])) return;
+    status[b] = 3;
+    int *qs = qpstat + ((size_t)b * 2 + stat_slot) * 8;
+    for (int i = 0; i < 8; i++) qs[i] = 0;
+    qs[6] = 3;
+}
+static void apply_nonfinite(slsqp_handle *h, const int *run, int stat_slot) {
+    hipLaunchKernelGGL(k_apply_nonfinite, dim3((h->B + 255) / 256), dim3(256), 0, h->st, h->B, h->databad, run, h->status, h->qpstat, stat_slot);
+}
+static void flag_nonfinite(slsqp_handle *h, const int *run, int *alive = nullptr, int *infeas = nullptr) {
+    const int SR = h->d.nx + h->d.ni;
+    const int nA = h->d.N * h->d.nx * h->d.nx, nAB = nA + h->d.N * h->d.nx * h->d.nu;
+    hipLaunchKernelGGL(k_flag_nonfinite, dim3(h->B), dim3(64), 0, h->st, h->n, h->mb, h->d.nx, SR, h->d.N * SR, nAB, h->q, h->ubg, h->lbg, h->A, h->Bm, nA, run, h->databad, h->runq, alive, infeas);
+}
+
 // instances of `run` whose mixed-precision solve did not end on the KKT certificate are solved again in fp64
 __global__ void k_mark_retry(int B, const int *run, const int *status, int *retry, int *count) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -951,7 +991,8 @@ static QpArgs make_qp_args(slsqp_handle *h, const int *run, const slsqp_opts *o,
 
 static int launch_qp(slsqp_handle *h, const int *run, const slsqp_opts *o, int warm, const double *prox = nullptr, int stat_slot = 0, int snap_take = 0, int snap_use = 0,
                      int warm_shift = 0) {
-    const QpArgs a = make_qp_args(h, run, o, warm, prox, stat_slot, snap_take, snap_use, warm_shift);
+    flag_nonfinite(h, run);
+    const QpArgs a = make_qp_args(h, h->runq, o, warm, prox, stat_slot, snap_take, snap_use, warm_shift);
     const bool mx = o->precision == 1;
     h->time_kernels = o->time_kernels != 0;
     auto go = [&](const QpArgs &q, bool m) {
@@ -964,7 +1005,7 @@ static int launch_qp(slsqp_handle *h, const int *run, const slsqp_opts *o, int w
     h->mx_retry = 0;
     if (mx) {
         HIPCHK(hipMemsetAsync(h->counter + 3, 0, sizeof(int), h->st));
-        hipLaunchKernelGGL(k_mark_retry, dim3((h->B + 255) / 256), dim3(256), 0, h->st, h->B, run, h->status, h->retry, h->counter + 3);
+        hipLaunchKernelGGL(k_mark_retry, dim3((h->B + 255) / 256), dim3(256), 0, h->st, h->B, a.run, h->status, h->retry, h->counter + 3);
         int nretry = 0;
         HIPCHK(hipMemcpyAsync(&nretry, h->counter + 3, sizeof(int), hipMemcpyDeviceToHost, h->st));
         HIPCHK(hipStreamSynchronize(h->st));
@@ -975,6 +1016,7 @@ static int launch_qp(slsqp_handle *h, const int *run, const slsqp_opts *o, int w
             if (go(r, false)) return -1;
         }
     }
+    apply_nonfinite(h, run, stat_slot);
     return 0;
 }
 
@@ -1150,13 +1192,14 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
             c.qplog = h->qplog; c.stepno = h->cl_stepno; c.log_steps = h->qplog_steps;
             c.fin_count = (unsigned *)(h->t0word + 1); c.cut_count = h->cl_cut_count;
             HIPCHK(hipMemsetAsync(h->t0word, 0, 2 * sizeof(unsigned long long), h->st));
-        }
+        } else flag_nonfinite(h, active, h->alive, h->infeas);      // (slsqp_cl_run's rounds and k_cl_loop linearise their own data; the NaN-keeping certificate guards them)
         const int tl_c = tl_begin(h, 4);
         int rc = -1;
 #define X(NX_, NU_) if (d.nx == NX_ && d.nu == NU_) rc = launch_chain_t<NX_, NU_>(h, c);
         SLSQP_DIM_LIST
 #undef X
         if (rc) return -1;
+        if (!h->cl_round) apply_nonfinite(h, active, 0);      // (an instance flagged at QP #1 never reaches QP #2)
         tl_end(h, tl_c);
         if (h->chain_times_host) HIPCHK(hipMemcpyAsync(h->chain_times_host, h->chain_times, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
         tl_end(h, tl_tot);

@@ -23,6 +23,9 @@
 namespace slsqp {
 
 constexpr double BIGB = 1e19;   // |bound| above this is "infinite" (the reference maps +-inf to +-1e20, qp_jit.py:382)
+// max that does not drop a NaN (fmax and wla::wave_max do): a NaN counts as +inf, so a NaN residual or certificate quantity fails every
+// test against a tolerance.  Bitwise fmax for finite arguments.
+__device__ __forceinline__ double nan_max(double a, double b) { return fmax(a, b == b ? b : INFINITY); }
 constexpr double EPS_PIN = 1e-10;
 constexpr int ST_INIT = -1;
 
@@ -933,11 +936,11 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
                     CU[e] = zn; CL[e] = cl;
                 }
                 const double gr = el.pd * zn + el.q + cl, ac = ACT[e];
-                if (el.fr && ac == 0.0) tvst = fmax(tvst, fabs(gr));
-                if (el.fu) tvbox = fmax(tvbox, zn - el.hi);
-                if (el.fl) tvbox = fmax(tvbox, el.lo - zn);
-                if (ac > 0.0) tvsign = fmax(tvsign, gr);
-                if (ac < 0.0) tvsign = fmax(tvsign, -gr);
+                if (el.fr && ac == 0.0) tvst = nan_max(tvst, fabs(gr));
+                if (el.fu) tvbox = nan_max(tvbox, zn - el.hi);
+                if (el.fl) tvbox = nan_max(tvbox, el.lo - zn);
+                if (ac > 0.0) tvsign = nan_max(tvsign, gr);
+                if (ac < 0.0) tvsign = nan_max(tvsign, -gr);
                 double nac = ac;
                 if (ac > 0.0 && gr > tolv) nac = 0.5;          // 0.5: released in this round (reads as "not in the set" below, counts as a change)
                 if (ac < 0.0 && -gr > tolv) nac = 0.5;
@@ -1055,11 +1058,11 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
         for (int e = lane; e < n; e += 64) {
                 const Elem el = elem_of<NX, NU>(e, n, N, ub, qg, cst);
                 const double zn = CU[e], gr = el.pd * zn + el.q + CL[e], ac = ACT[e];
-                if (el.fr && ac == 0.0) vst = fmax(vst, fabs(gr));
-                if (el.fu) vbox = fmax(vbox, zn - el.hi);
-                if (el.fl) vbox = fmax(vbox, el.lo - zn);
-                if (ac > 0.0) vsign = fmax(vsign, gr);     // lambda_u = -gr must be >= 0
-                if (ac < 0.0) vsign = fmax(vsign, -gr);    // lambda_l = +gr must be >= 0
+                if (el.fr && ac == 0.0) vst = nan_max(vst, fabs(gr));
+                if (el.fu) vbox = nan_max(vbox, zn - el.hi);
+                if (el.fl) vbox = nan_max(vbox, el.lo - zn);
+                if (ac > 0.0) vsign = nan_max(vsign, gr);     // lambda_u = -gr must be >= 0
+                if (ac < 0.0) vsign = nan_max(vsign, -gr);    // lambda_l = +gr must be >= 0
             }
             vst = wla::wave_max(vst); vbox = wla::wave_max(vbox); vsign = wla::wave_max(vsign);
             s.pst = vst; s.psign = vsign;
