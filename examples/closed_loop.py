@@ -6,6 +6,7 @@ fast_sls_rti_steps, step counts and (rocket) seed-s disturbance streams; B indep
     python examples/closed_loop.py --model pendulum  [--runs 256]          # x0 = [0.5, 0.5, 0, 0], 60 steps, no noise (main_pendulum...:27-60,96)
     python examples/closed_loop.py --model quadrotor [--runs 256]          # random x0 around hover (the script's x0 is unseeded), 30 steps
     python examples/closed_loop.py --model rocket    [--runs 256] [--x0-scale 0.3]
+    ... --persistent 1                                                     # the same loop as ONE persistent launch (same bits)
 
 The first nominal comes from the GPU initialiser (slsqp_nominal_solve) in place of IPOPT."""
 import argparse
@@ -26,6 +27,8 @@ def main():
     ap.add_argument("--N", type=int, default=None)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--x0-scale", type=float, default=0.3, help="rocket: x0 = x_ref + s (x0_script - x_ref); quadrotor: spread around hover")
+    ap.add_argument("--persistent", type=int, default=0, choices=[0, 1],
+                    help="1: the whole loop as one persistent launch (slsqp_cl_run / slsqp_cl_run_scp: instances advance independently, same bits); 0: one slsqp_cl_step per step")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -47,7 +50,8 @@ def main():
         W = np.stack([disturbance_stream(s, steps, m.nx) for s in range(B)], axis=1)   # seed 0 = the script's stream
     cl = ClosedLoopMPC(m, N, B)
     t0 = time.perf_counter()
-    out = cl.run_on_device(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1)
+    run = cl.run_decoupled if a.persistent else cl.run_on_device
+    out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1)
     dt = time.perf_counter() - t0
     dist0 = np.linalg.norm(out["state_trajectory"][:, :, 0] - m.x_ref, axis=1).mean()
     dist1 = np.linalg.norm(out["state_trajectory"][:, :, -1] - m.x_ref, axis=1).mean()

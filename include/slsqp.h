@@ -173,7 +173,16 @@ int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc, const slsq
    log (slsqp_cl_log with max_steps >= steps, before slsqp_cl_init) and `log_qp_stats`[int32] (steps,2,8).  *rounds_out (may be NULL): rounds taken.
    With opts.cl_persistent (the default) there are no rounds at all: see slsqp_opts. */
 int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc, const slsqp_opts *opts, double budget_ms, double cut_frac, int *rounds_out);
-/* wave statistics of the last persistent slsqp_cl_run: [0] wavefronts launched, [1] sum over the MPC steps of the time a wavefront spent on them (ms),
+/* `steps` MPC steps of every instance as ONE persistent launch, for any SCP setting of slsqp_cl_step (SCP_SLS.solve, SCP_SLS_jit.py:103-135):
+   rti > 0: exactly rti SCP iterations per MPC step; rti <= 0: converge mode (opts.scp_eps, opts.max_scp_iter), every instance leaving the loop at
+   its own iteration.  opts.rti_steps >= 1 fast-SLS steps per solve (fast_SLS.solve in RTI mode, fast_SLS_jit.py:278-296; fp64, box constraints,
+   fused chain allowed); fast-SLS converge mode (rti_steps <= 0) and precision = 1 are refused.
+   Same operations per instance in the same order as `steps` calls of slsqp_cl_step(h, rti, ...): same bits.  rti = 1 with rti_steps = 1 runs
+   slsqp_cl_run's persistent kernel.  Results as for slsqp_cl_run: the device-side log, the final state, slsqp_cl_run_stats and `log_qp_stats`
+   (steps,2,8), which holds per MPC step what `qp_stats` holds after the corresponding slsqp_cl_step (converge mode: an instance that left the SCP
+   loop before the last instance of the batch did has its slots marked "took no part", status -1, as the batch-wide launches leave them). */
+int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const double *W, int loc, const slsqp_opts *opts);
+/* wave statistics of the last persistent slsqp_cl_run / slsqp_cl_run_scp: [0] wavefronts launched, [1] sum over the MPC steps of the time a wavefront spent on them (ms),
    [2] MPC steps run, [3] duration of the launch (ms, HIP events; 0 without opts.time_kernels).  [1] / ([0] x [3]) = how busy the queue kept the waves. */
 #define SLSQP_CL_RUN_STATS_LEN 4
 int slsqp_cl_run_stats(slsqp_handle *h, double *out, int len);

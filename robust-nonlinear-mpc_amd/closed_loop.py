@@ -112,20 +112,27 @@ class ClosedLoopMPC:
         )
 
     def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0):
-        """Same results as run_on_device() -- bit for bit -- through slsqp_cl_run: the instances advance through their MPC steps independently (a
-        chain of QP solves that is not done budget_ms after its launch started suspends itself and resumes in the next round), so nobody waits for the
-        slowest instance of a step.  With opts.cl_persistent (the default) the whole loop is ONE launch: waves take instances from a device-side
-        FIFO and run one MPC step each time; budget_ms / cut_frac only matter for opts.cl_persistent = 0.  Only for the rocket script's setting
-        (rti = 1, one fast-SLS step, fp64).  Adds `qp_stats` (B, steps, 2, 8), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the
-        run's totals in their first entry."""
+        """Same results as run_on_device() -- bit for bit -- with the instances advancing through their MPC steps independently, so nobody waits for
+        the slowest instance of a step.
+        rti = 1 with one fast-SLS step (the rocket script's setting): slsqp_cl_run.  With opts.cl_persistent (the default) the whole loop is ONE launch:
+        waves take instances from a device-side FIFO and run one MPC step each time; with opts.cl_persistent = 0 it runs in rounds (a chain of QP
+        solves that is not done budget_ms after its launch started suspends itself and resumes in the next round; cut_frac: see slsqp_cl_run).
+        Every other setting slsqp_cl_step takes with a fixed number of fast-SLS steps (rti > 1, SCP converge mode rti <= 0, rti_steps > 1: the
+        pendulum and quadrotor scripts, SCP_SLS's default): slsqp_cl_run_scp, always one persistent launch (budget_ms / cut_frac ignored).  Fast-SLS
+        converge mode (fast_sls_rti_steps None), precision = 1 and SLSQP_FUSE_RTI=0 are refused with the library's message.
+        Adds `qp_stats` (B, steps, 2, 8), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the run's totals in their first entry."""
         f, m, N, B = self.f, self.m, self.N, self.B
-        assert self.rti == 1, "slsqp_cl_run runs rti = 1 closed loops"
         L.check(f.lib.slsqp_cl_log(f.h, int(steps)))
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
         Wc = None if W is None else _c(W)
         assert Wc is None or Wc.shape == (steps, B, m.nx)
         rounds = C.c_int(0)
-        L.check(f.lib.slsqp_cl_run(f.h, int(steps), _ptr(Wc), L.HOST, C.byref(f.opts), float(budget_ms), float(cut_frac), C.byref(rounds)))
+        one_by_one = self.rti == 1 and f.opts.rti_steps == 1
+        if one_by_one:
+            L.check(f.lib.slsqp_cl_run(f.h, int(steps), _ptr(Wc), L.HOST, C.byref(f.opts), float(budget_ms), float(cut_frac), C.byref(rounds)))
+        else:
+            L.check(f.lib.slsqp_cl_run_scp(f.h, int(steps), self.rti, _ptr(Wc), L.HOST, C.byref(f.opts)))
+            rounds.value = 1
         self.steps_done = steps
         t = f.timing_ms()
         t_qp, t_ric, t_jac = np.zeros((steps, 1)), np.zeros((steps, 1)), np.zeros((steps, 1))
@@ -133,7 +140,7 @@ class ClosedLoopMPC:
         out = self._log_result(steps, t_jac, t_qp, t_ric)
         out["qp_stats"] = f.get("log_qp_stats", (steps, 2, 8), np.int32)
         out["rounds"] = rounds.value
-        if f.opts.cl_persistent:      # one persistent launch: how busy the instance queue kept the waves
+        if f.opts.cl_persistent or not one_by_one:      # one persistent launch: how busy the instance queue kept the waves
             st = (C.c_double * L.CL_RUN_STATS_LEN)()
             L.check(f.lib.slsqp_cl_run_stats(f.h, st, L.CL_RUN_STATS_LEN))
             out["loop_stats"] = dict(waves=int(st[0]), busy_ms=float(st[1]), mpc_steps=int(st[2]), launch_ms=float(st[3]))

@@ -55,7 +55,7 @@ struct slsqp_handle {
     // slsqp_cl_run: per-instance progress through the closed loop (step counter, suspended-solve state, round masks), per-instance call ids, the launch's
     // start-time word, the per-step copy of qp_stats
     int *cl_stepno = nullptr, *cl_lag = nullptr, *cl_begin = nullptr, *cl_runm = nullptr, *cl_done = nullptr, *cl_skipb = nullptr, *cl_skip_begin = nullptr, *qplog = nullptr;
-    double *call_ids = nullptr, *cl_W = nullptr; size_t cl_W_doubles = 0; unsigned long long *t0word = nullptr; int qplog_steps = 0;
+    double *call_ids = nullptr, *cl_W = nullptr; size_t cl_W_doubles = 0; unsigned long long *t0word = nullptr; int qplog_steps = 0, qplog_cap = 0, *qplog_nsolves = nullptr;      // qplog: capacity in steps, steps of the current run; solves per (instance, step) (k_cl_loop_scp)
     int *clq_slots = nullptr, *clq_ctl = nullptr; unsigned clq_cap = 0; int cl_loop_waves = 0; double cl_loop_ms = 0.0; unsigned long long *cl_busy = nullptr, *cl_tbegin = nullptr, cl_busy_host[16] = {};      // k_cl_loop: instance FIFO (slots; head, tail, avail, err), wave life-time counters
     bool cl_round = false; unsigned long long cl_budget = 0; int cl_total_steps = 0; unsigned cl_cut_count = 0xFFFFFFFFu;
     unsigned long long *chain_times = nullptr, *chain_times_host = nullptr;   // (B,4) in-kernel wall-clock ticks per instance; pinned copy of instance 0's
@@ -239,6 +239,7 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     if (h->stage) hipFree(h->stage);
     if (h->cl_W) hipFree(h->cl_W);
     if (h->qplog) hipFree(h->qplog);
+    if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
     if (h->chain_times_host) hipHostFree(h->chain_times_host);
     for (auto &e : h->ev) hipEventDestroy(e);
     for (auto &e : h->tl) hipEventDestroy(e);
@@ -825,6 +826,194 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(LoopA
 #ifdef CL_LOOP_STAMP
     if (lane == 0) { const unsigned long long te_ = wall_clock64(); atomicAdd(L.busy + 13, te_ - tw0_); atomicMax(L.busy + 15, te_); atomicAdd(L.busy + 1, 1ULL); }
 #endif
+}
+
+// ---- the persistent loop for any SCP setting of slsqp_cl_step (slsqp_cl_run_scp) -------------------------------------------------------
+// One queue item is still one whole MPC step of one instance, but the step is the general one: max_it SCP iterations (SCP_SLS.solve,
+// SCP_SLS_jit.py:103-135), each a fast-SLS solve of rti_steps steps (fast_SLS.solve, fast_SLS_jit.py:278-296) -- what slsqp_cl_step and solve_impl
+// launch for the batch, here per instance by the wave that holds it, same device functions in the same order.  A kernel of its own: k_cl_loop
+// (one iteration, one step) keeps its code object.
+//   fixed rti: every instance runs its rti iterations; one whose step failed is masked through scp_active for the remaining ones exactly as the
+//     launches mask it (linearisation skipped, solve start / QPs / finish see it as "takes no part", no nominal update);
+//   converge mode (rti <= 0): an instance leaves as soon as cl_scp_update_wave clears its scp_active (converged or failed) -- the batch-wide
+//     launches go on until the last instance has left and, for the ones that left earlier, only rewrite their qp_stats slots as "took no part".
+//     nsolves (B, steps) keeps the number of solves each step of each instance ran, from which k_cl_qplog_masked reproduces that afterwards.
+struct ScpLoopArgs {
+    LoopArgs L;
+    int max_it, converge, rti_steps;
+    int *nsolves;
+};
+// shift + solver reset past the first step, SCP flags of the step (slsqp_cl_step's preamble)
+template <int MODEL>
+__device__ CLW_FN void cl_scp_step_begin(const LoopArgs &L, int b, int lane) {
+    const int s = L.stepno[b];
+    if (lane == 0) L.t_begin[b] = wall_clock64();
+    if (s > 0) {
+        cl_shift_wave<MODEL>(L.cl, b, lane);
+        for (int o = lane; o < L.n; o += 64) L.q[(size_t)b * L.n + o] = 0.0;
+        const int st = L.stale[b];
+        wla::wsync_mem();
+        if (lane == 0) { L.stale[b] = (st & 8) | 3; L.itnum[b] = 0; L.pending[b] = 0; }
+    }
+    if (lane == 0) { L.scp_active[b] = 1; L.sa.scp_success[b] = 0; L.sa.scp_iters[b] = 0; }
+    wla::wsync_mem();
+}
+// start of SCP iteration ii: linearisation (instances still iterating), x0 pin, call id, solve start
+template <int MODEL>
+__device__ CLW_FN void cl_scp_iter_begin(const LoopArgs &L, int b, int lane, int ii) {
+    constexpr int NX = dyn::Dims<MODEL>::NX;
+    const int act = __builtin_amdgcn_readfirstlane(L.scp_active[b]);
+    if (ii == 0 || act) lin_wave<MODEL>(L.lin, L.ba, b, lane);
+    if (lane < NX) L.cl.x0arg[(size_t)b * NX + lane] = L.cl.Xn[(size_t)b * (L.cl.N + 1) * NX + lane] - L.cl.xmeas[(size_t)b * NX + lane];
+    if (lane == 0) L.call_ids[b] += 1.0;
+    wla::wsync_mem();
+    solve_begin_wave(L.sb, b, lane);
+    wla::wsync_mem();
+}
+// end of SCP iteration ii: nominal += delta / the instance leaves the loop, primal infeasibility; returns 1 while the instance is still iterating
+template <int MODEL>
+__device__ CLW_FN int cl_scp_iter_end(const LoopArgs &L, int b, int lane, int ii, int converge) {
+    ScpArgs sa = L.sa;
+    sa.ii = ii; sa.converge = converge;
+    cl_scp_update_wave(L.cl, sa, b, lane);
+    wla::wsync_mem();
+    if (L.sa.updated[b]) cl_infeas_wave<MODEL>(L.cl, L.pinf, b, lane);
+    wla::wsync_mem();
+    return L.scp_active[b];
+}
+// log entries, plant step + noise, step counter; returns the instance's new step count while it has steps left, else 0
+template <int MODEL>
+__device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S, int b, int lane, int nsolves) {
+    const LoopArgs &L = S.L;
+    constexpr int NX = dyn::Dims<MODEL>::NX;
+    const int s = L.stepno[b];
+    if (L.have_log) {
+        const int per = 2 * ((L.lg.N + 1) * L.lg.NX + L.lg.N * L.lg.NU);
+        for (int o = lane; o < per; o += 64) cl_log_item(L.lg, b, o);
+    }
+    if (L.c.qplog && s < L.c.log_steps) {
+        if (lane < 16) L.c.qplog[((size_t)b * L.c.log_steps + s) * 16 + lane] = L.c.q1.qpstat[(size_t)b * 16 + lane];
+        if (lane == 0) S.nsolves[(size_t)b * L.c.log_steps + s] = nsolves;
+    }
+    if (lane == 0) {
+        cl_plant_one<MODEL>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr);
+        L.stepno[b] = s + 1;
+        if (L.busy) { atomicAdd(L.busy, wall_clock64() - L.t_begin[b]); atomicAdd(L.busy + 2, 1ULL); }
+    }
+    wla::wsync_mem();
+    return (s + 1 < L.steps) ? s + 1 : 0;
+}
+// one fast-SLS solve of rti_steps steps of one instance by one wave: what solve_impl launches (fast_SLS_jit.py:278-296).  QP i of the call gets the
+// arguments launch_qp builds for it: the first one q1's (warm per opts.warm_start, slot 0, no iterate copy to restart from), the middle ones warm,
+// slot 0, restart allowed, the last one q2's; the horizon shift only reaches the first and the last QP of the first solve after the shift
+template <int NX, int NU>
+__device__ __forceinline__ void sls_solve_dev(const ChainArgs &c, int b, int lane, double *sm, int rti_steps, int shifted) {
+#pragma unroll 1
+    for (int i = 0; i <= rti_steps; i++) {
+        asm volatile("" : "+v"(lane));
+        {
+            QpArgs q = c.q1;
+            q.warm = i > 0 ? 1 : c.q1.warm;
+            q.stat_slot = i == rti_steps ? 1 : 0;
+            q.snap_use = i > 0 ? c.q2.snap_use : 0;
+            q.warm_shift = (shifted && (i == 0 || i == rti_steps)) ? c.q1.warm_shift : 0;
+            qp_solve_dev<NX, NU, false>(q, b, lane, sm, c.max_ticks);
+        }
+        wla::wsync_mem();
+        if (i == rti_steps) break;
+        asm volatile("" : "+v"(lane));
+        AfterQpArgs aq = c.aq;
+        aq.first_iter = i == 0 ? 1 : 0; aq.ea.first_iter = aq.first_iter;
+        const int m = __builtin_amdgcn_readfirstlane(after_qp_wave(aq, b, lane));
+        wla::wsync_mem();
+        if (!m) continue;
+        if (i == 0) {      // beta = eps in every column: one Riccati recursion for all of them
+            sweep_ric1_dev<NX, NU>(c.sw, b, lane, sm);
+            wla::wsync_mem();
+#pragma unroll 1
+            for (int j = 0; j <= c.sw.s.N; j += 2) {
+                asm volatile("" : "+v"(lane));
+                sweep_prop_dev<NX, NU>(c.sw, b, j, min(2, c.sw.s.N + 1 - j), lane, sm);
+                wla::wsync();
+            }
+        } else {
+#pragma unroll 1
+            for (int j = 0; j <= c.sw.s.N; j++) {      // the general sweep, column by column
+                asm volatile("" : "+v"(lane));
+                sweep_col_dev<NX, NU>(c.sw.s, b, j, lane, sm);
+                wla::wsync();
+            }
+        }
+        wla::wsync_mem();
+        tighten_dev(c.ta, b, lane, 64);
+        wla::wsync_mem();
+    }
+    if (lane == 0) {
+        if (c.active && !c.active[b]) c.success[b] = 0;
+        else c.success[b] = (!c.infeas[b]) || c.success[b];           // fast_SLS_jit.py:295 (k_finish, RTI)
+    }
+    wla::wsync_mem();
+}
+template <int MODEL>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(ScpLoopArgs S) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    const LoopArgs &L = S.L;
+    int lane = threadIdx.x;
+    extern __shared__ double sm[];
+    int b = -1;
+#pragma unroll 1
+    for (;;) {
+        asm volatile("" : "+v"(lane));
+        if (b < 0) {
+            b = clq_pop(L.Q, lane);
+            if (b < 0) break;
+            if (L.fence & 1) __threadfence();
+        }
+        cl_scp_step_begin<MODEL>(L, b, lane);
+        b = __builtin_amdgcn_readfirstlane(b);
+        int nsolves = 0;
+#pragma unroll 1
+        for (int ii = 0; ii < S.max_it; ii++) {
+            asm volatile("" : "+v"(lane));
+            cl_scp_iter_begin<MODEL>(L, b, lane, ii);
+            b = __builtin_amdgcn_readfirstlane(b);
+            asm volatile("" : "+v"(lane));
+            sls_solve_dev<NX, NU>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0);
+            asm volatile("" : "+v"(lane));
+            const int act = __builtin_amdgcn_readfirstlane(cl_scp_iter_end<MODEL>(L, b, lane, ii, S.converge));
+            b = __builtin_amdgcn_readfirstlane(b);
+            nsolves = ii + 1;
+            if (S.converge && !act) break;
+        }
+        asm volatile("" : "+v"(lane));
+        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL>(S, b, lane, nsolves));
+        b = __builtin_amdgcn_readfirstlane(b);
+        if (!next) { b = -1; continue; }
+        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
+        if (behind && L.keep_laggards) continue;
+        if (L.fence & 2) __threadfence();
+        clq_push(L.Q, b, lane);
+        b = -1;
+    }
+}
+// converge mode: the batch-wide launches of step s run max over the instances of their solves; an instance that left earlier has its qp_stats
+// slots rewritten as "took no part" (status -1) by the QP launches that follow.  One block per step.
+__global__ void k_cl_qplog_masked(int B, int steps, int log_steps, const int *nsolves, int *qplog) {
+    const int s = blockIdx.x;
+    __shared__ int smax;
+    if (threadIdx.x == 0) smax = 0;
+    __syncthreads();
+    int mx = 0;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) mx = max(mx, nsolves[(size_t)b * log_steps + s]);
+    atomicMax(&smax, mx);
+    __syncthreads();
+    mx = smax;
+    for (int b = threadIdx.x; b < B; b += blockDim.x)
+        if (nsolves[(size_t)b * log_steps + s] < mx) {
+            int *qs = qplog + ((size_t)b * log_steps + s) * 16;
+            for (int i = 0; i < 16; i++) qs[i] = (i % 8 == 6) ? -1 : 0;
+        }
 }
 
 // ---- masked pieces of a closed-loop round (slsqp_cl_run) ----
@@ -1568,7 +1757,7 @@ __global__ void k_cl_begin_flags(int B, const int *begin, int *scp_success, int 
 }
 // the persistent closed-loop launch (k_cl_loop): as many waves as the GPU holds at the kernel's occupancy (or as there are instances)
 template <int MODEL>
-static int launch_loop_t(slsqp_handle *h, LoopArgs &L) {
+static int launch_loop_t(slsqp_handle *h, LoopArgs &L, const ScpLoopArgs *S = nullptr) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     const size_t lds = sizeof(double) * std::max({(size_t)qp_lds_doubles<NX, NU>(h->d.N), (size_t)(2 * h->n + 8), (size_t)sweep_lds_doubles<NX, NU>(), (size_t)sweep_prop_lds_doubles<NX, NU>()});
     int cu = 0;
@@ -1580,13 +1769,16 @@ static int launch_loop_t(slsqp_handle *h, LoopArgs &L) {
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     hipEventRecord(h->ev[8], h->st);
-    hipLaunchKernelGGL((k_cl_loop<MODEL>), dim3(grid), dim3(64), lds, h->st, L);
+    if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL>), dim3(grid), dim3(64), lds, h->st, *S);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
+    else hipLaunchKernelGGL((k_cl_loop<MODEL>), dim3(grid), dim3(64), lds, h->st, L);
     hipEventRecord(h->ev[9], h->st);
     if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
     HIPCHK(hipGetLastError());
     return 0;
 }
-static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out) {
+// scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp)
+static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out, bool scp = false, int scp_rti = 1) {
+    const int max_it = !scp ? 1 : (scp_rti > 0 ? scp_rti : o.max_scp_iter);
     const slsqp_dims &d = h->d;
     const int B = h->B;
     if (!h->beta_inited) {      // what the handle's first solve does once: beta = eps everywhere (later solves only repair swept instances)
@@ -1596,16 +1788,17 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     }
     h->time_kernels = o.time_kernels != 0;
     LoopArgs L;
-    L.c = make_chain_args(h, o, nullptr, 1);
+    const int *active = scp ? h->scp_active : nullptr;      // (k_cl_loop_scp masks an instance whose step failed for the rest of its MPC step, as slsqp_cl_step does)
+    L.c = make_chain_args(h, o, active, 1);
     L.c.q1.call_ids = L.c.q2.call_ids = h->call_ids;
     L.c.q1.shift_stepno = L.c.q2.shift_stepno = h->cl_stepno;      // the horizon has moved for the instances past their first step
     L.c.qplog = h->qplog; L.c.stepno = h->cl_stepno; L.c.log_steps = h->qplog_steps;
     L.cl = cl_args(h, nullptr);
     L.lin = LinArgs{B, d.N, h->Xn, h->Un, h->g_raw, h->gf_raw, costs_of(h), h->A, h->Bm, h->c, h->g, h->gN, h->q, nullptr, h->lin_stage, h->lin_tape};
     L.ba = BoundsArgs{B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, nullptr};
-    L.sb = SolveBeginArgs{B, d.nx, h->x0arg, h->x0val, nullptr, h->alive, h->infeas, h->success, h->pending_reset, h->itnum, h->stale,
+    L.sb = SolveBeginArgs{B, d.nx, h->x0arg, h->x0val, active, h->alive, h->infeas, h->success, h->pending_reset, h->itnum, h->stale,
                           h->eta, h->eta_f, (size_t)d.N * d.N * d.ni, (size_t)(d.N + 1) * d.ni_f,
-                          InitBackoffArgs{B, d.N, d.nx, d.nu, o.eps_backoff, nullptr, h->beta, h->beta_f, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, 0}, nullptr};
+                          InitBackoffArgs{B, d.N, d.nx, d.nu, o.eps_backoff, active, h->beta, h->beta_f, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, 0}, nullptr};
     L.lg = ClLogArgs{h->cl_stepno, nullptr, B, d.N, d.nx, d.nu, h->log_steps, 0, h->Xn, h->Un, h->backoff_x, h->backoff_u, h->scp_success, h->scp_iters,
                      h->pinf, h->lg_x, h->lg_u, h->lg_bx, h->lg_bu, h->lg_state, h->lg_u0, h->lg_pinf, h->lg_succ, h->lg_it};
     L.sa = ScpArgs{0, 0, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
@@ -1622,17 +1815,23 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
     const int tl_tot = tl_begin(h, 2), tl_c = tl_begin(h, 4);
     int rc = -1;
-    if (h->model_id == 0) rc = launch_loop_t<0>(h, L);
-    else if (h->model_id == 1) rc = launch_loop_t<1>(h, L);
-    else rc = launch_loop_t<2>(h, L);
+    ScpLoopArgs S{L, max_it, scp_rti <= 0 ? 1 : 0, o.rti_steps, h->qplog_nsolves};
+    const ScpLoopArgs *Sp = scp ? &S : nullptr;
+    if (h->model_id == 0) rc = launch_loop_t<0>(h, L, Sp);
+    else if (h->model_id == 1) rc = launch_loop_t<1>(h, L, Sp);
+    else rc = launch_loop_t<2>(h, L, Sp);
     if (rc) return -1;
+    if (scp && S.converge) hipLaunchKernelGGL(k_cl_qplog_masked, dim3(steps), dim3(256), 0, h->st, B, steps, h->qplog_steps, h->qplog_nsolves, h->qplog);
     tl_end(h, tl_c); tl_end(h, tl_tot);
     int ctl[4] = {0, 0, 0, 0};
     std::vector<int> sn((size_t)B);
     HIPCHK(hipMemcpyAsync(ctl, h->clq_ctl, sizeof(ctl), hipMemcpyDeviceToHost, h->st));
     HIPCHK(hipMemcpyAsync(sn.data(), h->cl_stepno, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, h->st));
     HIPCHK(hipMemcpyAsync(h->cl_busy_host, h->cl_busy, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
-    if (h->chain_times_host) HIPCHK(hipMemcpyAsync(h->chain_times_host, h->chain_times, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
+    if (h->chain_times_host) {
+        if (scp) memset(h->chain_times_host, 0, 4 * sizeof(unsigned long long));      // (no per-part clock in the general step: the launch counts as QP time)
+        else HIPCHK(hipMemcpyAsync(h->chain_times_host, h->chain_times, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
+    }
     HIPCHK(hipStreamSynchronize(h->st));
     tl_take(h);
     h->cl_loop_ms = ev_ms(h->ev[8], h->ev[9]);
@@ -1642,7 +1841,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     if (ctl[3] != 0 || unfinished != 0)
         return fail("slsqp_cl_run (persistent): the instance queue did not drain (err " + std::to_string(ctl[3]) + ", " + std::to_string(unfinished) + " instances short of their steps)");
     h->cl_steps = steps;
-    h->call_id += steps;
+    h->call_id += (double)steps * max_it;
     if (rounds_out) *rounds_out = 1;
     return 0;
 }
@@ -1653,6 +1852,39 @@ extern "C" int slsqp_cl_run_stats(slsqp_handle *h, double *out, int len) {
     out[0] = (double)h->cl_loop_waves; out[1] = (double)h->cl_busy_host[0] * 1e-5; out[2] = (double)h->cl_busy_host[2]; out[3] = h->cl_loop_ms;
     for (int i = 4; i < 16 && i < len; i++) out[i] = (double)h->cl_busy_host[i] * 1e-5;
     if (len >= 16) { out[14] = (double)(h->cl_busy_host[15] - h->cl_busy_host[14]) * 1e-5; out[15] = (double)h->cl_busy_host[1]; }      // first wave start -> last wave exit; waves that ran      // -DCL_LOOP_STAMP builds: ms spent in the parts of the step around the chain
+    return 0;
+}
+
+// what both closed-loop entry points do before their loop: disturbance samples on the device, the per-step qp_stats log of THIS run (registered and
+// indexed with the run's own step count; the allocation only grows), step counters, call ids
+static int cl_run_prepare(slsqp_handle *h, int steps, const double *W, int loc, const double **dW_out) {
+    const slsqp_dims &d = h->d;
+    const int B = h->B;
+    const double *dW = nullptr;
+    if (W) {
+        const size_t nW = (size_t)steps * B * d.nx;
+        if (loc == SLSQP_HOST) {
+            if (nW > h->cl_W_doubles) { if (h->cl_W) hipFree(h->cl_W); h->cl_W = nullptr; h->cl_W_doubles = 0; HIPCHK(hipMalloc((void **)&h->cl_W, nW * sizeof(double) + 64)); h->cl_W_doubles = nW; }
+            HIPCHK(hipMemcpyAsync(h->cl_W, W, nW * sizeof(double), hipMemcpyHostToDevice, h->st));
+            dW = h->cl_W;
+        } else dW = W;
+    }
+    if (h->qplog_cap < steps) {
+        if (h->qplog) hipFree(h->qplog);
+        if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
+        h->qplog = nullptr; h->qplog_nsolves = nullptr; h->qplog_cap = 0; h->qplog_steps = 0;
+        HIPCHK(hipMalloc((void **)&h->qplog, (size_t)B * steps * 16 * sizeof(int) + 64));
+        HIPCHK(hipMalloc((void **)&h->qplog_nsolves, (size_t)B * steps * sizeof(int) + 64));
+        h->qplog_cap = steps;
+    }
+    h->qplog_steps = steps;
+    HIPCHK(hipMemsetAsync(h->qplog, 0, (size_t)B * steps * 16 * sizeof(int), h->st));
+    HIPCHK(hipMemsetAsync(h->qplog_nsolves, 0, (size_t)B * steps * sizeof(int), h->st));
+    h->named["log_qp_stats"] = {h->qplog, sizeof(int) * 16 * (size_t)steps};
+    HIPCHK(hipMemsetAsync(h->cl_stepno, 0, sizeof(int) * B, h->st));
+    HIPCHK(hipMemsetAsync(h->cl_lag, 0, sizeof(int) * B, h->st));
+    hipLaunchKernelGGL(k_fill_doubles, dim3(64), dim3(256), 0, h->st, h->call_ids, h->call_id, (size_t)B);
+    *dW_out = dW;
     return 0;
 }
 
@@ -1677,25 +1909,7 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
     const slsqp_dims &d = h->d;
     const int B = h->B, gbi = (B + 255) / 256, gb = (B + 63) / 64;
     const double *dW = nullptr;
-    if (W) {
-        const size_t nW = (size_t)steps * B * d.nx;
-        if (loc == SLSQP_HOST) {
-            if (nW > h->cl_W_doubles) { if (h->cl_W) hipFree(h->cl_W); h->cl_W = nullptr; h->cl_W_doubles = 0; HIPCHK(hipMalloc((void **)&h->cl_W, nW * sizeof(double) + 64)); h->cl_W_doubles = nW; }
-            HIPCHK(hipMemcpyAsync(h->cl_W, W, nW * sizeof(double), hipMemcpyHostToDevice, h->st));
-            dW = h->cl_W;
-        } else dW = W;
-    }
-    if (h->qplog_steps < steps) {
-        if (h->qplog) hipFree(h->qplog);
-        h->qplog = nullptr; h->qplog_steps = 0;
-        HIPCHK(hipMalloc((void **)&h->qplog, (size_t)B * steps * 16 * sizeof(int) + 64));
-        h->qplog_steps = steps;
-    }
-    HIPCHK(hipMemsetAsync(h->qplog, 0, (size_t)B * h->qplog_steps * 16 * sizeof(int), h->st));
-    h->named["log_qp_stats"] = {h->qplog, sizeof(int) * 16 * (size_t)h->qplog_steps};
-    HIPCHK(hipMemsetAsync(h->cl_stepno, 0, sizeof(int) * B, h->st));
-    HIPCHK(hipMemsetAsync(h->cl_lag, 0, sizeof(int) * B, h->st));
-    hipLaunchKernelGGL(k_fill_doubles, dim3(64), dim3(256), 0, h->st, h->call_ids, h->call_id, (size_t)B);
+    if (cl_run_prepare(h, steps, W, loc, &dW)) return -1;
     if (o.cl_persistent) return cl_run_persistent(h, steps, dW, o, rounds_out);
     h->cl_budget = budget_ms > 0.0 ? (unsigned long long)(std::max(0.05, budget_ms) * 1e5) : (1ULL << 62);
     h->cl_total_steps = steps;
@@ -1755,6 +1969,29 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
     h->call_id += steps;
     if (rounds_out) *rounds_out = rounds;
     return 0;
+}
+
+// `steps` MPC steps of every instance as ONE persistent launch for any SCP setting of slsqp_cl_step (SCP_SLS.solve, SCP_SLS_jit.py:103-135, around
+// fast_SLS.solve in RTI mode, fast_SLS_jit.py:278-296): rti > 0 -> exactly rti SCP iterations per MPC step, rti <= 0 -> converge mode
+// (opts.scp_eps, opts.max_scp_iter), opts.rti_steps >= 1 fast-SLS steps per solve.  Per instance the same operations in the same order as
+// `steps` calls of slsqp_cl_step(h, rti, ...): same bits.  rti = 1 with rti_steps = 1 is slsqp_cl_run's own kernel.
+extern "C" int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const double *W, int loc, const slsqp_opts *opts) {
+    hipSetDevice(h->dev);
+    if (h->model_id < 0) return fail("slsqp_set_model must be called first");
+    if (h->cl_steps != 0) return fail("slsqp_cl_run_scp starts a closed loop: call slsqp_cl_init first");
+    if (steps < 1) return fail("slsqp_cl_run_scp: steps must be >= 1");
+    if (h->log_steps > 0 && h->log_steps < steps) return fail("slsqp_cl_run_scp: the device-side log (slsqp_cl_log) is shorter than the run");
+    slsqp_opts o;
+    if (opts) o = *opts; else slsqp_default_opts(&o);
+    if (o.rti_steps <= 0) return fail("slsqp_cl_run_scp: fast-SLS converge mode (rti_steps <= 0) does not run inside the persistent loop (use slsqp_cl_step)");
+    if (o.precision != 0) return fail("slsqp_cl_run_scp: mixed precision (precision = 1) does not run inside the persistent loop: fp64 only (use slsqp_cl_step)");
+    if (h->general_G) return fail("slsqp_cl_run_scp: box constraints only (general G: use the sweep-level boundary)");
+    if (!(o.fuse_rti && chain_allowed() && sweep_shared_allowed())) return fail("slsqp_cl_run_scp needs the fused chain: fuse_rti = 1, SLSQP_FUSE_RTI and SLSQP_SWEEP_SHARED not 0 (use slsqp_cl_step otherwise)");
+    if (rti <= 0 && o.max_scp_iter < 1) return fail("slsqp_cl_run_scp: converge mode needs max_scp_iter >= 1");
+    const double *dW = nullptr;
+    if (cl_run_prepare(h, steps, W, loc, &dW)) return -1;
+    if (rti == 1 && o.rti_steps == 1) return cl_run_persistent(h, steps, dW, o, nullptr);
+    return cl_run_persistent(h, steps, dW, o, nullptr, true, rti);
 }
 
 // ---- QP-level boundary (osqp_generated look-alike, batched) -------------------------------------------------

@@ -1453,29 +1453,12 @@ __host__ __device__ constexpr int sweep_lds_doubles() {
 #ifndef SWEEP_WAVES_PER_SIMD
 #define SWEEP_WAVES_PER_SIMD 3
 #endif
+// disturbance column j of instance b by one wave (k_sweep: one wave per column; k_cl_loop_scp: one wave walks the columns of its instance)
 template <int NX, int NU>
-__global__ __launch_bounds__(64, SWEEP_WAVES_PER_SIMD) void k_sweep(SweepArgs a) {
+__device__ __forceinline__ void sweep_col_dev(const SweepArgs &a, int b, int j, int lane, double *sm) {
     using L = Lay<NX, NU>;
     constexpr int NZ = L::NZ, NI = L::NI, NIF = L::NIF, NW = NX;
-    const int N = a.N, lane = threadIdx.x;
-    // XCD-aware mapping: blocks i and i+8 share an XCD; keep all columns of an instance on one XCD so its
-    // A_k/B_k stay in that XCD's L2 (speed only; any mapping is correct).
-    const int ncol = N + 1;
-    int b, j;
-    {
-        const int bid = blockIdx.x;
-        const int Bfull = (a.B / 8) * 8;
-        if (bid < Bfull * ncol) {
-            const int xcd = bid % 8, slot = bid / 8;
-            b = (slot / ncol) * 8 + xcd; j = slot % ncol;
-        } else {
-            const int r = bid - Bfull * ncol;
-            b = Bfull + r / ncol; j = r % ncol;
-        }
-    }
-    if (b >= a.B) return;
-    if (a.run && !a.run[b]) return;
-    extern __shared__ double sm[];
+    const int N = a.N;
     double *p = sm;
     double *sA = p; p += NX * NX; double *sS = p; p += NX * NX; double *sYm = p; p += NX * NX;
     double *sAcl = sA;                     // A + B K replaces A_k in place (every use of A_k precedes it)
@@ -1671,6 +1654,29 @@ __global__ __launch_bounds__(64, SWEEP_WAVES_PER_SIMD) void k_sweep(SweepArgs a)
     }
     ctube = wla::wave_sum(ctube);
     if (lane == 0 && a.ct_part) a.ct_part[(size_t)b * (N + 1) + j] = ctube;
+}
+template <int NX, int NU>
+__global__ __launch_bounds__(64, SWEEP_WAVES_PER_SIMD) void k_sweep(SweepArgs a) {
+    const int N = a.N, lane = threadIdx.x;
+    // XCD-aware mapping: blocks i and i+8 share an XCD; keep all columns of an instance on one XCD so its
+    // A_k/B_k stay in that XCD's L2 (speed only; any mapping is correct).
+    const int ncol = N + 1;
+    int b, j;
+    {
+        const int bid = blockIdx.x;
+        const int Bfull = (a.B / 8) * 8;
+        if (bid < Bfull * ncol) {
+            const int xcd = bid % 8, slot = bid / 8;
+            b = (slot / ncol) * 8 + xcd; j = slot % ncol;
+        } else {
+            const int r = bid - Bfull * ncol;
+            b = Bfull + r / ncol; j = r % ncol;
+        }
+    }
+    if (b >= a.B) return;
+    if (a.run && !a.run[b]) return;
+    extern __shared__ double sm[];
+    sweep_col_dev<NX, NU>(a, b, j, lane, sm);
 }
 
 // ------------------------------------------------------------------------------------------------

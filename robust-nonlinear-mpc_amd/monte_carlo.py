@@ -4,6 +4,8 @@ Seed s reproduces the disturbance stream of the reference script for `np.random.
 (expe/main_rocket_robust_closed_loop.py:30,180: w_t = 2*rand(nx) - 1 per closed-loop step; seed 0 is the script's own run).
 Rank r owns the contiguous seed slice shard_range(S, r, world); the only collective is one all-gather of the trajectories.
 """
+import os
+
 import numpy as np
 
 from .closed_loop import ClosedLoopMPC
@@ -15,12 +17,42 @@ def disturbance_stream(seed, steps, nx):
     return np.stack([2.0 * rs.rand(nx) - 1.0 for _ in range(steps)])
 
 
-def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None):
+def can_run_persistent(rti, rti_steps, opts=None, environ=os.environ):
+    """Whether ClosedLoopMPC.run_decoupled takes this setting (slsqp_cl_run / slsqp_cl_run_scp): any number of SCP iterations `rti` (<= 0: SCP
+    converge mode), a fixed number of fast-SLS steps `rti_steps` >= 1 (None / <= 0 is fast-SLS converge mode: not inside the loop), fp64, and the
+    fused chain with the shared first sweep allowed (opts.fuse_rti, SLSQP_FUSE_RTI, SLSQP_SWEEP_SHARED).  `opts`: a _lib.Opts (or anything with
+    precision / fuse_rti attributes), None = the library's defaults.  Plain Python: needs no handle and no GPU."""
+    if rti_steps is None or int(rti_steps) < 1:
+        return False
+    if opts is not None and (int(getattr(opts, "precision", 0)) != 0 or int(getattr(opts, "fuse_rti", 1)) == 0):
+        return False
+    if opts is None and int(environ.get("SLSQP_PRECISION", "0") or 0) != 0:      # (BatchedFastSLS takes its precision from there)
+        return False
+
+    def env_on(name):
+        v = environ.get(name)
+        if v is None:
+            return True
+        try:
+            return int(v) != 0
+        except ValueError:
+            return False      # (the library reads it with atoi: 0)
+    return env_on("SLSQP_FUSE_RTI") and env_on("SLSQP_SWEEP_SHARED")
+
+
+# rti = 1 with one fast-SLS step (the rocket script) takes the persistent launch by default, as before.  Plants whose script setting goes through
+# slsqp_cl_run_scp take it by default only where it was measured faster (profiles/r04/README.md); for the others it is an option (persistent=True)
+PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
+
+
+def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
     cl = ClosedLoopMPC(model, N, B, device=device)
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
-    if budget_ms != 0 and cl.rti == 1 and model.fast_sls_rti_steps == 1:      # instances advance independently (slsqp_cl_run): same bits
+    rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
+    want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
+    if budget_ms != 0 and want and can_run_persistent(cl.rti, rti_steps, cl.f.opts):      # instances advance independently (slsqp_cl_run / slsqp_cl_run_scp): same bits
         out = cl.run_decoupled(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation, budget_ms=8.0 if budget_ms is None else budget_ms)
     else:
         out = cl.run_on_device(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation)
@@ -31,10 +63,12 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 
 
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
-                    budget_ms=None):
+                    budget_ms=None, persistent=None):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
+    persistent: None = the plant's default (PERSISTENT_DEFAULT), True = the persistent launch for every setting can_run_persistent accepts (the
+    pendulum and quadrotor scripts' rti = 3 with 2 fast-SLS steps through slsqp_cl_run_scp), False = never.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -49,7 +83,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
 
     def work(k):
         try:
-            parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms)
+            kw = {} if persistent is None else dict(persistent=persistent)
+            parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:
             err.append(e)
 
