@@ -30,13 +30,15 @@ def main():
     ap.add_argument("--continuation", type=int, default=2, help="stages of the initial-state continuation of the nominal NLP (far-away x0)")
     ap.add_argument("--slices", type=int, default=3, help="independent slices (own stream + host thread) the seeds are cut into")
     ap.add_argument("--round-budget-ms", type=float, default=None, help="run the loop through slsqp_cl_run: instances advance independently, rounds of this length")
+    ap.add_argument("--x0-box-tol", type=float, default=0.0, help="how far the measured state may lie outside its own stage-0 box before a step is refused "
+                    "(0: strict; 1e-3: what the reference's OSQP settings let through; inf: never)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model("rocket")
     x0 = m.x_ref + a.x0_scale * (m.extra["x0"] - m.x_ref)
     t0 = time.perf_counter()
     r = run_monte_carlo(m, a.N, np.arange(a.seeds), a.steps, x0, solve_nominal=(a.init == "sqp"), slices=a.slices, continuation=a.continuation,
-                        budget_ms=a.round_budget_ms)
+                        budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol)
     dt = time.perf_counter() - t0
     ok = r["success"]
     if "nlp_status" in r:
@@ -44,7 +46,7 @@ def main():
               f"accepted steps mean {r['nlp_iterations'].mean():.1f}")
     print(f"{a.seeds} seeds x {a.steps} MPC steps (N={a.N}) in {dt:.2f} s; solved steps: {ok.mean():.3f}; "
           f"final |pos| mean {np.linalg.norm(r['state_trajectory'][:, :3, -1], axis=1).mean():.3f} "
-          f"(start {np.linalg.norm(x0[:3]):.3f}); QP {r['t_qp'].sum():.1f} ms, Riccati sweeps {r['t_riccati'].sum():.1f} ms")
+          f"(start {np.linalg.norm(x0[:3]):.3f}); largest stage-0 violation of the measured state {r['x0_violation'].max():.2e}; QP {r['t_qp'].sum():.1f} ms, Riccati sweeps {r['t_riccati'].sum():.1f} ms")
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         from robust_nonlinear_mpc_amd import ClosedLoopMPC

@@ -102,6 +102,7 @@ typedef struct {
                             for another instance; budget_ms / cut_frac are ignored and *rounds_out = 1.  0: the round-based loop described at
                             slsqp_cl_run.  Same results bit for bit either way. */
 } slsqp_opts;
+#define SLSQP_X0_BOX_TOL_OSQP_DEFAULT 1e-3
 
 void slsqp_default_opts(slsqp_opts *o);
 const char *slsqp_last_error(void);
@@ -134,6 +135,8 @@ int slsqp_solve(slsqp_handle *h, const double *x0, int loc, const slsqp_opts *op
    primal_vec (n) dual_vec (m-nx) cost_nominal (1) cost_tube (1; SLS.eval_cost of the last sweep, util/SLS.py:38-46) status[int32] (1) qp_iters[int32] (1) iteration_number[int32] (1)
    beta (N,N,ni) beta_f (N+1,ni_f) backoff (N,ni) backoff_f (ni_f) backoff_x (N+1,nx) backoff_u (N,nu)
    eta (N,N,ni) eta_f (N+1,ni_f) K (N,N+1,nu,nx) ubg (m-nx) lbg (m-nx) kkt (8) pin_dual (nx) success[int32] (1)
+   x0_viol (2): largest amount by which the pinned x_0 lay outside its stage-0 box in the instance's last first / last QP (<= 0: inside; +inf: NaN
+   state), written for accepted and refused solves alike (slsqp_set_x0_box_tol); a QP the instance took no part in (qp_stats status -1) leaves its entry as it was
    and the current problem data: A (N,nx,nx) Bm (N,nx,nu) c (N,nx) g (N,ni) gN (ni_f) q (n) */
 int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc);
 /* bytes slsqp_get copies per instance for `name` (the caller's buffer must hold batch x that), or -1 for an unknown name */
@@ -142,6 +145,20 @@ long long slsqp_result_bytes(slsqp_handle *h, const char *name);
    x_meas.  Same shapes as slsqp_get. */
 int slsqp_set(slsqp_handle *h, const char *name, const void *src, int loc);
 int slsqp_reset(slsqp_handle *h);
+/* Tolerance of the measured state against its own stage-0 box, kept by the handle for every following call (slsqp_opts keeps its layout: the value
+   is a property of the handle, like the costs).  0 (default): strict -- a QP whose pinned x_0 lies more than 1e-9 outside its own stage-0 box (the rows
+   of G [x_0;u_0] <= g that touch the state; the tightened QP moves them inwards by the back-off) ends with SLSQP_ST_INFEASIBLE and no work.  > 0: the
+   gate is max(1e-9, tol); INFINITY: the stage-0 state rows never gate (a measured state is data, not a decision variable).  A NaN or infinite state
+   is refused whatever the value; a negative or NaN tol is an error.  An accepted solve returns the exact optimum of the QP WITHOUT its stage-0 state
+   rows (their multipliers are 0; the stage-0 input rows stay constraints), certified like every other solve; if the rest of the QP is infeasible the
+   Farkas test answers (SLSQP_ST_INFEASIBLE_CERT).  Stands for what the reference gets from OSQP at eps_abs = eps_rel = 1e-3 with "solved inaccurate"
+   accepted (solver/qp_jit.py:370-400 solve and status check, :537-548 settings): violations below its primal tolerance pass unseen there.
+   SLSQP_X0_BOX_TOL_OSQP_DEFAULT lies where that solver accepted every QP measured; its iterate then moves x_0 itself by about
+   half the violation, which this library does not imitate.  Applies to every QP of slsqp_solve, slsqp_qp_solve, slsqp_cl_step, slsqp_cl_run and
+   slsqp_cl_run_scp; the QPs of slsqp_nominal_solve stay strict (their x_0 deviation is 0 by construction).  The largest violation of each solve can
+   be read afterwards: slsqp_get "x0_viol", "log_x0_viol". */
+int slsqp_set_x0_box_tol(slsqp_handle *h, double tol);
+double slsqp_get_x0_box_tol(slsqp_handle *h);
 int slsqp_sync(slsqp_handle *h);
 
 /* ---- the step in front of the path: batched linearisation (SCP_SLS.update_jacobian, solver/SCP_SLS_jit.py:251-366) ---------
@@ -170,7 +187,8 @@ int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc, const slsq
    previous round's deadline suspended; a chain still running budget_ms after its launch started (budget_ms <= 0: no time limit), or still running when
    cut_frac of the round's participants have finished (0 < cut_frac < 1; else off), suspends itself and continues in the next round.
    No instance waits for the slowest one of its step.  Call after slsqp_cl_init (+ slsqp_nominal_solve); per-step results through the device-side
-   log (slsqp_cl_log with max_steps >= steps, before slsqp_cl_init) and `log_qp_stats`[int32] (steps,2,8).  *rounds_out (may be NULL): rounds taken.
+   log (slsqp_cl_log with max_steps >= steps, before slsqp_cl_init), `log_qp_stats`[int32] (steps,2,8) and `log_x0_viol` (steps,2), the per-step
+   copies of qp_stats and x0_viol (0 where the QP took no part).  *rounds_out (may be NULL): rounds taken.
    With opts.cl_persistent (the default) there are no rounds at all: see slsqp_opts. */
 int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc, const slsqp_opts *opts, double budget_ms, double cut_frac, int *rounds_out);
 /* `steps` MPC steps of every instance as ONE persistent launch, for any SCP setting of slsqp_cl_step (SCP_SLS.solve, SCP_SLS_jit.py:103-135):
@@ -189,7 +207,8 @@ int slsqp_cl_run_stats(slsqp_handle *h, double *out, int len);
 /* Device-side log of the closed loop: every following slsqp_cl_step stores what the scripts keep per MPC step
    (expe/main_rocket_robust_closed_loop.py:160-178) in entry `step` of (B, max_steps, ...) device buffers, so a Monte-Carlo run makes no
    host round trip per step.  slsqp_get names (per instance): log_state (S,nx) log_u0 (S,nu) log_nominal_x (S,N+1,nx) log_nominal_u (S,N,nu)
-   log_backoff_x (S,N+1,nx) log_backoff_u (S,N,nu) log_success[int32] (S) log_scp_iterations[int32] (S) log_primal_infeasibility (S).
+   log_backoff_x (S,N+1,nx) log_backoff_u (S,N,nu) log_success[int32] (S) log_scp_iterations[int32] (S) log_primal_infeasibility (S)
+   log_x0_viol (S,2) (x0_viol after the step, 0 where the QP took no part; after a slsqp_cl_run / slsqp_cl_run_scp the name holds that run's (steps,2) instead).
    slsqp_cl_init restarts at entry 0. */
 int slsqp_cl_log(slsqp_handle *h, int max_steps);
 

@@ -7,6 +7,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("SLSQP_SO") or os.path.join(_HERE, "csrc", "libslsqp_hip.so")   # SLSQP_SO: experiment builds only
 HOST, DEVICE = 0, 1
 TIMING_LEN, KERNEL_TIMING_LEN, CL_RUN_STATS_LEN = 5, 8, 4      # SLSQP_TIMING_LEN / SLSQP_KERNEL_TIMING_LEN / SLSQP_CL_RUN_STATS_LEN of include/slsqp.h
+# SLSQP_X0_BOX_TOL_OSQP_DEFAULT of include/slsqp.h: the value of slsqp_set_x0_box_tol (HandleOpts.x0_box_tol) that stands for the reference's live OSQP settings (eps_abs = eps_rel
+# = 1e-3, "solved inaccurate" accepted): the largest stage-0 violation at which that solver still accepted every QP it was given
+# (tests/test_x0_policy_cpu.py measures it, DESIGN.md section 2.1 holds the table)
+X0_BOX_TOL_OSQP_DEFAULT = 1e-3
 
 
 class Dims(C.Structure):
@@ -19,11 +23,28 @@ class Opts(C.Structure):
                 ("max_scp_iter", C.c_int), ("scp_eps", C.c_double), ("precision", C.c_int), ("as_first", C.c_int), ("as_rounds", C.c_int), ("as_max_viol", C.c_int), ("ipm_restart", C.c_int), ("time_kernels", C.c_int), ("as_warm_max_set", C.c_int), ("as_warm_last", C.c_int), ("fuse_rti", C.c_int), ("cl_persistent", C.c_int)]
 
 
+class HandleOpts(Opts):
+    """The slsqp_opts of one handle as BatchedFastSLS keeps them (same layout as Opts: pass with ctypes.byref), plus `x0_box_tol`: that option is a
+    property of the handle in the C ABI (slsqp_set_x0_box_tol; the struct keeps its layout), so assigning it here calls the library at once."""
+
+    def bind(self, lib, handle):
+        self._lib, self._h = lib, handle
+        return self
+
+    @property
+    def x0_box_tol(self):
+        return float(self._lib.slsqp_get_x0_box_tol(self._h))
+
+    @x0_box_tol.setter
+    def x0_box_tol(self, tol):
+        check(self._lib.slsqp_set_x0_box_tol(self._h, float(tol)))
+
+
 EXPORTS = [
     "slsqp_default_opts", "slsqp_last_error", "slsqp_version", "slsqp_create", "slsqp_destroy", "slsqp_set_costs",
     "slsqp_set_constraints", "slsqp_update_dynamics", "slsqp_update_linear_cost", "slsqp_solve", "slsqp_get", "slsqp_reset",
     "slsqp_sync", "slsqp_qp_nnz", "slsqp_qp_update_data_mat", "slsqp_qp_update_data_vec", "slsqp_qp_solve", "slsqp_sweep",
-    "slsqp_last_timing", "slsqp_kernel_timing", "slsqp_stream", "slsqp_set_model", "slsqp_set_E", "slsqp_linearize", "slsqp_cl_init", "slsqp_cl_step", "slsqp_nominal_solve", "slsqp_set", "slsqp_cl_log", "slsqp_selftest", "slsqp_result_bytes", "slsqp_cl_run", "slsqp_cl_run_stats", "slsqp_cl_run_scp",
+    "slsqp_last_timing", "slsqp_kernel_timing", "slsqp_stream", "slsqp_set_model", "slsqp_set_E", "slsqp_linearize", "slsqp_cl_init", "slsqp_cl_step", "slsqp_nominal_solve", "slsqp_set", "slsqp_cl_log", "slsqp_selftest", "slsqp_result_bytes", "slsqp_cl_run", "slsqp_cl_run_stats", "slsqp_cl_run_scp", "slsqp_set_x0_box_tol", "slsqp_get_x0_box_tol",
 ]
 
 _lib = None
@@ -80,6 +101,9 @@ def load():
     lib.slsqp_cl_run.argtypes = [vp, C.c_int, dp, C.c_int, C.POINTER(Opts), C.c_double, C.c_double, C.POINTER(C.c_int)]
     lib.slsqp_cl_run_scp.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int, C.POINTER(Opts)]
     lib.slsqp_cl_run_stats.argtypes = [vp, dp, C.c_int]
+    lib.slsqp_set_x0_box_tol.argtypes = [vp, C.c_double]
+    lib.slsqp_get_x0_box_tol.argtypes = [vp]
+    lib.slsqp_get_x0_box_tol.restype = C.c_double
     lib.slsqp_selftest.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, C.c_int]
     lib.slsqp_stream.argtypes = [vp]
     lib.slsqp_stream.restype = vp

@@ -22,7 +22,10 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0):
+        """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
+        refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
+        state never fails a step on its own (slsqp_set_x0_box_tol)."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -32,6 +35,7 @@ class ClosedLoopMPC:
         if fast_sls_rti_steps is None and rti is None:
             fast_sls_rti_steps = m.fast_sls_rti_steps
         self.f.set_rti_steps(fast_sls_rti_steps)
+        self.f.opts.x0_box_tol = float(x0_box_tol)
         self.steps_done = 0
 
     def close(self):
@@ -79,6 +83,7 @@ class ClosedLoopMPC:
             backoff_x=f.get("backoff_x", (N + 1, m.nx)), backoff_u=f.get("backoff_u", (N, m.nu)),
             success=f.get("scp_success", (), np.int32).astype(bool), status=f.get("status", (), np.int32),
             scp_iterations=f.get("scp_iterations", (), np.int32), primal_infeasibility=f.get("primal_infeasibility", ()),
+            x0_violation=np.where(f.get("qp_stats", (2, 8), np.int32)[:, :, 6] == -1, 0.0, f.get("x0_viol", (2,))),      # (0 where the QP took no part, as in the log)
             t_qp_ms=f.timing_ms()["qp"], t_riccati_ms=f.timing_ms()["sweep"], t_jac_ms=f.timing_ms()["jac"],
         )
 
@@ -109,6 +114,7 @@ class ClosedLoopMPC:
             t_jac=t_jac, t_qp=t_qp, t_riccati=t_ric,
             success=f.get("log_success", (steps,), np.int32).astype(bool), scp_iterations=f.get("log_scp_iterations", (steps,), np.int32),
             primal_infeasibility=f.get("log_primal_infeasibility", (steps,)),
+            x0_violation=f.get("log_x0_viol", (steps, 2)),
         )
 
     def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0):
@@ -120,7 +126,7 @@ class ClosedLoopMPC:
         Every other setting slsqp_cl_step takes with a fixed number of fast-SLS steps (rti > 1, SCP converge mode rti <= 0, rti_steps > 1: the
         pendulum and quadrotor scripts, SCP_SLS's default): slsqp_cl_run_scp, always one persistent launch (budget_ms / cut_frac ignored).  Fast-SLS
         converge mode (fast_sls_rti_steps None), precision = 1 and SLSQP_FUSE_RTI=0 are refused with the library's message.
-        Adds `qp_stats` (B, steps, 2, 8), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the run's totals in their first entry."""
+        Adds `qp_stats` (B, steps, 2, 8) (next to `x0_violation` (B, steps, 2), which every logged run has), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the run's totals in their first entry."""
         f, m, N, B = self.f, self.m, self.N, self.B
         L.check(f.lib.slsqp_cl_log(f.h, int(steps)))
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
@@ -157,7 +163,7 @@ class ClosedLoopMPC:
             backoff_trajectory_x=np.zeros((B, m.nx, N + 1, steps)), backoff_trajectory_u=np.zeros((B, m.nu, N, steps)),
             t_jac=np.zeros((steps, 1)), t_qp=np.zeros((steps, 1)), t_riccati=np.zeros((steps, 1)),
             success=np.zeros((B, steps), dtype=bool), scp_iterations=np.zeros((B, steps), dtype=np.int32),
-            primal_infeasibility=np.full((B, steps), np.nan),
+            primal_infeasibility=np.full((B, steps), np.nan), x0_violation=np.zeros((B, steps, 2)),
         )
         for i in range(steps):
             r = self.step(None if W is None else W[i])
@@ -172,10 +178,12 @@ class ClosedLoopMPC:
             out["primal_infeasibility"][:, i] = r["primal_infeasibility"]
             out["success"][:, i] = r["success"]
             out["scp_iterations"][:, i] = r["scp_iterations"]
+            out["x0_violation"][:, i] = r["x0_violation"]
         return out
 
     def save_npz(self, path, out, b=0):
-        """Write instance b with exactly the key set the reference's plot()/loaders read (main_rocket...:189-206, 218-241)."""
+        """Write instance b with exactly the key set the reference's plot()/loaders read (main_rocket...:189-206, 218-241); what the result
+        dictionary holds beyond that (success, qp_stats, x0_violation, ...) is not written."""
         m = self.m
         steps = out["state_trajectory"].shape[2]
         np.savez(path, state_trajectory=out["state_trajectory"][b], input_trajectory=out["input_trajectory"][b],

@@ -67,6 +67,11 @@ struct slsqp_handle {
     double *lin_stage, *lin_tape;   // (B,N,3,nx) intermediate RK4 stage points of the linearisation (k_lin_val -> k_lin_tan); (B,N,4,NT_MAX) its transcendental values
     double call_id;             // counts fast-SLS calls (validity of the interior-point iterate copies, QpArgs::call_id)
     int *qpstat;                // (B,2,8) per-QP statistics, see QpArgs::qpstat
+    double *x0viol;             // (B,2) largest stage-0 violation of the instance's last first / last QP: part of the kkt allocation (x0_record, slsqp_kernels.hpp)
+    double x0_box_tol = 0.0;    // slsqp_set_x0_box_tol: the tolerance the following launches ask for
+    double x0_tol_dev = 0.0;    // the tolerance of the x0 gate the device currently holds (kkt[8 B]; written when a launch asks for another one)
+    double *x0vlog = nullptr;   // (B, qplog_steps, 2) per-step copy of x0viol of a slsqp_cl_run / slsqp_cl_run_scp (allocated with qplog)
+    double *lg_x0v = nullptr;   // (B, log_steps, 2) the same for slsqp_cl_step loops (part of the slsqp_cl_log buffers)
     int *stale;                 // (B) bit 0: eta / eta_f, bit 1: K hold values from before the last slsqp_reset (zeroed lazily on slsqp_get)
     double *pinf; double t_jac;  // primal_infeasibility of the last SCP update (SCP_SLS_jit.py:449-456); linearisation time of the last cl_step
     // qp-level CSC maps
@@ -159,7 +164,7 @@ extern "C" slsqp_handle *slsqp_create(const slsqp_dims *d, int batch, int device
     rc |= dalloc(h->owned, &h->u0, B * nu); rc |= dalloc(h->owned, &h->wbuf, B * nx); rc |= dalloc(h->owned, &h->u_init, (size_t)nu); h->cl_steps = 0; rc |= dalloc(h->owned, &h->cst, (size_t)(3 * nx + 2 * nu) * 2);
     rc |= dalloc(h->owned, &h->ubg, B * h->mb); rc |= dalloc(h->owned, &h->lbg, B * h->mb);
     rc |= dalloc(h->owned, &h->primal, B * h->n); rc |= dalloc(h->owned, &h->dual, B * h->mb); rc |= dalloc(h->owned, &h->cost, B); rc |= dalloc(h->owned, &h->pin_dual, B * nx);
-    rc |= dalloc(h->owned, &h->kkt, B * 8); rc |= dalloc(h->owned, &h->prev_primal, B * h->n); rc |= dalloc(h->owned, &h->Linv, B * N * nx * nx); rc |= dalloc(h->owned, &h->ws, B * qp_ws_doubles(h->n, N, nx)); rc |= dalloc(h->owned, &h->qpstate, B * 40);
+    rc |= dalloc(h->owned, &h->kkt, kkt_doubles(B)); rc |= dalloc(h->owned, &h->prev_primal, B * h->n); rc |= dalloc(h->owned, &h->Linv, B * N * nx * nx); rc |= dalloc(h->owned, &h->ws, B * qp_ws_doubles(h->n, N, nx)); rc |= dalloc(h->owned, &h->qpstate, B * 40);
     rc |= dalloc(h->owned, &h->eta, B * N * N * ni); rc |= dalloc(h->owned, &h->eta_f, B * (N + 1) * nif); rc |= dalloc(h->owned, &h->beta, B * N * N * ni);
     rc |= dalloc(h->owned, &h->beta_f, B * (N + 1) * nif); rc |= dalloc(h->owned, &h->backoff, B * N * ni); rc |= dalloc(h->owned, &h->backoff_f, B * nif);
     rc |= dalloc(h->owned, &h->backoff_x, B * (N + 1) * nx); rc |= dalloc(h->owned, &h->backoff_u, B * N * nu); rc |= dalloc(h->owned, &h->K, B * N * (N + 1) * nu * nx);
@@ -222,7 +227,7 @@ extern "C" slsqp_handle *slsqp_create(const slsqp_dims *d, int batch, int device
     reg("nominal_x", h->Xn, sizeof(double) * (N + 1) * nx); reg("nominal_u", h->Un, sizeof(double) * N * nu); reg("x_meas", h->xmeas, sizeof(double) * nx); reg("u0", h->u0, sizeof(double) * nu);
     reg("A", h->A, sizeof(double) * N * nx * nx); reg("Bm", h->Bm, sizeof(double) * N * nx * nu); reg("c", h->c, sizeof(double) * N * nx);
     reg("g", h->g, sizeof(double) * N * ni); reg("gN", h->gN, sizeof(double) * nif); reg("q", h->q, sizeof(double) * h->n); reg("pin_dual", h->pin_dual, sizeof(double) * nx);
-    reg("chain_times", h->chain_times, sizeof(unsigned long long) * 4); reg("primal_infeasibility", h->pinf, sizeof(double)); reg("qp_stats", h->qpstat, sizeof(int) * 16); reg("x0_arg", h->x0arg, sizeof(double) * nx);
+    reg("chain_times", h->chain_times, sizeof(unsigned long long) * 4); reg("primal_infeasibility", h->pinf, sizeof(double)); reg("qp_stats", h->qpstat, sizeof(int) * 16); h->x0viol = x0_record(h->kkt, h->B) + 2; reg("x0_viol", h->x0viol, sizeof(double) * 2); reg("x0_arg", h->x0arg, sizeof(double) * nx);
 #ifdef QP_DIAG_SPAN
     if (dalloc(h->owned, &h->qp_diag, B * 64)) return nullptr;
     reg("qp_diag", h->qp_diag, sizeof(int) * 64);
@@ -239,6 +244,7 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     if (h->stage) hipFree(h->stage);
     if (h->cl_W) hipFree(h->cl_W);
     if (h->qplog) hipFree(h->qplog);
+    if (h->x0vlog) hipFree(h->x0vlog);
     if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
     if (h->chain_times_host) hipHostFree(h->chain_times_host);
     for (auto &e : h->ev) hipEventDestroy(e);
@@ -571,6 +577,7 @@ struct ChainArgs {
     unsigned long long budget;      // wall-clock ticks (100 MHz) after the start at which unfinished solves suspend themselves
     unsigned *fin_count; unsigned cut_count;      // chains of this launch that have ended (device counter, zeroed by the host); solves suspend once it reaches cut_count
     int *qplog; const int *stepno; int log_steps;      // (B, log_steps, 16) per-step copy of the instance's qp_stats, entry stepno[b]
+    double *x0vlog;                 // (B, log_steps, 2) per-step copy of the instance's x0_viol, kept wherever qplog is
 };
 template <int NX, int NU>
 __device__ __forceinline__ int rti_chain_dev(const ChainArgs &c, int b, int lane, double *sm) {
@@ -619,6 +626,8 @@ __device__ __forceinline__ int rti_chain_dev(const ChainArgs &c, int b, int lane
         if (c.lag) { c.lag[b] = 0; c.done[b] = 1; atomicAdd(c.fin_count, 1u); }
     }
     if (c.qplog && lane < 16) c.qplog[((size_t)b * c.log_steps + min(c.stepno[b], c.log_steps - 1)) * 16 + lane] = c.q1.qpstat[(size_t)b * 16 + lane];
+    if (c.qplog && lane >= 16 && lane < 18)      // per-step copy of x0_viol; a QP that took no part (qp_stats status -1) records 0
+        c.x0vlog[((size_t)b * c.log_steps + min(c.stepno[b], c.log_steps - 1)) * 2 + lane - 16] = c.q1.qpstat[(size_t)b * 16 + (lane - 16) * 8 + 6] == -1 ? 0.0 : x0_record(c.q1.kkt, c.q1.B)[2 + (size_t)b * 2 + lane - 16];
     return 1;
 }
 template <int NX, int NU>
@@ -893,6 +902,7 @@ __device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S, int b, int lane, int
     }
     if (L.c.qplog && s < L.c.log_steps) {
         if (lane < 16) L.c.qplog[((size_t)b * L.c.log_steps + s) * 16 + lane] = L.c.q1.qpstat[(size_t)b * 16 + lane];
+        else if (lane < 18) L.c.x0vlog[((size_t)b * L.c.log_steps + s) * 2 + lane - 16] = L.c.q1.qpstat[(size_t)b * 16 + (lane - 16) * 8 + 6] == -1 ? 0.0 : x0_record(L.c.q1.kkt, L.c.q1.B)[2 + (size_t)b * 2 + lane - 16];
         if (lane == 0) S.nsolves[(size_t)b * L.c.log_steps + s] = nsolves;
     }
     if (lane == 0) {
@@ -999,7 +1009,7 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(S
 }
 // converge mode: the batch-wide launches of step s run max over the instances of their solves; an instance that left earlier has its qp_stats
 // slots rewritten as "took no part" (status -1) by the QP launches that follow.  One block per step.
-__global__ void k_cl_qplog_masked(int B, int steps, int log_steps, const int *nsolves, int *qplog) {
+__global__ void k_cl_qplog_masked(int B, int steps, int log_steps, const int *nsolves, int *qplog, double *x0vlog) {
     const int s = blockIdx.x;
     __shared__ int smax;
     if (threadIdx.x == 0) smax = 0;
@@ -1013,6 +1023,7 @@ __global__ void k_cl_qplog_masked(int B, int steps, int log_steps, const int *ns
         if (nsolves[(size_t)b * log_steps + s] < mx) {
             int *qs = qplog + ((size_t)b * log_steps + s) * 16;
             for (int i = 0; i < 16; i++) qs[i] = (i % 8 == 6) ? -1 : 0;
+            x0vlog[((size_t)b * log_steps + s) * 2] = 0.0; x0vlog[((size_t)b * log_steps + s) * 2 + 1] = 0.0;      // (a QP that took no part records 0)
         }
 }
 
@@ -1152,10 +1163,20 @@ __global__ void k_mark_retry(int B, const int *run, const int *status, int *retr
     if (r) atomicAdd(count, 1);
 }
 
+// the tolerance of the x0 gate (slsqp_set_x0_box_tol) goes to the device word the QP kernels read it from (x0_record), on the handle's stream, when
+// it differs from what is there: the default (0, what the allocation holds) never launches anything
+static void set_x0_tol(slsqp_handle *h, double tol) {
+    if (!(tol > 0.0)) tol = 0.0;      // (negative or NaN: strict)
+    if (tol == h->x0_tol_dev) return;
+    hipLaunchKernelGGL(k_fill_doubles, dim3(1), dim3(64), 0, h->st, x0_record(h->kkt, h->B), tol, (size_t)1);
+    h->x0_tol_dev = tol;
+}
+
 static QpArgs make_qp_args(slsqp_handle *h, const int *run, const slsqp_opts *o, int warm, const double *prox = nullptr, int stat_slot = 0, int snap_take = 0, int snap_use = 0,
                            int warm_shift = 0) {
     QpArgs a;
     a.qpstat = h->qpstat; a.stat_slot = stat_slot; a.diag = h->qp_diag;
+    set_x0_tol(h, prox ? 0.0 : h->x0_box_tol);      // (prox: the nominal initialiser's QPs stay strict)
     static const double snap_mu = getenv("SLSQP_SNAP_MU") ? atof(getenv("SLSQP_SNAP_MU")) : 1e-3;
     a.snap_take = snap_take; a.snap_use = snap_use && o->ipm_restart; a.snap_mu = snap_mu; a.call_id = h->call_id; a.call_ids = h->cl_round ? h->call_ids : nullptr; a.as_first = o->as_first; a.as_rounds = o->as_rounds; a.as_max_viol = o->as_max_viol; a.as_warm_max_set = o->as_warm_max_set; a.as_warm_last = o->as_warm_last;
     { static const double pe = getenv("SLSQP_PINF_EPS") ? atof(getenv("SLSQP_PINF_EPS")) : 1e-4; a.pinf_eps = pe; }
@@ -1270,7 +1291,7 @@ static ChainArgs make_chain_args(slsqp_handle *h, const slsqp_opts &o, const int
     c.ta = TightenArgs{B, d.N, d.nx, d.nu, d.ni, d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, h->mask, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, 1, h->ct_part, h->cost_tube};
     c.active = active; c.success = h->success; c.infeas = h->infeas; c.times = h->chain_times;
     c.max_ticks = qp_max_ticks(c.q1, o.qp_max_iter);
-    c.lag = nullptr; c.runm = nullptr; c.done = nullptr; c.t0word = nullptr; c.budget = 0; c.qplog = nullptr; c.stepno = nullptr; c.log_steps = 0; c.fin_count = nullptr; c.cut_count = 0xFFFFFFFFu;
+    c.lag = nullptr; c.runm = nullptr; c.done = nullptr; c.t0word = nullptr; c.budget = 0; c.qplog = nullptr; c.x0vlog = nullptr; c.stepno = nullptr; c.log_steps = 0; c.fin_count = nullptr; c.cut_count = 0xFFFFFFFFu;
     return c;
 }
 
@@ -1378,7 +1399,7 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
         ChainArgs c = make_chain_args(h, o, active, wshift);
         if (h->cl_round) {      // a round of slsqp_cl_run: suspended solves resume, unfinished ones suspend at the deadline
             c.lag = h->cl_lag; c.runm = h->cl_runm; c.done = h->cl_done; c.t0word = h->t0word; c.budget = h->cl_budget;
-            c.qplog = h->qplog; c.stepno = h->cl_stepno; c.log_steps = h->qplog_steps;
+            c.qplog = h->qplog; c.x0vlog = h->x0vlog; c.stepno = h->cl_stepno; c.log_steps = h->qplog_steps;
             c.fin_count = (unsigned *)(h->t0word + 1); c.cut_count = h->cl_cut_count;
             HIPCHK(hipMemsetAsync(h->t0word, 0, 2 * sizeof(unsigned long long), h->st));
         } else flag_nonfinite(h, active, h->alive, h->infeas);      // (slsqp_cl_run's rounds and k_cl_loop linearise their own data; the NaN-keeping certificate guards them)
@@ -1457,6 +1478,13 @@ extern "C" long long slsqp_result_bytes(slsqp_handle *h, const char *name) {
     auto it = h->named.find(name);
     return it == h->named.end() ? -1LL : (long long)it->second.second;
 }
+
+extern "C" int slsqp_set_x0_box_tol(slsqp_handle *h, double tol) {
+    if (!(tol >= 0.0)) return fail("slsqp_set_x0_box_tol: the tolerance must be >= 0 (0 = strict, INFINITY = the stage-0 state rows never gate)");
+    h->x0_box_tol = tol;
+    return 0;
+}
+extern "C" double slsqp_get_x0_box_tol(slsqp_handle *h) { return h->x0_box_tol; }
 
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
@@ -1659,8 +1687,9 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     HIPCHK(hipStreamSynchronize(h->st));
     h->log_steps = 0;
     free_all(h->log_owned);
-    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility"};
+    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol"};
     for (const char *nm : names) h->named.erase(nm);
+    h->lg_x0v = nullptr;
     h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr;
     const slsqp_dims &d = h->d;
     const size_t B = h->B, S = max_steps, nX = (size_t)(d.N + 1) * d.nx, nU = (size_t)d.N * d.nu;
@@ -1668,16 +1697,22 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     auto &ow = h->log_owned;
     rc |= dalloc(ow, &h->lg_x, B * S * nX); rc |= dalloc(ow, &h->lg_u, B * S * nU); rc |= dalloc(ow, &h->lg_bx, B * S * nX); rc |= dalloc(ow, &h->lg_bu, B * S * nU);
     rc |= dalloc(ow, &h->lg_state, B * S * d.nx); rc |= dalloc(ow, &h->lg_u0, B * S * d.nu); rc |= dalloc(ow, &h->lg_succ, B * S); rc |= dalloc(ow, &h->lg_it, B * S);
-    rc |= dalloc(ow, &h->lg_pinf, B * S);
-    if (rc) { free_all(ow); h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
+    rc |= dalloc(ow, &h->lg_pinf, B * S); rc |= dalloc(ow, &h->lg_x0v, B * S * 2);
+    if (rc) { free_all(ow); h->lg_x0v = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
     h->log_steps = max_steps;
     auto reg = [&](const char *nm, void *p, size_t bytes) { h->named[nm] = {p, bytes}; };
     reg("log_nominal_x", h->lg_x, sizeof(double) * S * nX); reg("log_nominal_u", h->lg_u, sizeof(double) * S * nU);
     reg("log_backoff_x", h->lg_bx, sizeof(double) * S * nX); reg("log_backoff_u", h->lg_bu, sizeof(double) * S * nU);
     reg("log_state", h->lg_state, sizeof(double) * S * d.nx); reg("log_u0", h->lg_u0, sizeof(double) * S * d.nu);
     reg("log_success", h->lg_succ, sizeof(int) * S); reg("log_scp_iterations", h->lg_it, sizeof(int) * S);
-    reg("log_primal_infeasibility", h->lg_pinf, sizeof(double) * S);
+    reg("log_primal_infeasibility", h->lg_pinf, sizeof(double) * S); reg("log_x0_viol", h->lg_x0v, sizeof(double) * S * 2);
     return 0;
+}
+
+// entry `step` of the per-step copy of x0_viol (slsqp_cl_step with slsqp_cl_log; the closed-loop kernels write theirs themselves)
+__global__ void k_cl_log_x0v(int B, int log_steps, int step, const double *x0viol, const int *qpstat, double *lg) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * B) lg[((size_t)(i / 2) * log_steps + step) * 2 + (i & 1)] = qpstat[(size_t)i * 8 + 6] == -1 ? 0.0 : x0viol[i];      // (a QP that took no part records 0)
 }
 
 // One MPC step for the whole batch: [warm-start shift + solver reset] -> rti x (linearise, fast-SLS solve of x_nom0 - x_meas,
@@ -1739,6 +1774,8 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
         ClLogArgs la{nullptr, nullptr, h->B, d.N, d.nx, d.nu, h->log_steps, h->cl_steps, h->Xn, h->Un, h->backoff_x, h->backoff_u, h->scp_success, h->scp_iters,
                      h->pinf, h->lg_x, h->lg_u, h->lg_bx, h->lg_bu, h->lg_state, h->lg_u0, h->lg_pinf, h->lg_succ, h->lg_it};
         hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, la);
+        hipLaunchKernelGGL(k_cl_log_x0v, dim3((2 * h->B + 255) / 256), dim3(256), 0, h->st, h->B, h->log_steps, h->cl_steps, h->x0viol, h->qpstat, h->lg_x0v);
+        h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};      // (a slsqp_cl_run in between points the name at its own per-run buffer)
     }
     if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
     else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant<1>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
@@ -1792,7 +1829,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     L.c = make_chain_args(h, o, active, 1);
     L.c.q1.call_ids = L.c.q2.call_ids = h->call_ids;
     L.c.q1.shift_stepno = L.c.q2.shift_stepno = h->cl_stepno;      // the horizon has moved for the instances past their first step
-    L.c.qplog = h->qplog; L.c.stepno = h->cl_stepno; L.c.log_steps = h->qplog_steps;
+    L.c.qplog = h->qplog; L.c.x0vlog = h->x0vlog; L.c.stepno = h->cl_stepno; L.c.log_steps = h->qplog_steps;
     L.cl = cl_args(h, nullptr);
     L.lin = LinArgs{B, d.N, h->Xn, h->Un, h->g_raw, h->gf_raw, costs_of(h), h->A, h->Bm, h->c, h->g, h->gN, h->q, nullptr, h->lin_stage, h->lin_tape};
     L.ba = BoundsArgs{B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, nullptr};
@@ -1821,7 +1858,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     else if (h->model_id == 1) rc = launch_loop_t<1>(h, L, Sp);
     else rc = launch_loop_t<2>(h, L, Sp);
     if (rc) return -1;
-    if (scp && S.converge) hipLaunchKernelGGL(k_cl_qplog_masked, dim3(steps), dim3(256), 0, h->st, B, steps, h->qplog_steps, h->qplog_nsolves, h->qplog);
+    if (scp && S.converge) hipLaunchKernelGGL(k_cl_qplog_masked, dim3(steps), dim3(256), 0, h->st, B, steps, h->qplog_steps, h->qplog_nsolves, h->qplog, h->x0vlog);
     tl_end(h, tl_c); tl_end(h, tl_tot);
     int ctl[4] = {0, 0, 0, 0};
     std::vector<int> sn((size_t)B);
@@ -1871,16 +1908,20 @@ static int cl_run_prepare(slsqp_handle *h, int steps, const double *W, int loc, 
     }
     if (h->qplog_cap < steps) {
         if (h->qplog) hipFree(h->qplog);
+        if (h->x0vlog) hipFree(h->x0vlog);
         if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
-        h->qplog = nullptr; h->qplog_nsolves = nullptr; h->qplog_cap = 0; h->qplog_steps = 0;
+        h->qplog = nullptr; h->x0vlog = nullptr; h->qplog_nsolves = nullptr; h->qplog_cap = 0; h->qplog_steps = 0;
         HIPCHK(hipMalloc((void **)&h->qplog, (size_t)B * steps * 16 * sizeof(int) + 64));
+        HIPCHK(hipMalloc((void **)&h->x0vlog, (size_t)B * steps * 2 * sizeof(double) + 64));
         HIPCHK(hipMalloc((void **)&h->qplog_nsolves, (size_t)B * steps * sizeof(int) + 64));
         h->qplog_cap = steps;
     }
     h->qplog_steps = steps;
     HIPCHK(hipMemsetAsync(h->qplog, 0, (size_t)B * steps * 16 * sizeof(int), h->st));
     HIPCHK(hipMemsetAsync(h->qplog_nsolves, 0, (size_t)B * steps * sizeof(int), h->st));
+    HIPCHK(hipMemsetAsync(h->x0vlog, 0, (size_t)B * steps * 2 * sizeof(double), h->st));
     h->named["log_qp_stats"] = {h->qplog, sizeof(int) * 16 * (size_t)steps};
+    h->named["log_x0_viol"] = {h->x0vlog, sizeof(double) * 2 * (size_t)steps};
     HIPCHK(hipMemsetAsync(h->cl_stepno, 0, sizeof(int) * B, h->st));
     HIPCHK(hipMemsetAsync(h->cl_lag, 0, sizeof(int) * B, h->st));
     hipLaunchKernelGGL(k_fill_doubles, dim3(64), dim3(256), 0, h->st, h->call_ids, h->call_id, (size_t)B);

@@ -75,6 +75,7 @@ struct QpArgs {
     double *pin_dual;         // (B,NX) multipliers of the x0-pin rows (may be NULL)
     double *kkt;              // (B,8) [0..3] accepted solution: stationarity, box violation, multiplier-sign violation, mu;
                               //       [4],[5] last polish attempt: stationarity, box; [6],[7] factor sweeps / solves used
+                              // followed by the x0 record (x0_record below): the tolerance of the x0 gate and (B,2) violations
     int *status, *iters;      // (B)
     int max_iter;
     double eps;
@@ -109,6 +110,18 @@ struct QpArgs {
     int n_refine;             // refinement solves per polish (1 in fp64, 3 with fp32 factorisations)
     double early_ctol;        // tolerance (relative to max(1,|q|inf)) of the look at the un-refined polish solve: its accuracy class
 };
+
+// The x0 gate's tolerance and record live in device memory BEHIND the kkt block, not in QpArgs: k_rti_chain / k_cl_loop keep both QpArgs of a call in
+// scalar registers (selected field by field between QP #1 and QP #2), and two more fields there cost the closed-loop kernel 5 % (SGPR spills into VGPR
+// lanes).  Layout: kkt[8 B] = tolerance (the pinned x_0 may lie that far outside its own stage-0 box before the solve is refused
+// with status 2: the gate is max(1e-9, tolerance), +inf = the stage-0 state rows never gate, a NaN / infinite state is refused whatever the value),
+// kkt[8 B + 1] unused, then x0_viol (B,2): the largest stage-0 violation of the instance's last first / last QP (<= 0 inside the box, +inf for a NaN
+// state), written by one lane for accepted and refused solves alike; the slot of a QP that took no part keeps its previous value (qp_stats says -1).
+// An accepted solve is the solve of every other instance: x_0 has no box inside the solver, so the answer is the optimum of the QP without its
+// stage-0 state rows (their multipliers 0).  The tolerance is wave-uniform and read once per solve, in phase_update's `first` branch only.  The host
+// writes it before a launch (set_x0_tol); the nominal initialiser's QPs run with 0 (strict): their x_0 deviation is 0 by construction.
+__host__ __device__ inline size_t kkt_doubles(size_t B) { return 8 * B + 2 + 2 * B; }
+__host__ __device__ inline double *x0_record(double *kkt, int B) { return kkt + (size_t)8 * B; }      // [0] tolerance, [2 + 2 b + slot] violation
 
 // LDS layout of one QP wave: NX x NX buffers A_k | [T = M1 Dinv_{k-1}, vector-ALU path only] | Dinv_{k-1}, then T, then D_k | M1 -> Dinv_k (the last two rotate),
 // B_k, and a handful of stage vectors.  Everything of size n (IPM vectors) lives in an HBM/L2 workspace.
@@ -570,6 +583,15 @@ __device__ __forceinline__ FwdPlan fwd_plan(const QpState *st, int phase, int N)
     return p;
 }
 
+// The x0 gate: records the solve's largest stage-0 violation and says whether it is refused.  Deliberately NOT inlined: inlined into phase_update the
+// same five lines made the persistent closed-loop kernel 3 % slower (its register allocation moves with any change of that function, DESIGN.md
+// sections 4 (vii) and 11); as a call, once per solve and outside the tick loop, the kernel runs as fast as before.
+__device__ __noinline__ int x0_gate(double *kkt, int B, int b, int slot, double vmax, int lane) {
+    double *xr = x0_record(kkt, B);
+    if (lane == 0) xr[2 + (size_t)b * 2 + slot] = vmax;
+    return (vmax > fmax(1e-9, xr[0]) || !(vmax < INFINITY)) ? 1 : 0;
+}
+
 // first = 1: set up the instance (x0-pin check, starting rhs); else consume the solve of the current phase.
 template <int NX, int NU>
 __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, int lane, double *sm = nullptr) {
@@ -605,13 +627,13 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
 
     if (first) {
         int status = ST_INIT;
-        double viol = 0.0;   // x0 pin vs its own box (the reference applies both the pin rows and the stage-0 inequality rows)
+        double viol = -INFINITY;   // x0 pin vs its own box (the reference applies both the pin rows and the stage-0 inequality rows)
         if (lane < NX) {
             const double xv = a.x0val[(size_t)b * NX + lane];
             viol = fmax(xv - ub[NX + lane], -ub[NX + NZ + lane] - xv);
             if (isnan(viol)) viol = INFINITY;      // a NaN state (a failed run whose plant overflowed) is outside every box; wave_max would drop the NaN
         }
-        if (wla::wave_max(viol) > 1e-9) status = 2;
+        if (x0_gate(a.kkt, a.B, b, a.stat_slot, wla::wave_max(viol), lane)) status = 2;
         // warm start: the previous solve of this instance ended with a certified active set -> polish from it first
         // the first QP of a call starts from the set the first QP of an earlier call ended on (the un-tightened QPs of consecutive MPC steps
         // resemble each other more than a tightened and an un-tightened one: 2.8 against 3.9 rounds, scripts/proto/as_warm_sources.py) -- also

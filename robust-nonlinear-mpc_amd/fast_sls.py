@@ -12,6 +12,9 @@
     .solve(x0) -> dict                               .solve(x0[B,nx]) -> dict of [B,...] arrays (same keys)
     .reset_solver_to_zeros()                         .reset_solver_to_zeros()
 
+`opts.x0_box_tol` (default 0: strict; kept by the handle, slsqp_set_x0_box_tol) lets a measured state lie that far outside its own stage-0 box before a QP is refused (see
+include/slsqp.h); `get("x0_viol", (2,))` reads the largest violation of the last first / last QP.
+
 `fast_SLS` (lower case, the reference's class name) is the B=1 view returning the reference's exact shapes,
 so SCP_SLS-style callers can switch by changing one import.  All arithmetic runs in the HIP library; this
 module only moves arrays.
@@ -102,7 +105,7 @@ class BatchedFastSLS:
         self.h = self.lib.slsqp_create(C.byref(self.dims), self.B, device)
         if not self.h:
             raise RuntimeError("slsqp_create: " + self.lib.slsqp_last_error().decode())
-        self.opts = L.Opts()
+        self.opts = L.HandleOpts().bind(self.lib, self.h)
         self.lib.slsqp_default_opts(C.byref(self.opts))
         self.opts.rti_steps = 0       # fast_SLS default: iterate to convergence (fast_SLS_jit.py:214)
         import os
