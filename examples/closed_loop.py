@@ -31,6 +31,8 @@ def main():
                     help="1: the whole loop as one persistent launch (slsqp_cl_run / slsqp_cl_run_scp: instances advance independently, same bits); 0: one slsqp_cl_step per step")
     ap.add_argument("--x0-box-tol", type=float, default=0.0, help="how far the measured state may lie outside its own stage-0 box before a step is refused "
                     "(0: strict; 1e-3: what the reference's OSQP settings let through; inf: never)")
+    ap.add_argument("--solve-waves", type=int, default=1, choices=[1, 2, 4, 8], help="waves per instance of the QP solves (above 1: the multi-wave kernel, for a few runs; "
+                    "the loop then runs step by step)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -50,7 +52,7 @@ def main():
     else:
         x0 = np.tile(m.x_ref + a.x0_scale * (m.extra["x0"] - m.x_ref), (B, 1))
         W = np.stack([disturbance_stream(s, steps, m.nx) for s in range(B)], axis=1)   # seed 0 = the script's stream
-    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol)
+    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves)
     t0 = time.perf_counter()
     run = cl.run_decoupled if a.persistent else cl.run_on_device
     out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1)

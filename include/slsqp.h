@@ -159,6 +159,17 @@ int slsqp_reset(slsqp_handle *h);
    be read afterwards: slsqp_get "x0_viol", "log_x0_viol". */
 int slsqp_set_x0_box_tol(slsqp_handle *h, double tol);
 double slsqp_get_x0_box_tol(slsqp_handle *h);
+
+/* Waves per MPC instance of the QP solves (a property of the handle, like the tolerance above; slsqp_opts keeps its layout).
+   1 (default): the single-wave kernels -- one wavefront owns one instance, the right mapping for large batches.
+   2, 4, 8: every QP that slsqp_qp_solve, slsqp_solve, slsqp_cl_step and slsqp_nominal_solve run is solved by one workgroup of that many waves
+   per instance, the block-tridiagonal system by block cyclic reduction (a dependent chain of log2 N levels instead of N stages): for a caller
+   with one plant or a handful.  fp64 only (opts.precision = 1 is refused); the fused RTI chain is not used; slsqp_cl_run and slsqp_cl_run_scp
+   (one wave per instance by construction) refuse.  Every answer passes the same KKT certificate as with 1.
+   Any other value is an error (< 0, slsqp_last_error) and leaves the setting as it was.  Changing the value makes the next solve of every instance
+   factorise afresh (the two paths do not read each other's stored factors); warm-start sets and results stay valid. */
+int slsqp_set_solve_waves(slsqp_handle *h, int waves);
+int slsqp_get_solve_waves(slsqp_handle *h);
 int slsqp_sync(slsqp_handle *h);
 
 /* ---- the step in front of the path: batched linearisation (SCP_SLS.update_jacobian, solver/SCP_SLS_jit.py:251-366) ---------
@@ -259,6 +270,16 @@ void *slsqp_stream(slsqp_handle *h); /* hipStream_t, for callers that share devi
    product pair of the SLS propagation, the Gauss-Jordan SPD inverse, the D_k assembly) on packed row-major host operands; (nx,nu) = (17,4)
    or (13,4).  Cases and operand order: slsqp_api.hip, k_selftest.  Used by tests/test_gpu_parity.py::test_wave_level_building_blocks. */
 int slsqp_selftest(int nx, int nu, int which, const double *in, int n_in, double *out, int n_out);
+
+/* Diagnostic: ONE block solve  Y nu = b  of the solver's normal equations for every instance, on the handle's current A_k, B_k and weights the
+   caller gives:  Y = E diag(PI) E' + delta I,  b = E V  (E: the dynamics rows [A_k B_k -I]; no dynamics offsets).
+   PI, V: (B,n).  W: (B,N nx) = nu.  G: (B,n) = E' nu.  bmax: (B) max|b| with waves > 1, the largest forward-eliminated entry with waves = 1 (may be NULL).
+   fail: (B) 1 = a block was not positive definite (may be NULL).
+   waves = 1: the sequential block LDL' sweeps of the single-wave kernels (full factorisation).  2, 4, 8: the block cyclic reduction of the multi-wave kernel.
+   factor = 0: substitution only, with the factors the previous factorising call with the same `waves` left; refused when there is none, or when a QP
+   solve of the handle ran in between (it overwrites the factor buffers).  update_dynamics must have been called.
+   The stored factorisations of the handle's QP solves are discarded (their next solve factorises).  Used by tests/test_gpu_multiwave.py. */
+int slsqp_ne_solve(slsqp_handle *h, int waves, int factor, const double *PI, const double *V, double delta, double *W, double *G, double *bmax, int *fail, int loc);
 
 #ifdef __cplusplus
 }

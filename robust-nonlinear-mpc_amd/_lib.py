@@ -25,7 +25,8 @@ class Opts(C.Structure):
 
 class HandleOpts(Opts):
     """The slsqp_opts of one handle as BatchedFastSLS keeps them (same layout as Opts: pass with ctypes.byref), plus `x0_box_tol`: that option is a
-    property of the handle in the C ABI (slsqp_set_x0_box_tol; the struct keeps its layout), so assigning it here calls the library at once."""
+    property of the handle in the C ABI (slsqp_set_x0_box_tol; the struct keeps its layout), so assigning it here calls the library at once.
+    `solve_waves` (slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = the multi-wave kernel for small batches) works the same way."""
 
     def bind(self, lib, handle):
         self._lib, self._h = lib, handle
@@ -39,12 +40,21 @@ class HandleOpts(Opts):
     def x0_box_tol(self, tol):
         check(self._lib.slsqp_set_x0_box_tol(self._h, float(tol)))
 
+    @property
+    def solve_waves(self):
+        return int(self._lib.slsqp_get_solve_waves(self._h))
+
+    @solve_waves.setter
+    def solve_waves(self, waves):
+        check(self._lib.slsqp_set_solve_waves(self._h, int(waves)))
+
 
 EXPORTS = [
     "slsqp_default_opts", "slsqp_last_error", "slsqp_version", "slsqp_create", "slsqp_destroy", "slsqp_set_costs",
     "slsqp_set_constraints", "slsqp_update_dynamics", "slsqp_update_linear_cost", "slsqp_solve", "slsqp_get", "slsqp_reset",
     "slsqp_sync", "slsqp_qp_nnz", "slsqp_qp_update_data_mat", "slsqp_qp_update_data_vec", "slsqp_qp_solve", "slsqp_sweep",
     "slsqp_last_timing", "slsqp_kernel_timing", "slsqp_stream", "slsqp_set_model", "slsqp_set_E", "slsqp_linearize", "slsqp_cl_init", "slsqp_cl_step", "slsqp_nominal_solve", "slsqp_set", "slsqp_cl_log", "slsqp_selftest", "slsqp_result_bytes", "slsqp_cl_run", "slsqp_cl_run_stats", "slsqp_cl_run_scp", "slsqp_set_x0_box_tol", "slsqp_get_x0_box_tol",
+    "slsqp_set_solve_waves", "slsqp_get_solve_waves", "slsqp_ne_solve",
 ]
 
 _lib = None
@@ -104,6 +114,9 @@ def load():
     lib.slsqp_set_x0_box_tol.argtypes = [vp, C.c_double]
     lib.slsqp_get_x0_box_tol.argtypes = [vp]
     lib.slsqp_get_x0_box_tol.restype = C.c_double
+    lib.slsqp_set_solve_waves.argtypes = [vp, C.c_int]
+    lib.slsqp_get_solve_waves.argtypes = [vp]
+    lib.slsqp_ne_solve.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_double, dp, dp, dp, ip, C.c_int]
     lib.slsqp_selftest.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, C.c_int]
     lib.slsqp_stream.argtypes = [vp]
     lib.slsqp_stream.restype = vp

@@ -22,10 +22,12 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
-        state never fails a step on its own (slsqp_set_x0_box_tol)."""
+        state never fails a step on its own (slsqp_set_x0_box_tol).
+        solve_waves: 1, or 2 / 4 / 8 waves per instance for the QP solves (slsqp_set_solve_waves: for one plant or a handful); run_decoupled then
+        takes the step-by-step loop, the persistent kernels being one wave per instance."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -36,6 +38,8 @@ class ClosedLoopMPC:
             fast_sls_rti_steps = m.fast_sls_rti_steps
         self.f.set_rti_steps(fast_sls_rti_steps)
         self.f.opts.x0_box_tol = float(x0_box_tol)
+        if solve_waves != 1:
+            self.f.opts.solve_waves = int(solve_waves)
         self.steps_done = 0
 
     def close(self):
@@ -128,6 +132,10 @@ class ClosedLoopMPC:
         converge mode (fast_sls_rti_steps None), precision = 1 and SLSQP_FUSE_RTI=0 are refused with the library's message.
         Adds `qp_stats` (B, steps, 2, 8) (next to `x0_violation` (B, steps, 2), which every logged run has), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the run's totals in their first entry."""
         f, m, N, B = self.f, self.m, self.N, self.B
+        if f.opts.solve_waves > 1:      # the persistent kernels are one wave per instance: the same loop, step by step (no qp_stats / loop_stats)
+            out = self.run_on_device(x0, steps, W, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
+            out["rounds"] = steps
+            return out
         L.check(f.lib.slsqp_cl_log(f.h, int(steps)))
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
         Wc = None if W is None else _c(W)

@@ -15,6 +15,7 @@
 
 #include "../../include/slsqp.h"
 #include "slsqp_kernels.hpp"
+#include "slsqp_mw.hpp"
 
 using namespace slsqp;
 
@@ -69,6 +70,9 @@ struct slsqp_handle {
     int *qpstat;                // (B,2,8) per-QP statistics, see QpArgs::qpstat
     double *x0viol;             // (B,2) largest stage-0 violation of the instance's last first / last QP: part of the kkt allocation (x0_record, slsqp_kernels.hpp)
     double x0_box_tol = 0.0;    // slsqp_set_x0_box_tol: the tolerance the following launches ask for
+    int solve_waves = 1;        // slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = k_qp_solve_mw (one workgroup of that many waves per instance)
+    double *cr = nullptr;       // (B,N,3,nx,nx) scratch of the cyclic reduction (slsqp_mw.hpp), allocated by the first launch that needs it
+    int ne_waves = 0;           // slsqp_ne_solve: the path whose factors the last factorising call left (0 = none)
     double x0_tol_dev = 0.0;    // the tolerance of the x0 gate the device currently holds (kkt[8 B]; written when a launch asks for another one)
     double *x0vlog = nullptr;   // (B, qplog_steps, 2) per-step copy of x0viol of a slsqp_cl_run / slsqp_cl_run_scp (allocated with qplog)
     double *lg_x0v = nullptr;   // (B, log_steps, 2) the same for slsqp_cl_step loops (part of the slsqp_cl_log buffers)
@@ -1199,8 +1203,70 @@ static QpArgs make_qp_args(slsqp_handle *h, const int *run, const slsqp_opts *o,
     return a;
 }
 
+// ---- the multi-wave path (slsqp_mw.hpp): one workgroup of solve_waves waves per instance -------------------------
+static int ensure_cr(slsqp_handle *h) {
+    if (h->cr) return 0;
+    return dalloc(h->owned, &h->cr, (size_t)h->B * h->d.N * 3 * h->d.nx * h->d.nx);
+}
+// LDS of a multi-wave workgroup: the work areas of the reduction, or the two n-vectors of the phase logic (wave 0, between the block solves)
+template <int NX, int NU>
+static size_t mw_lds_bytes(const slsqp_handle *h, int W) {
+    return sizeof(double) * std::max((size_t)MwLds<NX, NU>::total(h->d.N, W), (size_t)(2 * h->n + 8));
+}
+// more than 64 KB of dynamic LDS (quadrotor and rocket with 8 waves) has to be asked for.  The attribute belongs to the function on the CURRENT device, so it
+// is set before every launch (a host-side table write), not once per process: handles on several devices share this code
+template <typename K>
+static int allow_lds(K kernel) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    return 0;
+}
+template <int NX, int NU>
+static int launch_qp_mw_t(slsqp_handle *h, const QpArgs &a, int max_iter) {
+    if (ensure_cr(h) || allow_lds(k_qp_solve_mw<NX, NU>)) return -1;
+    const int W = h->solve_waves;
+    const size_t lds = mw_lds_bytes<NX, NU>(h, W);
+    if (lds > 160 * 1024) return fail("solve_waves: the work areas of that many waves do not fit the LDS for this horizon");
+    const int max_ticks = qp_max_ticks(a, max_iter);
+    const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
+    if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
+    hipLaunchKernelGGL((k_qp_solve_mw<NX, NU>), dim3(h->B), dim3(64 * W), lds, h->st, a, max_ticks, h->cr, W);
+    if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the stored factorisations of every instance are forgotten (the two paths keep theirs in different scratch buffers and layouts): the next
+// solve of each instance factorises.  Warm sets and everything else in QpState stay.
+__global__ void k_forget_factors(int B, double *state) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    QpState *st = (QpState *)state + b;
+    st->fact_call = 0.0; st->uf_valid = 0.0;
+}
+static void forget_factors(slsqp_handle *h) { hipLaunchKernelGGL(k_forget_factors, dim3((h->B + 255) / 256), dim3(256), 0, h->st, h->B, h->qpstate); }
+
+// what the multi-wave path does not serve is refused at the entry points, before anything is launched or a timeline interval is begun
+static int mw_refuse(const slsqp_handle *h, const slsqp_opts &o) {
+    if (h->solve_waves > 1 && o.precision == 1) return fail("solve_waves > 1: the multi-wave QP kernel is fp64 only (precision = 1 needs solve_waves = 1)");
+    return 0;
+}
+
 static int launch_qp(slsqp_handle *h, const int *run, const slsqp_opts *o, int warm, const double *prox = nullptr, int stat_slot = 0, int snap_take = 0, int snap_use = 0,
                      int warm_shift = 0) {
+    h->ne_waves = 0;      // (this launch overwrites the factor buffers: slsqp_ne_solve(factor = 0) may not substitute with them)
+    if (h->solve_waves > 1) {
+        if (mw_refuse(h, *o)) return -1;
+        flag_nonfinite(h, run);
+        const QpArgs a = make_qp_args(h, h->runq, o, warm, prox, stat_slot, snap_take, snap_use, warm_shift);
+        h->time_kernels = o->time_kernels != 0;
+        h->mx_retry = 0;
+        int rc = -1;
+#define X(NX_, NU_) if (h->d.nx == NX_ && h->d.nu == NU_) rc = launch_qp_mw_t<NX_, NU_>(h, a, o->qp_max_iter);
+        SLSQP_DIM_LIST
+#undef X
+        if (rc) return -1;
+        apply_nonfinite(h, run, stat_slot);
+        return 0;
+    }
     flag_nonfinite(h, run);
     const QpArgs a = make_qp_args(h, h->runq, o, warm, prox, stat_slot, snap_take, snap_use, warm_shift);
     const bool mx = o->precision == 1;
@@ -1301,6 +1367,7 @@ static int launch_chain_t(slsqp_handle *h, ChainArgs &c) {
     const size_t lds = sizeof(double) * std::max({(size_t)qp_lds_doubles<NX, NU>(h->d.N), (size_t)(2 * h->n + 8), (size_t)sweep_lds_doubles<NX, NU>(), (size_t)sweep_prop_lds_doubles<NX, NU>()});
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
+    h->ne_waves = 0;      // (slsqp_ne_solve's factors do not survive a QP solve)
     hipLaunchKernelGGL((k_rti_chain<NX, NU>), dim3(h->B), dim3(64), lds, h->st, c);
     if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
     HIPCHK(hipGetLastError());
@@ -1346,6 +1413,7 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
     if (!h->have_costs || !h->have_cons || !h->have_dyn) return fail("set_costs, set_constraints and update_dynamics must be called first");
     slsqp_opts o;
     if (opts) o = *opts; else slsqp_default_opts(&o);
+    if (mw_refuse(h, o)) return -1;
     const slsqp_dims &d = h->d;
     const int B = h->B, gb = (B + 255) / 256;
     // x_0 is pinned to -x0 (qp_jit.py:376-379)
@@ -1393,7 +1461,7 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
     // waits for -- 1.1 against 1.6 ms per rocket RTI step -- while from ~150 instances on the columns of one instance would only compete with other
     // instances' for the same SIMDs.  fuse_rti = 2 forces the chain, slsqp_cl_run always uses it.)
     const bool fuse_here = o.fuse_rti == 2 || h->cl_round || (o.fuse_rti == 1 && (long)B * (d.N + 1) >= 3072);
-    if (rti && steps == 1 && o.precision == 0 && fuse_here && chain_allowed() && sweep_shared_allowed() && !h->general_G) {
+    if (rti && steps == 1 && o.precision == 0 && fuse_here && h->solve_waves == 1 && chain_allowed() && sweep_shared_allowed() && !h->general_G) {
         // fast_SLS.solve with rti_steps = 1 (the rocket script's setting) as ONE launch: every wave takes its instance through the whole chain
         h->time_kernels = o.time_kernels != 0;
         ChainArgs c = make_chain_args(h, o, active, wshift);
@@ -1485,6 +1553,17 @@ extern "C" int slsqp_set_x0_box_tol(slsqp_handle *h, double tol) {
     return 0;
 }
 extern "C" double slsqp_get_x0_box_tol(slsqp_handle *h) { return h->x0_box_tol; }
+
+extern "C" int slsqp_set_solve_waves(slsqp_handle *h, int waves) {
+    if (waves != 1 && waves != 2 && waves != 4 && waves != 8) return fail("slsqp_set_solve_waves: waves must be 1 (the single-wave kernels), 2, 4 or 8");
+    if (waves == h->solve_waves) return 0;
+    hipSetDevice(h->dev);
+    forget_factors(h);      // neither path may read the factors the other one stored
+    HIPCHK(hipGetLastError());
+    h->solve_waves = waves;
+    return 0;
+}
+extern "C" int slsqp_get_solve_waves(slsqp_handle *h) { return h->solve_waves; }
 
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
@@ -1635,6 +1714,7 @@ extern "C" int slsqp_nominal_solve(slsqp_handle *h, int max_qp, double tol, doub
     if (h->model_id < 0 || !h->have_costs || !h->have_cons) return fail("set_model, set_costs and set_constraints must be called first");
     slsqp_opts o;
     if (opts) o = *opts; else slsqp_default_opts(&o);
+    if (mw_refuse(h, o)) return -1;
     const slsqp_dims &d = h->d;
     const int B = h->B, gbi = (B + 255) / 256;
     if (max_qp <= 0) max_qp = 120;
@@ -1720,6 +1800,7 @@ __global__ void k_cl_log_x0v(int B, int log_steps, int step, const double *x0vio
 extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc, const slsqp_opts *opts) {
     hipSetDevice(h->dev);
     if (h->model_id < 0) return fail("slsqp_set_model must be called first");
+    if (opts && mw_refuse(h, *opts)) return -1;
     const slsqp_dims &d = h->d;
     const int gb = (h->B + 63) / 64;
     const double *dw = nullptr;
@@ -1945,6 +2026,8 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
     if (h->log_steps > 0 && h->log_steps < steps) return fail("slsqp_cl_run: the device-side log (slsqp_cl_log) is shorter than the run");
     slsqp_opts o;
     if (opts) o = *opts; else slsqp_default_opts(&o);
+    if (h->solve_waves > 1) return fail("slsqp_cl_run: the persistent loop is one wave per instance: solve_waves must be 1 (use slsqp_cl_step with solve_waves > 1)");
+    h->ne_waves = 0;      // (slsqp_ne_solve's factors do not survive a QP solve)
     if (!(o.rti_steps == 1 && o.precision == 0 && o.fuse_rti && chain_allowed() && sweep_shared_allowed()) || h->general_G)
         return fail("slsqp_cl_run needs the fused RTI chain: rti_steps = 1, fp64, fuse_rti = 1, box constraints (use slsqp_cl_step otherwise)");
     const slsqp_dims &d = h->d;
@@ -2024,6 +2107,8 @@ extern "C" int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const doubl
     if (h->log_steps > 0 && h->log_steps < steps) return fail("slsqp_cl_run_scp: the device-side log (slsqp_cl_log) is shorter than the run");
     slsqp_opts o;
     if (opts) o = *opts; else slsqp_default_opts(&o);
+    if (h->solve_waves > 1) return fail("slsqp_cl_run_scp: the persistent loop is one wave per instance: solve_waves must be 1 (use slsqp_cl_step with solve_waves > 1)");
+    h->ne_waves = 0;      // (slsqp_ne_solve's factors do not survive a QP solve)
     if (o.rti_steps <= 0) return fail("slsqp_cl_run_scp: fast-SLS converge mode (rti_steps <= 0) does not run inside the persistent loop (use slsqp_cl_step)");
     if (o.precision != 0) return fail("slsqp_cl_run_scp: mixed precision (precision = 1) does not run inside the persistent loop: fp64 only (use slsqp_cl_step)");
     if (h->general_G) return fail("slsqp_cl_run_scp: box constraints only (general G: use the sweep-level boundary)");
@@ -2092,6 +2177,7 @@ extern "C" int slsqp_qp_solve(slsqp_handle *h, double *x, double *y, int *status
     if (!h->have_costs) return fail("costs not set");
     slsqp_opts o;
     if (opts) o = *opts; else slsqp_default_opts(&o);
+    if (mw_refuse(h, o)) return -1;
     HIPCHK(hipEventRecord(h->ev[0], h->st));
     if (launch_qp(h, nullptr, &o, o.warm_start ? 1 : 0)) return -1;
     HIPCHK(hipEventRecord(h->ev[1], h->st));
@@ -2188,4 +2274,61 @@ extern "C" int slsqp_selftest(int nx, int nu, int which, const double *in, int n
     hipFree(din); hipFree(dout);
     if (rc == -2) return fail("selftest: (nx, nu) must be (17, 4) or (13, 4)");
     return rc ? fail("selftest: HIP error") : 0;
+}
+
+// ---- one block solve of the normal equations on given weights (diagnostic, like slsqp_selftest) -----------------------
+template <int NX, int NU>
+static int launch_ne_solve_t(slsqp_handle *h, int W, int factor, double delta, double *dPI, double *dV, double *dW, double *dG, double *dUF, double *dout) {
+    if (allow_lds(k_ne_solve<NX, NU>)) return -1;
+    NeG<NX, NU> g;
+    g.A = h->A; g.Bm = h->Bm; g.ub = h->ubg; g.lb = h->lbg; g.Linv = h->Linv; g.PI = dPI; g.V = dV; g.G = dG; g.W = dW; g.UF = dUF; g.N = h->d.N;
+    const size_t lds = W == 1 ? sizeof(double) * (size_t)qp_lds_doubles<NX, NU>(h->d.N) : sizeof(double) * (size_t)MwLds<NX, NU>::total(h->d.N, W);
+    if (lds > 160 * 1024) return fail("slsqp_ne_solve: the work areas of that many waves do not fit the LDS for this horizon");
+    hipLaunchKernelGGL((k_ne_solve<NX, NU>), dim3(h->B), dim3(64 * W), lds, h->st, g, h->B, h->cr, W, factor, delta, dout);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+extern "C" int slsqp_ne_solve(slsqp_handle *h, int waves, int factor, const double *PI, const double *V, double delta, double *W, double *G, double *bmax, int *fail_out,
+                              int loc) {
+    hipSetDevice(h->dev);
+    if (waves != 1 && waves != 2 && waves != 4 && waves != 8) return fail("slsqp_ne_solve: waves must be 1, 2, 4 or 8");
+    if (!PI || !V || !W || !G) return fail("slsqp_ne_solve: PI, V, W and G are required");
+    if (!h->have_dyn) return fail("slsqp_ne_solve: update_dynamics must be called first (A and B are the handle's)");
+    if (!factor && h->ne_waves != waves) return fail("slsqp_ne_solve: factor = 0 needs a factorising call with the same `waves` before it, with no QP solve in between");
+    if (waves > 1 && ensure_cr(h)) return -1;
+    const size_t B = h->B, n = h->n, nw = (size_t)h->d.N * h->d.nx;
+    // device operands: PI | V | G (n each), W | UF (N nx each), (max|b|, flag) per instance
+    const size_t total = B * (3 * n + 2 * nw + 2);
+    double *buf = nullptr;
+    HIPCHK(hipMalloc(&buf, sizeof(double) * total));
+    double *dPI = buf, *dV = dPI + B * n, *dG = dV + B * n, *dW = dG + B * n, *dUF = dW + B * nw, *dout = dUF + B * nw;
+    const hipMemcpyKind kin = loc == SLSQP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, kout = loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    int rc = 0;
+    std::vector<double> ho(2 * B);
+    if (hipMemsetAsync(dG, 0, sizeof(double) * B * (n + 2 * nw + 2), h->st) != hipSuccess) rc = -1;
+    if (!rc && hipMemcpyAsync(dPI, PI, sizeof(double) * B * n, kin, h->st) != hipSuccess) rc = -1;
+    if (!rc && hipMemcpyAsync(dV, V, sizeof(double) * B * n, kin, h->st) != hipSuccess) rc = -1;
+    if (!rc) {
+        // the QP solves' own stored factors live in the same scratch: they are gone after this call
+        forget_factors(h);
+        rc = -2;
+#define X(NX_, NU_) if (h->d.nx == NX_ && h->d.nu == NU_) rc = launch_ne_solve_t<NX_, NU_>(h, waves, factor, delta, dPI, dV, dW, dG, dUF, dout);
+        SLSQP_DIM_LIST
+#undef X
+    }
+    if (!rc && hipMemcpyAsync(W, dW, sizeof(double) * B * nw, kout, h->st) != hipSuccess) rc = -1;
+    if (!rc && hipMemcpyAsync(G, dG, sizeof(double) * B * n, kout, h->st) != hipSuccess) rc = -1;
+    if (!rc && hipMemcpyAsync(ho.data(), dout, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->st) != hipSuccess) rc = -1;
+    if (hipStreamSynchronize(h->st) != hipSuccess && !rc) rc = -1;
+    if (!rc) {
+        std::vector<double> bm(B); std::vector<int> fl(B);
+        for (size_t b = 0; b < B; b++) { bm[b] = ho[2 * b]; fl[b] = (int)ho[2 * b + 1]; }
+        const hipMemcpyKind kh = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice;
+        if (bmax && hipMemcpy(bmax, bm.data(), sizeof(double) * B, kh) != hipSuccess) rc = -1;
+        if (fail_out && hipMemcpy(fail_out, fl.data(), sizeof(int) * B, kh) != hipSuccess) rc = -1;
+        if (factor) h->ne_waves = waves;
+    }
+    hipFree(buf);
+    if (rc == -1) return fail("slsqp_ne_solve: HIP error");
+    return rc ? -1 : 0;
 }

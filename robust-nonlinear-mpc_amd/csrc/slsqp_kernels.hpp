@@ -592,8 +592,17 @@ __device__ __noinline__ int x0_gate(double *kkt, int B, int b, int slot, double 
     return (vmax > fmax(1e-9, xr[0]) || !(vmax < INFINITY)) ? 1 : 0;
 }
 
+// Hand-over through global memory between the lanes of the wave that runs the phase logic.  WG1 (every kernel whose workgroup is that one wave):
+// wla::wsync_mem().  In a workgroup of several waves (k_qp_solve_mw: the phase logic on wave 0, the others waiting at the barrier behind it) a
+// workgroup barrier inside the phase logic would pair with that one: there the fence alone orders the wave's own stores and loads.
+template <bool WG1>
+__device__ __forceinline__ void phase_sync() {
+    if constexpr (WG1) wla::wsync_mem();
+    else { __threadfence_block(); __builtin_amdgcn_wave_barrier(); }
+}
+
 // first = 1: set up the instance (x0-pin check, starting rhs); else consume the solve of the current phase.
-template <int NX, int NU>
+template <int NX, int NU, bool WG1 = true>
 __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, int lane, double *sm = nullptr) {
     using L = Lay<NX, NU>;
     constexpr int NZ = L::NZ, SR = L::SR;
@@ -739,7 +748,7 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
         s.cold_as = 1.0; s.warm = 2.0; s.pol_round = 0.0; s.pol_fail = 0.0; s.nviol = 0.0;
         as_from_init = true;
         phase = P_POL0;
-        wla::wsync_mem();
+        phase_sync<WG1>();
     }
     if (phase == P_INIT) {
         for (int o = lane; o < N * NX; o += 64) NUA[o] = W[o];
@@ -858,7 +867,7 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
                 CL[e] = (firstp ? 0.0 : CL[e]) + gg;
             }
             for (int o = lane; o < N * NX; o += 64) NUP[o] = (firstp ? 0.0 : NUP[o]) + W[o];
-            wla::wsync_mem();
+            phase_sync<WG1>();
         }
         // Correction of the active set from the solve in CU (primal) / CL (E'nu): multipliers of the wrong sign leave, violated bounds enter --
         // all of them for the inputs (control constraints are active on arcs), but for a state component only the stages where its violation
@@ -927,7 +936,7 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
             return rep;
         };
         auto apply_set = [&]() {
-            wla::wsync_mem();
+            phase_sync<WG1>();
 #pragma unroll 4
             for (int e = lane; e < n; e += 64) {
                 const Elem el = elem_of<NX, NU>(e, n, N, ub, qg, cst);
@@ -1049,7 +1058,7 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
             if (s.warm > 0.0 && (nv > (double)a.as_max_viol || (s.pol_round > 0.0 && nv > 2.0 * s.nviol + 8.0 && nv > 24.0))) { again = false; give_up = true; }
             s.nviol = nv;
             if (again) { s.pol_round += 1.0; if (fused_look) fused_apply(); else apply_set(); s.uf_valid = 1.0; }      // the sweep just consumed solved the un-refined system of this attempt
-            if (fused_look) wla::wsync_mem();
+            if (fused_look) phase_sync<WG1>();
         } else if (phase == P_POL0 && s.warm > 0.0) give_up = true;      // out of rounds (or a pivot failed): do not refine a set known to be wrong
         if (again) {
             phase = P_POL0;
@@ -1139,7 +1148,7 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
     }
 
     if (start_iter) {
-        wla::wsync_mem();
+        phase_sync<WG1>();
         // residuals, complementarity, termination test; predictor rhs written in the same pass
         double rmax = 0.0, musum = 0.0;
 #pragma unroll 4
@@ -1229,7 +1238,7 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
     }
 
     if (phase == P_DONE) {
-        wla::wsync_mem();
+        phase_sync<WG1>();
         // ---- write-out (reference layouts: primal qp_jit.py:489-490, duals :493-501) ----
         double *pr = a.primal + (size_t)b * n, *du = a.dual + (size_t)b * mb;
         double csum = 0.0, nact = 0.0;

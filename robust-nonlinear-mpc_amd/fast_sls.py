@@ -14,6 +14,8 @@
 
 `opts.x0_box_tol` (default 0: strict; kept by the handle, slsqp_set_x0_box_tol) lets a measured state lie that far outside its own stage-0 box before a QP is refused (see
 include/slsqp.h); `get("x0_viol", (2,))` reads the largest violation of the last first / last QP.
+`opts.solve_waves` (default 1; slsqp_set_solve_waves) = 2, 4 or 8 solves every QP with one workgroup of that many waves per instance (block cyclic
+reduction): the setting for B = 1 or a handful of instances, where the single-wave kernels leave the device idle.
 
 `fast_SLS` (lower case, the reference's class name) is the B=1 view returning the reference's exact shapes,
 so SCP_SLS-style callers can switch by changing one import.  All arithmetic runs in the HIP library; this
@@ -285,6 +287,18 @@ class BatchedFastSLS:
         it = np.empty(self.B, dtype=np.int32)
         L.check(self.lib.slsqp_qp_solve(self.h, _ptr(x), _ptr(y), st.ctypes.data_as(C.c_void_p), it.ctypes.data_as(C.c_void_p), L.HOST, C.byref(self.opts)))
         return x, y, st, it, self.timing_ms()["qp"] * 1e-3
+
+    def ne_solve(self, PI, V, waves=1, factor=True, delta=1e-13):
+        """One block solve  Y nu = b  of the solver's normal equations per instance (slsqp_ne_solve: a diagnostic), Y = E diag(PI) E' + delta,
+        b = E V on the handle's current A_k, B_k.  waves = 1: the single-wave kernels' sweeps; 2, 4, 8: the multi-wave kernel's cyclic reduction.
+        Returns dict(nu (B,N,nx), G (B,n) = E' nu, bmax (B), fail (B))."""
+        PI, V = _c(PI), _c(V)
+        assert PI.shape == (self.B, self.n) and V.shape == (self.B, self.n)
+        W, G = np.empty((self.B, self.N, self.m.nx)), np.empty((self.B, self.n))
+        bmax, fl = np.empty(self.B), np.empty(self.B, dtype=np.int32)
+        L.check(self.lib.slsqp_ne_solve(self.h, int(waves), 1 if factor else 0, _ptr(PI), _ptr(V), float(delta), _ptr(W), _ptr(G), _ptr(bmax),
+                                        fl.ctypes.data_as(C.c_void_p), L.HOST))
+        return dict(nu=W, G=G, bmax=bmax, fail=fl)
 
     def sweep(self, eta, eta_f):
         m, N, B = self.m, self.N, self.B
