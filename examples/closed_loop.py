@@ -7,6 +7,7 @@ fast_sls_rti_steps, step counts and (rocket) seed-s disturbance streams; B indep
     python examples/closed_loop.py --model quadrotor [--runs 256]          # random x0 around hover (the script's x0 is unseeded), 30 steps
     python examples/closed_loop.py --model rocket    [--runs 256] [--x0-scale 0.3]
     ... --persistent 1                                                     # the same loop as ONE persistent launch (same bits)
+    ... --reference neutral | figure8                                      # track the plant's neutral point / a figure of eight in x, y
 
 The first nominal comes from the GPU initialiser (slsqp_nominal_solve) in place of IPOPT."""
 import argparse
@@ -33,6 +34,9 @@ def main():
                     "(0: strict; 1e-3: what the reference's OSQP settings let through; inf: never)")
     ap.add_argument("--solve-waves", type=int, default=1, choices=[1, 2, 4, 8], help="waves per instance of the QP solves (above 1: the multi-wave kernel, for a few runs; "
                     "the loop then runs step by step)")
+    ap.add_argument("--reference", default="none", choices=["none", "neutral", "figure8"],
+                    help="what the loop tracks: none = the cost around the origin of the raw state (the scripts); neutral = the setpoint (x_ref, u_ref); "
+                    "figure8 = x = 0.3 sin 2t, y = 0.3 (1 - cos 2t), z constant, the rest the neutral point (plants with a position: quadrotor, rocket)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -52,7 +56,18 @@ def main():
     else:
         x0 = np.tile(m.x_ref + a.x0_scale * (m.extra["x0"] - m.x_ref), (B, 1))
         W = np.stack([disturbance_stream(s, steps, m.nx) for s in range(B)], axis=1)   # seed 0 = the script's stream
-    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves)
+    Xref = None
+    if a.reference == "neutral":
+        Xref, Uref = np.asarray(m.x_ref, dtype=float)[None, :], np.asarray(m.u_ref, dtype=float)[None, :]
+    elif a.reference == "figure8":
+        if a.model == "pendulum":
+            ap.error("--reference figure8 needs a plant with a position in space (quadrotor, rocket)")
+        T = steps + N + 1
+        t = 0.05 * np.arange(T)                                              # row t of the reference = MPC step t (RK4 step 0.05 s)
+        Xref = np.tile(np.asarray(m.x_ref, dtype=float), (T, 1))
+        Xref[:, 0], Xref[:, 1] = 0.3 * np.sin(2.0 * t), 0.3 * (1.0 - np.cos(2.0 * t))
+        Uref = np.tile(np.asarray(m.u_ref, dtype=float), (T, 1))
+    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref))
     t0 = time.perf_counter()
     run = cl.run_decoupled if a.persistent else cl.run_on_device
     out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1)
@@ -61,6 +76,10 @@ def main():
     dist1 = np.linalg.norm(out["state_trajectory"][:, :, -1] - m.x_ref, axis=1).mean()
     print(f"{a.model}: {B} runs x {steps} MPC steps (N={N}, rti={cl.rti}) in {dt:.2f} s; nominal NLP solved for {np.mean(cl.nlp_status == 0):.3f}; "
           f"MPC steps solved {out['success'].mean():.3f}; mean |x - x_ref| {dist0:.3f} -> {dist1:.3f}; QP {out['t_qp'].sum():.0f} ms, sweeps {out['t_riccati'].sum():.0f} ms")
+    if Xref is not None:
+        rows = np.minimum(np.arange(steps), len(Xref) - 1)
+        err = np.linalg.norm(out["state_trajectory"].transpose(0, 2, 1) - Xref[rows][None], axis=2).mean(axis=0)      # (steps,)
+        print(f"reference {a.reference}: mean distance of the measured state to the reference {err[0]:.3f} at the first step -> {err[-1]:.3f} at the last")
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         cl.save_npz(os.path.join(a.out, f"{a.model}_robust_closed_loop_run0.npz"), out, 0)

@@ -170,12 +170,29 @@ double slsqp_get_x0_box_tol(slsqp_handle *h);
    factorise afresh (the two paths do not read each other's stored factors); warm-start sets and results stay valid. */
 int slsqp_set_solve_waves(slsqp_handle *h, int waves);
 int slsqp_get_solve_waves(slsqp_handle *h);
+
+/* Reference trajectory of the closed loop (a property of the handle, like the two settings above; slsqp_opts keeps its layout).
+   Xref (T,nx), Uref (T,nu) shared by the batch (per_instance = 0), or (B,T,nx), (B,T,nu) (per_instance = 1); T >= 1; host or device buffers (`loc`),
+   copied by the call.  Row t belongs to absolute MPC time t, counted from the slsqp_cl_init that starts a run: at MPC step s (completed steps of the
+   instance since slsqp_cl_init) stage k = 0..N of the horizon uses row min(s + k, T - 1) -- the last row is held, T = 1 is a setpoint.  The step's cost is
+       sum_k (x_k - xr)'Q(x_k - xr) + (u_k - ur)'R(u_k - ur) + (x_N - xr_N)'Qf(x_N - xr_N),
+   i.e. the linear cost of every SCP iteration of the step becomes q = 2 H (y_nom - y_ref window); H, the bounds, c, A, B and the tubes do not depend
+   on it.  The reference need not be feasible or dynamically consistent.  Uref = NULL: zero input reference.  Xref = NULL with T = 0 clears the
+   reference (the default: q = 2 H y_nom); a zero reference gives the same bits as none.
+   Errors (< 0, slsqp_last_error; the previous reference stays in force): T < 0, T = 0 with Xref, T > 0 without, a NaN or infinite entry,
+   per_instance outside {0, 1}.
+   Reaches every place where the library forms the cost: slsqp_linearize (window of the handle's step count: 0 after slsqp_cl_init, + 1 per
+   slsqp_cl_step, + steps per slsqp_cl_run / slsqp_cl_run_scp), slsqp_cl_step, slsqp_cl_run (persistent and round-based: every instance reads the window
+   of its own step), slsqp_cl_run_scp, and slsqp_nominal_solve (objective and QPs use the window of step 0, so the first nominal minimises the tracked
+   cost).  Survives slsqp_cl_init (which only restarts the step count); may be replaced between runs.  slsqp_update_linear_cost, slsqp_solve and
+   slsqp_qp_* bring their own q and are not affected. */
+int slsqp_cl_set_reference(slsqp_handle *h, const double *Xref, const double *Uref, int T, int per_instance, int loc);
 int slsqp_sync(slsqp_handle *h);
 
 /* ---- the step in front of the path: batched linearisation (SCP_SLS.update_jacobian, solver/SCP_SLS_jit.py:251-366) ---------
    model_id: 0 pendulum, 1 quadrotor, 2 rocket (ODEs of dyn/{pendulum,quadrotor,rocket}.py, RK4 h=0.05, dyn/model.py:15-34); g_raw (ni): the plant's stage bound g.
    slsqp_linearize: X (B,N+1,nx), U (B,N,nu) nominal trajectories (stage-major) -> A,B (forward-mode AD through RK4),
-   c_k = f(x_k,u_k) - x_{k+1}, g_k = g - G[x_k;u_k], g_N = gf - Gf x_N, q = 2 H y_nom, then the un-tightened bounds; E is untouched
+   c_k = f(x_k,u_k) - x_{k+1}, g_k = g - G[x_k;u_k], g_N = gf - Gf x_N, q = 2 H y_nom (2 H (y_nom - y_ref) with slsqp_cl_set_reference), then the un-tightened bounds; E is untouched
    (set it once with slsqp_update_dynamics or slsqp_set_E). Equivalent to update_dynamics + update_linear_cost. */
 int slsqp_set_model(slsqp_handle *h, int model_id, const double *g_raw);
 int slsqp_set_E(slsqp_handle *h, const double *E, int loc);   /* E (N+1,nx,nw) */

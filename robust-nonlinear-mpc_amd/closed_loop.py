@@ -22,12 +22,13 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
         state never fails a step on its own (slsqp_set_x0_box_tol).
         solve_waves: 1, or 2 / 4 / 8 waves per instance for the QP solves (slsqp_set_solve_waves: for one plant or a handful); run_decoupled then
-        takes the step-by-step loop, the persistent kernels being one wave per instance."""
+        takes the step-by-step loop, the persistent kernels being one wave per instance.
+        reference: see set_reference (None: the cost is around the origin of the raw state, as in the reference's scripts)."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -41,6 +42,20 @@ class ClosedLoopMPC:
         if solve_waves != 1:
             self.f.opts.solve_waves = int(solve_waves)
         self.steps_done = 0
+        if reference is not None:
+            self.set_reference(reference)
+
+    def set_reference(self, reference, Uref=None):
+        """What the closed loop tracks from the next reset() on: a tuple (Xref, Uref) or Xref, Uref -- arrays (T,nx), (T,nu) shared by the batch or
+        (B,T,nx), (B,T,nu) per instance, row t for MPC step t after reset(), last row held (BatchedFastSLS.set_reference); "neutral": the
+        setpoint (model.x_ref, model.u_ref), the plant's own neutral point; None: no reference."""
+        if isinstance(reference, str):
+            if reference != "neutral":
+                raise ValueError(f"reference: unknown shorthand {reference!r} (only \"neutral\")")
+            reference, Uref = np.asarray(self.m.x_ref, dtype=float)[None, :], np.asarray(self.m.u_ref, dtype=float)[None, :]
+        elif isinstance(reference, tuple) and len(reference) == 2 and Uref is None:
+            reference, Uref = reference
+        self.f.set_reference(reference, Uref)
 
     def close(self):
         self.f.close()

@@ -71,6 +71,7 @@ struct slsqp_handle {
     double *x0viol;             // (B,2) largest stage-0 violation of the instance's last first / last QP: part of the kkt allocation (x0_record, slsqp_kernels.hpp)
     double x0_box_tol = 0.0;    // slsqp_set_x0_box_tol: the tolerance the following launches ask for
     int solve_waves = 1;        // slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = k_qp_solve_mw (one workgroup of that many waves per instance)
+    double *ref_Y = nullptr; int ref_T = 0; size_t ref_stride = 0;      // slsqp_cl_set_reference: packed rows [x_ref; u_ref] (T, nz), per instance with ref_stride = T nz, shared with 0; ref_T = 0: none
     double *cr = nullptr;       // (B,N,3,nx,nx) scratch of the cyclic reduction (slsqp_mw.hpp), allocated by the first launch that needs it
     int ne_waves = 0;           // slsqp_ne_solve: the path whose factors the last factorising call left (0 = none)
     double x0_tol_dev = 0.0;    // the tolerance of the x0 gate the device currently holds (kkt[8 B]; written when a launch asks for another one)
@@ -98,6 +99,7 @@ struct slsqp_handle {
     double *lg_x, *lg_u, *lg_bx, *lg_bu, *lg_state, *lg_u0, *lg_pinf; int *lg_succ, *lg_it;
 };
 
+static RefArgs ref_args(slsqp_handle *h) { return RefArgs{h->ref_Y, h->ref_T, h->ref_stride}; }
 static Costs costs_of(slsqp_handle *h) {
     const int nx = h->d.nx, nu = h->d.nu;
     Costs c;
@@ -247,6 +249,7 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     free_all(h->owned);
     if (h->stage) hipFree(h->stage);
     if (h->cl_W) hipFree(h->cl_W);
+    if (h->ref_Y) hipFree(h->ref_Y);
     if (h->qplog) hipFree(h->qplog);
     if (h->x0vlog) hipFree(h->x0vlog);
     if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
@@ -727,8 +730,8 @@ struct LoopArgs {
 };
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
-template <int MODEL>
-__device__ CLW_FN void cl_step_begin(const LoopArgs &L, int b, int lane) {
+template <int MODEL, bool REF = false>
+__device__ CLW_FN void cl_step_begin(const LoopArgs &L, int b, int lane, const RefArgs *rf = nullptr) {
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int s = L.stepno[b];
     if (lane == 0) L.t_begin[b] = wall_clock64();
@@ -749,7 +752,7 @@ __device__ CLW_FN void cl_step_begin(const LoopArgs &L, int b, int lane) {
     if (lane == 0) { L.call_ids[b] += 1.0; L.sa.scp_success[b] = 0; L.sa.scp_iters[b] = 0; }
     wla::wsync_mem();
     CLSTAMP(4);
-    lin_wave<MODEL>(L.lin, L.ba, b, lane);
+    lin_wave<MODEL, REF>(L.lin, L.ba, b, lane, rf, s);      // (REF: the window of the instance's OWN step count)
     CLSTAMP(5);
     if (lane < NX) L.cl.x0arg[(size_t)b * NX + lane] = L.cl.Xn[(size_t)b * (L.cl.N + 1) * NX + lane] - L.cl.xmeas[(size_t)b * NX + lane];
     wla::wsync_mem();
@@ -840,6 +843,43 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(LoopA
     if (lane == 0) { const unsigned long long te_ = wall_clock64(); atomicAdd(L.busy + 13, te_ - tw0_); atomicMax(L.busy + 15, te_); atomicAdd(L.busy + 1, 1ULL); }
 #endif
 }
+// The same loop for a handle with a reference (slsqp_cl_set_reference): the only difference is the tracked linear cost of cl_step_begin.  A kernel of
+// its own, so that k_cl_loop keeps its arguments and its code object (profiles/r07/resource_usage.txt); keep the two bodies in step --
+// tests/test_gpu_reference.py holds this one to the step-by-step loop bit for bit.  (No CL_LOOP_STAMP instrumentation here.)
+template <int MODEL>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_ref(LoopArgs L, RefArgs rf) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    int lane = threadIdx.x;
+    extern __shared__ double sm[];
+    int b = -1;
+#pragma unroll 1
+    for (;;) {
+        asm volatile("" : "+v"(lane));
+        if (b < 0) {
+            b = clq_pop(L.Q, lane);
+            if (b < 0) break;
+            if (L.fence & 1) __threadfence();      // acquire: what the wave that ran this instance's previous step wrote (possibly through another XCD's L2)
+        }
+        cl_step_begin<MODEL, true>(L, b, lane, &rf);
+        b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
+        asm volatile("" : "+v"(lane));
+        rti_chain_dev<NX, NU>(L.c, b, lane, sm);
+        wla::wsync_mem();
+        asm volatile("" : "+v"(lane));
+        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL>(L, b, lane));
+        b = __builtin_amdgcn_readfirstlane(b);
+        if (!next) { b = -1; continue; }
+        // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
+        // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
+        // waves are shared fairly among the instances that are level
+        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
+        if (behind && L.keep_laggards) continue;
+        if (L.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
+        clq_push(L.Q, b, lane);
+        b = -1;
+    }
+}
 
 // ---- the persistent loop for any SCP setting of slsqp_cl_step (slsqp_cl_run_scp) -------------------------------------------------------
 // One queue item is still one whole MPC step of one instance, but the step is the general one: max_it SCP iterations (SCP_SLS.solve,
@@ -872,11 +912,11 @@ __device__ CLW_FN void cl_scp_step_begin(const LoopArgs &L, int b, int lane) {
     wla::wsync_mem();
 }
 // start of SCP iteration ii: linearisation (instances still iterating), x0 pin, call id, solve start
-template <int MODEL>
-__device__ CLW_FN void cl_scp_iter_begin(const LoopArgs &L, int b, int lane, int ii) {
+template <int MODEL, bool REF = false>
+__device__ CLW_FN void cl_scp_iter_begin(const LoopArgs &L, int b, int lane, int ii, const RefArgs *rf = nullptr) {
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int act = __builtin_amdgcn_readfirstlane(L.scp_active[b]);
-    if (ii == 0 || act) lin_wave<MODEL>(L.lin, L.ba, b, lane);
+    if (ii == 0 || act) lin_wave<MODEL, REF>(L.lin, L.ba, b, lane, rf, REF ? L.stepno[b] : 0);      // (REF: every iteration of the step uses the window of the instance's own step count)
     if (lane < NX) L.cl.x0arg[(size_t)b * NX + lane] = L.cl.Xn[(size_t)b * (L.cl.N + 1) * NX + lane] - L.cl.xmeas[(size_t)b * NX + lane];
     if (lane == 0) L.call_ids[b] += 1.0;
     wla::wsync_mem();
@@ -990,6 +1030,50 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(S
         for (int ii = 0; ii < S.max_it; ii++) {
             asm volatile("" : "+v"(lane));
             cl_scp_iter_begin<MODEL>(L, b, lane, ii);
+            b = __builtin_amdgcn_readfirstlane(b);
+            asm volatile("" : "+v"(lane));
+            sls_solve_dev<NX, NU>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0);
+            asm volatile("" : "+v"(lane));
+            const int act = __builtin_amdgcn_readfirstlane(cl_scp_iter_end<MODEL>(L, b, lane, ii, S.converge));
+            b = __builtin_amdgcn_readfirstlane(b);
+            nsolves = ii + 1;
+            if (S.converge && !act) break;
+        }
+        asm volatile("" : "+v"(lane));
+        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL>(S, b, lane, nsolves));
+        b = __builtin_amdgcn_readfirstlane(b);
+        if (!next) { b = -1; continue; }
+        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
+        if (behind && L.keep_laggards) continue;
+        if (L.fence & 2) __threadfence();
+        clq_push(L.Q, b, lane);
+        b = -1;
+    }
+}
+// k_cl_loop_scp for a handle with a reference: as k_cl_loop_ref above, the tracked linear cost in cl_scp_iter_begin is the only difference
+template <int MODEL>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_ref(ScpLoopArgs S, RefArgs rf) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    const LoopArgs &L = S.L;
+    int lane = threadIdx.x;
+    extern __shared__ double sm[];
+    int b = -1;
+#pragma unroll 1
+    for (;;) {
+        asm volatile("" : "+v"(lane));
+        if (b < 0) {
+            b = clq_pop(L.Q, lane);
+            if (b < 0) break;
+            if (L.fence & 1) __threadfence();
+        }
+        cl_scp_step_begin<MODEL>(L, b, lane);
+        b = __builtin_amdgcn_readfirstlane(b);
+        int nsolves = 0;
+#pragma unroll 1
+        for (int ii = 0; ii < S.max_it; ii++) {
+            asm volatile("" : "+v"(lane));
+            cl_scp_iter_begin<MODEL, true>(L, b, lane, ii, &rf);
             b = __builtin_amdgcn_readfirstlane(b);
             asm volatile("" : "+v"(lane));
             sls_solve_dev<NX, NU>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0);
@@ -1565,6 +1649,39 @@ extern "C" int slsqp_set_solve_waves(slsqp_handle *h, int waves) {
 }
 extern "C" int slsqp_get_solve_waves(slsqp_handle *h) { return h->solve_waves; }
 
+// Reference of the tracked cost: validated and packed on the host into rows [x_ref(t); u_ref(t)], then one upload; the previous reference stays in
+// force until the new one is complete.
+extern "C" int slsqp_cl_set_reference(slsqp_handle *h, const double *Xref, const double *Uref, int T, int per_instance, int loc) {
+    hipSetDevice(h->dev);
+    if (per_instance != 0 && per_instance != 1) return fail("slsqp_cl_set_reference: per_instance must be 0 (one reference for the batch) or 1 (Xref (B,T,nx), Uref (B,T,nu))");
+    if (T < 0) return fail("slsqp_cl_set_reference: T must be >= 1 (or 0 with Xref = NULL to clear the reference)");
+    if (T == 0 && Xref) return fail("slsqp_cl_set_reference: T = 0 clears the reference and takes Xref = NULL; a reference has T >= 1 rows");
+    if (T > 0 && !Xref) return fail("slsqp_cl_set_reference: Xref is NULL with T > 0 (T = 0 clears the reference)");
+    if (loc != SLSQP_HOST && loc != SLSQP_DEVICE) return fail("slsqp_cl_set_reference: loc must be SLSQP_HOST or SLSQP_DEVICE");
+    HIPCHK(hipStreamSynchronize(h->st));      // no launch may still read the buffer that is replaced
+    if (T == 0) {
+        if (h->ref_Y) hipFree(h->ref_Y);
+        h->ref_Y = nullptr; h->ref_T = 0; h->ref_stride = 0;
+        return 0;
+    }
+    const size_t nx = h->d.nx, nu = h->d.nu, nz = nx + nu, rows = (size_t)(per_instance ? h->B : 1) * T;
+    std::vector<double> X(rows * nx), U(rows * nu, 0.0), Y(rows * nz);
+    const hipMemcpyKind kind = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
+    HIPCHK(hipMemcpy(X.data(), Xref, sizeof(double) * X.size(), kind));
+    if (Uref) HIPCHK(hipMemcpy(U.data(), Uref, sizeof(double) * U.size(), kind));
+    for (size_t r = 0; r < rows; r++) {
+        for (size_t i = 0; i < nx; i++) Y[r * nz + i] = X[r * nx + i];
+        for (size_t i = 0; i < nu; i++) Y[r * nz + nx + i] = U[r * nu + i];
+    }
+    for (double v : Y) if (!std::isfinite(v)) return fail("slsqp_cl_set_reference: the reference holds a NaN or infinite entry");
+    double *dY = nullptr;
+    HIPCHK(hipMalloc((void **)&dY, sizeof(double) * Y.size() + 64));
+    if (hipMemcpy(dY, Y.data(), sizeof(double) * Y.size(), hipMemcpyHostToDevice) != hipSuccess) { hipFree(dY); return fail("slsqp_cl_set_reference: upload failed"); }
+    if (h->ref_Y) hipFree(h->ref_Y);
+    h->ref_Y = dY; h->ref_T = T; h->ref_stride = per_instance ? (size_t)T * nz : 0;
+    return 0;
+}
+
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
     auto it = h->named.find(name);
@@ -1635,7 +1752,8 @@ extern "C" int slsqp_set_E(slsqp_handle *h, const double *E, int loc) {
     return put_E(h, E, loc);
 }
 
-static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int loc, const int *run) {
+// step / stepno: the MPC step whose window of the reference forms q (a handle with a reference only): `step` for every instance, or stepno[b]
+static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int loc, const int *run, int step, const int *stepno = nullptr) {
     hipSetDevice(h->dev);
     if (h->model_id < 0 || !h->have_costs || !h->have_cons) return fail("set_model, set_costs and set_constraints must be called first");
     const slsqp_dims &d = h->d;
@@ -1654,13 +1772,16 @@ static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int
     const int gval = (int)((B * d.N + blk - 1) / blk);
     if (h->model_id == 0) {
         hipLaunchKernelGGL((k_lin_val<0>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<0>), dim3(grid), dim3(blk), 0, h->st, a);
-        hipLaunchKernelGGL((k_lin_vec<4, 1>), dim3(grid), dim3(256), 0, h->st, a);
+        if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<4, 1>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
+        else hipLaunchKernelGGL((k_lin_vec<4, 1>), dim3(grid), dim3(256), 0, h->st, a);
     } else if (h->model_id == 1) {
         hipLaunchKernelGGL((k_lin_val<1>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<1>), dim3(grid), dim3(blk), 0, h->st, a);
-        hipLaunchKernelGGL((k_lin_vec<13, 4>), dim3(grid), dim3(256), 0, h->st, a);
+        if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<13, 4>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
+        else hipLaunchKernelGGL((k_lin_vec<13, 4>), dim3(grid), dim3(256), 0, h->st, a);
     } else {
         hipLaunchKernelGGL((k_lin_val<2>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<2>), dim3(grid), dim3(blk), 0, h->st, a);
-        hipLaunchKernelGGL((k_lin_vec<17, 4>), dim3(grid), dim3(256), 0, h->st, a);
+        if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<17, 4>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
+        else hipLaunchKernelGGL((k_lin_vec<17, 4>), dim3(grid), dim3(256), 0, h->st, a);
     }
     BoundsArgs ba{h->B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, run};
     hipLaunchKernelGGL(k_set_bounds, dim3(1024), dim3(256), 0, h->st, ba);
@@ -1669,7 +1790,7 @@ static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int
     h->have_dyn = true;
     return 0;
 }
-extern "C" int slsqp_linearize(slsqp_handle *h, const double *X, const double *U, int loc) { return linearize_impl(h, X, U, loc, nullptr); }
+extern "C" int slsqp_linearize(slsqp_handle *h, const double *X, const double *U, int loc) { return linearize_impl(h, X, U, loc, nullptr, h->cl_steps); }
 
 
 // ---- closed-loop driver around the path (SCP_SLS.solve + reset_warm_start + plant) -------------------------
@@ -1729,14 +1850,20 @@ extern "C" int slsqp_nominal_solve(slsqp_handle *h, int max_qp, double tol, doub
     na.n_active = h->counter + 2; na.rho = rho; na.tol = tol; na.w_max = 1e8;
     auto eval = [&](int mode) {
         na.mode = mode;
-        if (h->model_id == 0) hipLaunchKernelGGL((k_nom_eval<0>), dim3(B), dim3(128), 0, h->st, na);
+        if (h->ref_T > 0) {      // the tracked objective, window of step 0
+            const RefArgs rf = ref_args(h);
+            if (h->model_id == 0) hipLaunchKernelGGL((k_nom_eval_ref<0>), dim3(B), dim3(128), 0, h->st, na, rf);
+            else if (h->model_id == 1) hipLaunchKernelGGL((k_nom_eval_ref<1>), dim3(B), dim3(128), 0, h->st, na, rf);
+            else hipLaunchKernelGGL((k_nom_eval_ref<2>), dim3(B), dim3(128), 0, h->st, na, rf);
+        }
+        else if (h->model_id == 0) hipLaunchKernelGGL((k_nom_eval<0>), dim3(B), dim3(128), 0, h->st, na);
         else if (h->model_id == 1) hipLaunchKernelGGL((k_nom_eval<1>), dim3(B), dim3(128), 0, h->st, na);
         else hipLaunchKernelGGL((k_nom_eval<2>), dim3(B), dim3(128), 0, h->st, na);
     };
     eval(0);
     double tq = 0;
     for (int it = 0; it < max_qp; it++) {
-        if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, h->nom_need_lin)) return -1;     // accepted instances only; the others re-solve
+        if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, h->nom_need_lin, 0)) return -1;     // accepted instances only; the others re-solve
         NomBoundsArgs ba{B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->nom_st, active, h->ubg, h->lbg, 1e-10};
         hipLaunchKernelGGL(k_nom_bounds, dim3(1024), dim3(256), 0, h->st, ba);
         hipLaunchKernelGGL(k_nom_x0, dim3((B * d.nx + 255) / 256), dim3(256), 0, h->st, B, d.N, d.nx, h->Xn, h->xmeas, h->nom_st, h->x0val);
@@ -1826,7 +1953,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     hipLaunchKernelGGL(k_fill_int, dim3(gbi), dim3(256), 0, h->st, h->scp_iters, 0, B);
     {
         const int tl_j = tl_begin(h, 3);
-        if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, nullptr)) return -1;
+        if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, nullptr, h->cl_steps)) return -1;
         tl_end(h, tl_j);
     }
     for (int ii = 0; ii < max_it; ii++) {
@@ -1848,7 +1975,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
             if (nact == 0) break;
         }
         const int tl_j = tl_begin(h, 3);
-        if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, h->scp_active)) return -1;   // update_jacobian for the next iteration (:138)
+        if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, h->scp_active, h->cl_steps)) return -1;   // update_jacobian for the next iteration (:138)
         tl_end(h, tl_j);
     }
     if (h->log_steps > 0 && h->cl_steps < h->log_steps) {
@@ -1887,7 +2014,12 @@ static int launch_loop_t(slsqp_handle *h, LoopArgs &L, const ScpLoopArgs *S = nu
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     hipEventRecord(h->ev[8], h->st);
-    if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL>), dim3(grid), dim3(64), lds, h->st, *S);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
+    if (h->ref_T > 0) {      // tracked cost: the kernels that take the reference
+        const RefArgs rf = ref_args(h);
+        if (S) hipLaunchKernelGGL((k_cl_loop_scp_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, *S, rf);
+        else hipLaunchKernelGGL((k_cl_loop_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, L, rf);
+    }
+    else if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL>), dim3(grid), dim3(64), lds, h->st, *S);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
     else hipLaunchKernelGGL((k_cl_loop<MODEL>), dim3(grid), dim3(64), lds, h->st, L);
     hipEventRecord(h->ev[9], h->st);
     if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
@@ -2060,7 +2192,7 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         h->have_dyn = false;
         {
             const int tl_j = tl_begin(h, 3);
-            if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, h->cl_begin)) return -1;
+            if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, h->cl_begin, 0, h->cl_stepno)) return -1;
             tl_end(h, tl_j);
         }
         hipLaunchKernelGGL(k_cl_x0arg, dim3(64), dim3(256), 0, h->st, a, h->cl_begin);

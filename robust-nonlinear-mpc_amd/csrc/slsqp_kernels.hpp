@@ -2253,19 +2253,32 @@ __global__ __launch_bounds__(128) void k_lin_tan(LinArgs a) {
         lin_tan_item<MODEL>(a, b, k, dir);
     }
 }
-template <int NX, int NU>
-__device__ __forceinline__ void lin_vec_item(const LinArgs &a, int b, int e) {
+// Reference trajectory of the tracked cost (slsqp_cl_set_reference): rows y_ref(t) = [x_ref(t); u_ref(t)] of absolute MPC time t, packed (T, NX+NU),
+// shared by the batch (stride 0) or one block per instance (stride T (NX+NU)).  Stage k of the horizon of MPC step s reads row min(s + k, T - 1): the
+// last row is held.  Only the kernels launched for a handle WITH a reference take this argument (the REF = true instantiations below); every
+// other kernel keeps its arguments and its code.
+struct RefArgs { const double *Y; int T; size_t stride; };
+template <int NZ>
+__device__ __forceinline__ double ref_entry(const RefArgs &r, int b, int s, int k, int i) {
+    return r.Y[(size_t)b * r.stride + (size_t)min(s + k, r.T - 1) * NZ + i];
+}
+// g_k, g_N and q of element e of instance b.  REF: q = 2 H (y_nom - y_ref) with the window of MPC step s (formed as a difference first: a zero
+// reference gives the bits of 2 H y_nom)
+template <int NX, int NU, bool REF = false>
+__device__ __forceinline__ void lin_vec_item(const LinArgs &a, int b, int e, const RefArgs *rf = nullptr, int s = 0) {
     constexpr int NZ = NX + NU, NI = 2 * NZ, NIF = 2 * NX;
     const int n = NZ * a.N + NX, k = e / NZ, i = e % NZ;
     const double z = (i < NX) ? a.X[((size_t)b * (a.N + 1) + k) * NX + i] : a.U[((size_t)b * a.N + k) * NU + (i - NX)];
+    double zq = z;
+    if constexpr (REF) zq = z - ref_entry<NZ>(*rf, b, s, k, i);
     if (k < a.N) {
         double *g = a.g + ((size_t)b * a.N + k) * NI;
         g[i] = a.g_raw[i] - z; g[NZ + i] = a.g_raw[NZ + i] + z;
-        a.q[(size_t)b * n + e] = 2.0 * (i < NX ? a.cst.Qd[i] : a.cst.Rd[i - NX]) * z;
+        a.q[(size_t)b * n + e] = 2.0 * (i < NX ? a.cst.Qd[i] : a.cst.Rd[i - NX]) * zq;
     } else {
         double *g = a.gN + (size_t)b * NIF;
         g[i] = a.gf_raw[i] - z; g[NX + i] = a.gf_raw[NX + i] + z;
-        a.q[(size_t)b * n + e] = 2.0 * a.cst.Qfd[i] * z;
+        a.q[(size_t)b * n + e] = 2.0 * a.cst.Qfd[i] * zq;
     }
 }
 template <int NX, int NU>
@@ -2279,15 +2292,27 @@ __global__ void k_lin_vec(LinArgs a) {
         lin_vec_item<NX, NU>(a, b, e);
     }
 }
+// the same for a handle with a reference: every instance at MPC step `step`, or at its own stepno[b] (the rounds of slsqp_cl_run)
+template <int NX, int NU>
+__global__ void k_lin_vec_ref(LinArgs a, RefArgs rf, int step, const int *stepno) {
+    constexpr int NZ = NX + NU;
+    const int n = NZ * a.N + NX;
+    const size_t tot = (size_t)a.B * n;
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < tot; t += (size_t)gridDim.x * blockDim.x) {
+        const int e = t % n, b = t / n;
+        if (a.run && !a.run[b]) continue;
+        lin_vec_item<NX, NU, true>(a, b, e, &rf, stepno ? stepno[b] : step);
+    }
+}
 // the whole linearisation of ONE instance by one wave (the persistent closed-loop kernel k_cl_loop): same items, same arithmetic
-template <int MODEL>
-__device__ CLW_FN void lin_wave(const LinArgs &a, const BoundsArgs &ba, int b, int lane) {
+template <int MODEL, bool REF = false>
+__device__ CLW_FN void lin_wave(const LinArgs &a, const BoundsArgs &ba, int b, int lane, const RefArgs *rf = nullptr, int s = 0) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU, NZ = NX + NU;
     const int n = NZ * a.N + NX;
     if (lane < a.N) lin_val_item<MODEL>(a, b, lane);
     wla::wsync_mem();
     for (int t = lane; t < a.N * NZ; t += 64) lin_tan_item<MODEL>(a, b, t / NZ, t % NZ);
-    for (int e = lane; e < n; e += 64) lin_vec_item<NX, NU>(a, b, e);
+    for (int e = lane; e < n; e += 64) lin_vec_item<NX, NU, REF>(a, b, e, rf, s);
     wla::wsync_mem();
     const int mb = ba.N * (ba.NX + ba.NI) + ba.NIF;
     for (int r = lane; r < mb; r += 64) set_bounds_row(ba, b, r);
@@ -2560,6 +2585,84 @@ __global__ __launch_bounds__(128) void k_nom_eval(NomArgs a) {
         const double hw = (k < N) ? (i < NX ? a.cst.Qd[i] : a.cst.Rd[i - NX]) : a.cst.Qfd[i];
         const double hi = (k < N) ? a.g_raw[i] : a.gf_raw[i], lo = (k < N) ? -a.g_raw[NZ + i] : -a.gf_raw[NX + i];
         f += hw * z * z;
+        if (e >= NX) v += fmax(z - hi, 0.0) + fmax(lo - z, 0.0);   // x_0 is data (pinned to x_meas), its box is not the solver's to fix
+        dm = fmax(dm, fabs(dv));
+    }
+    for (int k = t; k < N; k += 128) {
+        double x[NX], u[NU], xp[NX];
+        for (int i = 0; i < NX; i++) x[i] = X[k * NX + i] + (trial ? d[k * NZ + i] : 0.0);
+        for (int i = 0; i < NU; i++) u[i] = U[k * NU + i] + (trial ? d[k * NZ + NX + i] : 0.0);
+        dyn::ddyn<MODEL, double>(x, u, xp);
+        for (int i = 0; i < NX; i++) c += fabs(xp[i] - (X[(k + 1) * NX + i] + (trial ? d[(k + 1) * NZ + i] : 0.0)));
+    }
+    if (t < NX) c += fabs(X[t] + (trial ? d[t] : 0.0) - a.xmeas[(size_t)b * NX + t]);
+    f = block_sum128(f, red); v = block_sum128(v, red); c = block_sum128(c, red); dm = block_max128(dm, red);
+    if (t == 0) {
+        int dec = 0;   // 0 retry the QP (same linearisation), 1 step accepted, 2 converged, 3 failed
+        double w = S[0], kap = S[1], kap0 = S[2];
+        const double f0 = S[3], c0 = S[4], v0 = S[5];
+        if (!trial) {
+            S[3] = f; S[4] = c; S[5] = v; S[1] = (v > 1e-7 || c > 1e-6) ? kap0 : 0.0;
+            dec = -1;
+        } else {
+            const int qs = a.qp_status[b];
+            const double phi0 = f0 + a.rho * (c0 + v0);
+            double r = 0.0;
+            if (!(qs == 0 || qs == 4)) {       // QP infeasible at this tau: ask for less
+                if (kap < 0.995) { kap = 1.0 - 0.3 * (1.0 - kap); dec = 0; } else dec = 3;
+            } else {
+                const double pred = phi0 - (f + a.rho * kap * (v0 + c0));     // linearised model: violation shrinks to kappa * (v0 + c0)
+                const double act = phi0 - (f + a.rho * (c + v));
+                r = pred > 0.0 ? act / pred : -1.0;
+                if (pred <= 1e-12 * fmax(1.0, fabs(phi0)) || dm < a.tol) dec = (v0 < 1e-7 && c0 < 1e-7)   /* l1 sums; the QP's own 1e-10 pads on every bound add up to ~1e-9 */ ? 2 : 1;
+                else if (r < 0.1) { w *= 4.0; kap = 1.0 - (1.0 - kap) / 3.0; dec = (w > a.w_max) ? 3 : 0; }
+                else { dec = 1; kap0 = kap; if (r > 0.7) { w = fmax(w / 3.0, 1e-6); kap0 = kap > 0.01 ? kap / 3.0 : 0.0; } }
+            }
+            S[6] = r; S[7] = dm;
+            if (dec == 1 || dec == 2) {
+                S[3] = f; S[4] = c; S[5] = v;
+                kap = (v > 1e-7 || c > 1e-6) ? kap0 : 0.0;
+                a.iters[b] += 1;
+            }
+            S[0] = w; S[1] = kap; S[2] = kap0;
+            a.need_lin[b] = (dec == 1) ? 1 : 0;
+            if (dec == 2) { a.status[b] = 0; a.active[b] = 0; }
+            else if (dec == 3) { a.status[b] = 2; a.active[b] = 0; }
+            else atomicAdd(a.n_active, 1);
+        }
+        dec_s = dec;
+    }
+    __syncthreads();
+    if (dec_s == 1 || dec_s == 2) {
+        for (int e = t; e < n; e += 128) {
+            const int k = e / NZ, i = e % NZ;
+            if (i < NX) X[k * NX + i] += d[e]; else U[k * NU + (i - NX)] += d[e];
+        }
+    }
+}
+// k_nom_eval for a handle with a reference: the objective is the tracked cost sum hw (z - y_ref)^2 with the window of MPC step 0 (the initialiser runs
+// before the first step); everything else as above.  A kernel of its own: k_nom_eval keeps its arguments and its code.
+template <int MODEL>
+__global__ __launch_bounds__(128) void k_nom_eval_ref(NomArgs a, RefArgs rf) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU, NZ = NX + NU;
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (!a.active[b]) return;
+    __shared__ double red[128];
+    __shared__ int dec_s;
+    const int N = a.N, n = NZ * N + NX;
+    double *X = a.Xn + (size_t)b * (N + 1) * NX, *U = a.Un + (size_t)b * N * NU;
+    const double *d = a.primal + (size_t)b * n;
+    double *S = a.st + (size_t)b * 12;
+    const bool trial = a.mode == 1;
+    double f = 0.0, v = 0.0, dm = 0.0, c = 0.0;
+    for (int e = t; e < n; e += 128) {
+        const int k = e / NZ, i = e % NZ;
+        const double z0 = (i < NX) ? X[k * NX + i] : U[k * NU + (i - NX)];
+        const double dv = trial ? d[e] : 0.0, z = z0 + dv;
+        const double hw = (k < N) ? (i < NX ? a.cst.Qd[i] : a.cst.Rd[i - NX]) : a.cst.Qfd[i];
+        const double hi = (k < N) ? a.g_raw[i] : a.gf_raw[i], lo = (k < N) ? -a.g_raw[NZ + i] : -a.gf_raw[NX + i];
+        const double zt = z - ref_entry<NZ>(rf, b, 0, k, i);
+        f += hw * zt * zt;
         if (e >= NX) v += fmax(z - hi, 0.0) + fmax(lo - z, 0.0);   // x_0 is data (pinned to x_meas), its box is not the solver's to fix
         dm = fmax(dm, fabs(dv));
     }

@@ -182,6 +182,24 @@ class BatchedFastSLS:
         assert X.shape == (self.B, self.N + 1, self.m.nx) and U.shape == (self.B, self.N, self.m.nu)
         L.check(self.lib.slsqp_linearize(self.h, _ptr(X), _ptr(U), L.HOST))
 
+    def set_reference(self, Xref, Uref=None):
+        """Reference trajectory of the closed-loop entry points (slsqp_cl_set_reference): Xref (T,nx), Uref (T,nu) shared by the batch, or
+        (B,T,nx), (B,T,nu) per instance; row t belongs to MPC time t counted from the reset that starts a run, the last row is held (T = 1: a
+        setpoint).  Uref None: zero input reference.  Xref None clears the reference (cost around the origin, the default).  Kept by the handle
+        until replaced; linearize(), the closed-loop steps / runs and the nominal initialiser then form q = 2 H (y_nom - y_ref)."""
+        if Xref is None:
+            if Uref is not None:
+                raise ValueError("set_reference: Uref without Xref")
+            L.check(self.lib.slsqp_cl_set_reference(self.h, None, None, 0, 0, L.HOST))
+            return
+        X = _c(Xref)
+        if X.ndim not in (2, 3) or X.shape[-1] != self.m.nx or X.shape[-2] < 1 or (X.ndim == 3 and X.shape[0] != self.B):
+            raise ValueError(f"set_reference: Xref must be (T,{self.m.nx}) or ({self.B},T,{self.m.nx}) with T >= 1, got {X.shape}")
+        U = None if Uref is None else _c(Uref)
+        if U is not None and U.shape != X.shape[:-1] + (self.m.nu,):
+            raise ValueError(f"set_reference: Uref must be {X.shape[:-1] + (self.m.nu,)}, got {U.shape}")
+        L.check(self.lib.slsqp_cl_set_reference(self.h, _ptr(X), _ptr(U), int(X.shape[-2]), int(X.ndim == 3), L.HOST))
+
     def update_linear_cost(self, q):
         q = _c(q)
         assert q.shape == (self.B, self.n)

@@ -45,10 +45,11 @@ def can_run_persistent(rti, rti_steps, opts=None, environ=os.environ):
 PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
 
 
-def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1):
+def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1,
+               reference=None):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
-    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves)
+    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference)
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
     rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
     want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
@@ -63,7 +64,7 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 
 
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
-                    budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1):
+                    budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
@@ -72,6 +73,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     x0_box_tol: tolerance of the measured state against its own stage-0 box, for every slice and shard alike (ClosedLoopMPC; 0 = strict); the result
     holds `x0_violation` (seeds, steps, 2), the largest such violation of each step's first / last QP, whatever the tolerance.
     solve_waves: waves per instance of the QP solves (ClosedLoopMPC; above 1 the loops run step by step: for a handful of seeds).
+    reference: what every seed tracks (ClosedLoopMPC.set_reference: "neutral", Xref or (Xref, Uref)); arrays with a leading axis of len(seeds)
+    ((S,T,nx), (S,T,nu)) are per seed and are cut with the seeds into shards and slices.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -81,6 +84,16 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     mine = seeds[lo:hi]
     B = len(mine)
     K = max(1, min(int(slices), B))
+
+    def ref_rows(a, b):      # the rows of a per-seed reference for the seeds [a, b) of this rank's shard
+        if reference is None or isinstance(reference, str):
+            return reference
+        Xr, Ur = reference if isinstance(reference, tuple) else (reference, None)
+        if np.ndim(Xr) != 3:
+            return reference
+        if len(Xr) != S:
+            raise ValueError(f"run_monte_carlo: a per-seed reference needs {S} leading rows, got {len(Xr)}")
+        return (np.asarray(Xr)[lo + a:lo + b], None if Ur is None else np.asarray(Ur)[lo + a:lo + b])
     cuts = [(B * k // K, B * (k + 1) // K) for k in range(K)]
     parts, err = [None] * K, []
 
@@ -91,6 +104,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["x0_box_tol"] = x0_box_tol
             if solve_waves != 1:
                 kw["solve_waves"] = solve_waves
+            if reference is not None:
+                kw["reference"] = ref_rows(*cuts[k])
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:
             err.append(e)
