@@ -8,6 +8,7 @@ fast_sls_rti_steps, step counts and (rocket) seed-s disturbance streams; B indep
     python examples/closed_loop.py --model rocket    [--runs 256] [--x0-scale 0.3]
     ... --persistent 1                                                     # the same loop as ONE persistent launch (same bits)
     ... --reference neutral | figure8                                      # track the plant's neutral point / a figure of eight in x, y
+    ... --plant-scale mass=1.15 --plant-spread 10                          # a true plant that differs from the controller's model (see --help)
 
 The first nominal comes from the GPU initialiser (slsqp_nominal_solve) in place of IPOPT."""
 import argparse
@@ -18,7 +19,8 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from robust_nonlinear_mpc_amd import ClosedLoopMPC, disturbance_stream, get_model  # noqa: E402
+from robust_nonlinear_mpc_amd import ClosedLoopMPC, disturbance_stream, get_model, plant_param_names  # noqa: E402
+from robust_nonlinear_mpc_amd._plant_cli import parse_plant_scale, sample_plant_params  # noqa: E402
 
 
 def main():
@@ -37,9 +39,18 @@ def main():
     ap.add_argument("--reference", default="none", choices=["none", "neutral", "figure8"],
                     help="what the loop tracks: none = the cost around the origin of the raw state (the scripts); neutral = the setpoint (x_ref, u_ref); "
                     "figure8 = x = 0.3 sin 2t, y = 0.3 (1 - cos 2t), z constant, the rest the neutral point (plants with a position: quadrotor, rocket)")
+    ap.add_argument("--plant-scale", action="append", default=[], metavar="NAME=FACTOR",
+                    help="the TRUE plant's parameter NAME is FACTOR x the controller's value, for every run (repeatable; names: plant_param_names(model))")
+    ap.add_argument("--plant-spread", type=float, default=None, metavar="PCT",
+                    help="every parameter of the true plant of run s uniform within +-PCT %% of its default, drawn from a generator seeded with s (gimbal lengths excluded)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
+    try:
+        scale = parse_plant_scale(a.plant_scale)
+        P = sample_plant_params(m, np.arange(a.runs), a.plant_spread or 0.0, scale) if (scale or a.plant_spread is not None) else None
+    except ValueError as e:
+        ap.error(f"{e} (parameters of {a.model}: {', '.join(plant_param_names(m))})")
     N = a.N or 15                                                            # the scripts' default horizon (main_*_robust_closed_loop.py: N = 15)
     steps = a.steps or m.extra.get("sim_steps", 30)
     B = a.runs
@@ -67,7 +78,7 @@ def main():
         Xref = np.tile(np.asarray(m.x_ref, dtype=float), (T, 1))
         Xref[:, 0], Xref[:, 1] = 0.3 * np.sin(2.0 * t), 0.3 * (1.0 - np.cos(2.0 * t))
         Uref = np.tile(np.asarray(m.u_ref, dtype=float), (T, 1))
-    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref))
+    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P)
     t0 = time.perf_counter()
     run = cl.run_decoupled if a.persistent else cl.run_on_device
     out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1)
@@ -76,6 +87,10 @@ def main():
     dist1 = np.linalg.norm(out["state_trajectory"][:, :, -1] - m.x_ref, axis=1).mean()
     print(f"{a.model}: {B} runs x {steps} MPC steps (N={N}, rti={cl.rti}) in {dt:.2f} s; nominal NLP solved for {np.mean(cl.nlp_status == 0):.3f}; "
           f"MPC steps solved {out['success'].mean():.3f}; mean |x - x_ref| {dist0:.3f} -> {dist1:.3f}; QP {out['t_qp'].sum():.0f} ms, sweeps {out['t_riccati'].sum():.0f} ms")
+    if P is not None:
+        du = out["disturbance_used"]
+        print(f"plant mismatch: steps with disturbance_used > 1 (model error + noise outside the box the tubes assume): {np.mean(du > 1.0):.3f}; "
+              f"largest {np.nanmax(du):.2f}; largest |model error| {np.abs(out['model_error']).max():.3e}")
     if Xref is not None:
         rows = np.minimum(np.arange(steps), len(Xref) - 1)
         err = np.linalg.norm(out["state_trajectory"].transpose(0, 2, 1) - Xref[rows][None], axis=2).mean(axis=0)      # (steps,)

@@ -8,6 +8,9 @@ The reference starts from an IPOPT nominal trajectory (SCP_SLS.solve_nominal_tra
 nominal NLP on the GPU (slsqp_nominal_solve, trust-region SCP from a hover roll-out) and `--init rollout` uses the bare roll-out.
 `--x0-scale s` starts from x_ref + s (x0_script - x_ref); the script's own x0 (s = 1, the default) needs the initial-state continuation
 (`--continuation 2`, default).
+`--plant-scale NAME=FACTOR` (repeatable) and `--plant-spread PCT` make the TRUE plant differ from the controller's model: a rocket that is heavier,
+a servo that is slower, every parameter of seed s uniform within +-PCT % of its default.  The run then reports how often the model error plus the
+noise left the disturbance box the tubes were designed for (`disturbance_used` > 1) and the constraint violations of the measured states.
 """
 import argparse
 import os
@@ -17,7 +20,8 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from robust_nonlinear_mpc_amd import get_model, run_monte_carlo  # noqa: E402
+from robust_nonlinear_mpc_amd import get_model, plant_param_names, run_monte_carlo  # noqa: E402
+from robust_nonlinear_mpc_amd._plant_cli import parse_plant_scale, sample_plant_params  # noqa: E402
 
 
 def main():
@@ -32,13 +36,22 @@ def main():
     ap.add_argument("--round-budget-ms", type=float, default=None, help="run the loop through slsqp_cl_run: instances advance independently, rounds of this length")
     ap.add_argument("--x0-box-tol", type=float, default=0.0, help="how far the measured state may lie outside its own stage-0 box before a step is refused "
                     "(0: strict; 1e-3: what the reference's OSQP settings let through; inf: never)")
+    ap.add_argument("--plant-scale", action="append", default=[], metavar="NAME=FACTOR",
+                    help="the TRUE plant's parameter NAME is FACTOR x the controller's value, for every seed (repeatable), e.g. mass=1.15")
+    ap.add_argument("--plant-spread", type=float, default=None, metavar="PCT",
+                    help="every parameter of the true plant of seed s uniform within +-PCT %% of its default, drawn from a generator seeded with s (gimbal lengths excluded)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model("rocket")
+    try:
+        scale = parse_plant_scale(a.plant_scale)
+        P = sample_plant_params(m, np.arange(a.seeds), a.plant_spread or 0.0, scale) if (scale or a.plant_spread is not None) else None
+    except ValueError as e:
+        ap.error(f"{e} (parameters: {', '.join(plant_param_names(m))})")
     x0 = m.x_ref + a.x0_scale * (m.extra["x0"] - m.x_ref)
     t0 = time.perf_counter()
     r = run_monte_carlo(m, a.N, np.arange(a.seeds), a.steps, x0, solve_nominal=(a.init == "sqp"), slices=a.slices, continuation=a.continuation,
-                        budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol)
+                        budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P)
     dt = time.perf_counter() - t0
     ok = r["success"]
     if "nlp_status" in r:
@@ -47,6 +60,13 @@ def main():
     print(f"{a.seeds} seeds x {a.steps} MPC steps (N={a.N}) in {dt:.2f} s; solved steps: {ok.mean():.3f}; "
           f"final |pos| mean {np.linalg.norm(r['state_trajectory'][:, :3, -1], axis=1).mean():.3f} "
           f"(start {np.linalg.norm(x0[:3]):.3f}); largest stage-0 violation of the measured state {r['x0_violation'].max():.2e}; QP {r['t_qp'].sum():.1f} ms, Riccati sweeps {r['t_riccati'].sum():.1f} ms")
+    if P is not None:
+        X = r["state_trajectory"]      # (seeds, nx, steps): the measured states
+        viol = np.maximum(X - m.x_ub[None, :, None], m.x_lb[None, :, None] - X).max(axis=1)
+        print(f"measured states outside the state box: {np.mean(viol > 0):.4f} of the steps, largest violation {max(viol.max(), 0.0):.3e}")
+        du = r["disturbance_used"]
+        print(f"plant mismatch (spread {a.plant_spread or 0.0:g} %, scale {scale or {}}): steps with disturbance_used > 1: {np.mean(du > 1.0):.4f}; "
+              f"median {np.nanmedian(du):.2f}, largest {np.nanmax(du):.2f}")
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         from robust_nonlinear_mpc_amd import ClosedLoopMPC

@@ -187,6 +187,34 @@ int slsqp_get_solve_waves(slsqp_handle *h);
    cost).  Survives slsqp_cl_init (which only restarts the step count); may be replaced between runs.  slsqp_update_linear_cost, slsqp_solve and
    slsqp_qp_* bring their own q and are not affected. */
 int slsqp_cl_set_reference(slsqp_handle *h, const double *Xref, const double *Uref, int T, int per_instance, int loc);
+
+/* Plant parameters of the closed loop: a true plant that differs from the controller's model (a property of the handle, like the settings above;
+   slsqp_opts keeps its layout).  What a user of the reference does by editing `m.params` before the loop of expe/main_*_closed_loop.py -- except
+   that there the controller changes with the plant; here ONLY the plant step x_meas <- ddyn_p(x_meas, u0) + E w of slsqp_cl_step, slsqp_cl_run
+   (persistent and round-based) and slsqp_cl_run_scp uses the parameters.  The linearisation, the predicted last state of the shifted nominal and
+   the nominal initialiser keep the model's constants: controller != plant is the point.
+   Parameter vectors, in this order (quadrotor, rocket: the reference's dict order, dyn/quadrotor.py:32-40, dyn/rocket.py:25-39):
+       model 0 pendulum   4: m1, m2, l, g
+       model 1 quadrotor  7: m, g, l, Jx, Jy, Jz, kM
+       model 2 rocket    13: mass, gravity_constant, inertia_xx, inertia_yy, inertia_zz, thrust_cog_offset, thrust_magnitude_time_constant,
+                             servo_angle_time_constant, gimbal_a, gimbal_b, gimbal_c, gimbal_d, gimbal_e
+   (the rocket's thrust offset 11.3796 is a literal of the reference's ODE, not a parameter: a heavier rocket sags).
+   slsqp_plant_param_count: the length for a model id (-1: unknown id).  slsqp_plant_param_name: entry i's name (NULL outside the range).
+   slsqp_plant_param_defaults: the model's constants into out[0..count) (len >= count); returns the count, < 0 on error.
+   slsqp_cl_set_plant_params: P (np) shared by the batch (per_instance = 0) or (B,np) (per_instance = 1), host or device (`loc`), copied by the call;
+   np must be the count of the handle's model; np = 0 with P = NULL clears (the default: the plant is the model).  Survives slsqp_cl_init; may be
+   replaced between runs, not during one.  A row holding the defaults bit for bit takes the model's own step: its model_err is exactly 0 (the closed loop then has the bits of no parameters at
+   the tested sizes; at rocket B = 4096 rounding-level differences remain).
+   Errors (< 0, slsqp_last_error; the previous parameters stay in force): no slsqp_set_model yet, np not the model's count, a NaN or infinite entry, an
+   entry <= 0 among the masses, inertias, lengths, time constants, g and the gimbal lengths (everything but the quadrotor's kM), per_instance
+   outside {0, 1}.
+   Results (slsqp_get): "plant_params" (np) per instance (a shared row repeated; the defaults without parameters); "model_err" (nx):
+   ddyn_p(x,u0) - ddyn(x,u0) of the last plant step, before the noise is added (zeros without parameters); "log_model_error" (S,nx) with
+   slsqp_cl_log: the same for every MPC step, in the layout of log_state (zeros without parameters). */
+int slsqp_plant_param_count(int model_id);
+const char *slsqp_plant_param_name(int model_id, int i);
+int slsqp_plant_param_defaults(int model_id, double *out, int len);
+int slsqp_cl_set_plant_params(slsqp_handle *h, const double *P, int np, int per_instance, int loc);
 int slsqp_sync(slsqp_handle *h);
 
 /* ---- the step in front of the path: batched linearisation (SCP_SLS.update_jacobian, solver/SCP_SLS_jit.py:251-366) ---------

@@ -22,13 +22,14 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
         state never fails a step on its own (slsqp_set_x0_box_tol).
         solve_waves: 1, or 2 / 4 / 8 waves per instance for the QP solves (slsqp_set_solve_waves: for one plant or a handful); run_decoupled then
         takes the step-by-step loop, the persistent kernels being one wave per instance.
-        reference: see set_reference (None: the cost is around the origin of the raw state, as in the reference's scripts)."""
+        reference: see set_reference (None: the cost is around the origin of the raw state, as in the reference's scripts).
+        plant_params: see set_plant_params (None: the true plant is the controller's model)."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -44,6 +45,15 @@ class ClosedLoopMPC:
         self.steps_done = 0
         if reference is not None:
             self.set_reference(reference)
+        if plant_params is not None:
+            self.set_plant_params(plant_params)
+
+    def set_plant_params(self, plant_params):
+        """Physical parameters of the TRUE plant from the next step on: a dict {name: scalar or (B,)}, an array (np,) or (B,np)
+        (models.pack_plant_params), None: the plant is the controller's model again.  Only the plant step x+ = ddyn_p(x, u0) + E w uses them; the
+        linearisation, the warm-start shift and the nominal initialiser keep the model's constants.  Logged runs then hold `model_error`
+        (ddyn_p - ddyn of every plant step) and `disturbance_used`."""
+        self.f.set_plant_params(plant_params)
 
     def set_reference(self, reference, Uref=None):
         """What the closed loop tracks from the next reset() on: a tuple (Xref, Uref) or Xref, Uref -- arrays (T,nx), (T,nu) shared by the batch or
@@ -76,6 +86,7 @@ class ClosedLoopMPC:
         x_first = x_meas if K == 1 else _c(m.x_ref + (x_meas - m.x_ref) / K)
         L.check(f.lib.slsqp_cl_init(f.h, _ptr(x_first), _ptr(Xn), _ptr(Un), _ptr(ui), L.HOST))
         self.steps_done = 0
+        self._W_log = []      # the disturbance samples of the run's steps (disturbance_used)
         self.nlp_status = None
         if solve_nominal:
             L.check(f.lib.slsqp_nominal_solve(f.h, int(max_qp), float(tol), float(rho), C.byref(f.opts)))
@@ -93,6 +104,7 @@ class ClosedLoopMPC:
         wv = None if w is None else _c(w)
         L.check(f.lib.slsqp_cl_step(f.h, self.rti, _ptr(wv), L.HOST, C.byref(f.opts)))
         self.steps_done += 1
+        self._W_log.append(wv)
         if not fetch:
             return None
         m, N = self.m, self.N
@@ -125,7 +137,7 @@ class ClosedLoopMPC:
         lx = f.get("log_nominal_x", (steps, N + 1, m.nx)); lu = f.get("log_nominal_u", (steps, N, m.nu))
         lbx = f.get("log_backoff_x", (steps, N + 1, m.nx)); lbu = f.get("log_backoff_u", (steps, N, m.nu))
         u0 = f.get("log_u0", (steps, m.nu))
-        return dict(
+        out = dict(
             state_trajectory=f.get("log_state", (steps, m.nx)).transpose(0, 2, 1).copy(),
             input_trajectory=u0[:, :max(steps - 1, 0)].transpose(0, 2, 1).copy(),
             nominal_trajectory_x=lx.transpose(0, 3, 2, 1).copy(), nominal_trajectory_u=lu.transpose(0, 3, 2, 1).copy(),
@@ -135,6 +147,24 @@ class ClosedLoopMPC:
             primal_infeasibility=f.get("log_primal_infeasibility", (steps,)),
             x0_violation=f.get("log_x0_viol", (steps, 2)),
         )
+        if f.plant_params is not None:
+            me = f.get("log_model_error", (steps, m.nx))
+            out.update(model_error=me.transpose(0, 2, 1).copy(), disturbance_used=self._disturbance_used(me), plant_params=np.array(f.plant_params))
+        return out
+
+    def _disturbance_used(self, me):
+        """me (B,steps,nx): ddyn_p - ddyn of every plant step.  (steps,B): max_i |(E^-1 me)_i + w_i|, how much of the unit box the tubes assume the
+        mismatch and the noise sample of the step used together (> 1: outside what the tubes were designed for); NaN when E is not square and
+        nonsingular."""
+        m, B, steps = self.m, me.shape[0], me.shape[1]
+        E = np.asarray(m.E, dtype=float)
+        if E.ndim != 2 or E.shape[0] != E.shape[1] or np.linalg.matrix_rank(E) < E.shape[0]:
+            return np.full((steps, B), np.nan)
+        wm = np.linalg.solve(E, me.reshape(-1, m.nx).T).T.reshape(B, steps, m.nx)
+        for i, w in enumerate(self._W_log[:steps]):
+            if w is not None:
+                wm[:, i] += w
+        return np.max(np.abs(wm), axis=2).T.copy()
 
     def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0):
         """Same results as run_on_device() -- bit for bit -- with the instances advancing through their MPC steps independently, so nobody waits for
@@ -155,6 +185,7 @@ class ClosedLoopMPC:
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
         Wc = None if W is None else _c(W)
         assert Wc is None or Wc.shape == (steps, B, m.nx)
+        self._W_log = [None] * steps if Wc is None else list(Wc)
         rounds = C.c_int(0)
         one_by_one = self.rti == 1 and f.opts.rti_steps == 1
         if one_by_one:
@@ -202,6 +233,10 @@ class ClosedLoopMPC:
             out["success"][:, i] = r["success"]
             out["scp_iterations"][:, i] = r["scp_iterations"]
             out["x0_violation"][:, i] = r["x0_violation"]
+            if self.f.plant_params is not None:
+                out.setdefault("model_error", np.zeros((B, m.nx, steps)))[:, :, i] = self.f.get("model_err", (m.nx,))
+        if "model_error" in out:
+            out.update(disturbance_used=self._disturbance_used(out["model_error"].transpose(0, 2, 1)), plant_params=np.array(self.f.plant_params))
         return out
 
     def save_npz(self, path, out, b=0):
@@ -213,4 +248,7 @@ class ClosedLoopMPC:
                  nominal_trajectory_x=out["nominal_trajectory_x"][b], nominal_trajectory_u=out["nominal_trajectory_u"][b],
                  backoff_trajectory_x=out["backoff_trajectory_x"][b], backoff_trajectory_u=out["backoff_trajectory_u"][b],
                  dt=0.05, g=m.g, nx=m.nx, nu=m.nu, simulation_time_steps=steps, N=self.N,
-                 t_jac=out["t_jac"], t_qp=out["t_qp"], t_riccati=out["t_riccati"])
+                 t_jac=out["t_jac"], t_qp=out["t_qp"], t_riccati=out["t_riccati"],
+                 **({} if "model_error" not in out else dict(      # (only a run with plant parameters: the key set of every other run is unchanged)
+                     plant_params=out["plant_params"] if out["plant_params"].ndim == 1 else out["plant_params"][b], model_error=out["model_error"][b],
+                     disturbance_used=out["disturbance_used"][:, b])))

@@ -6,6 +6,9 @@
 //   Quadrotor.ode  dyn/quadrotor.py:108-174   (m=1, g=9.81, l=0.15, J=diag(0.02,0.02,0.04), kM=0.01)
 //   Rocket.ode     dyn/rocket.py:165-254      (parameters :24-38; gimbal linkage `compute_gimbal_angle` :246-254)
 //   Model.ddyn     dyn/model.py:15-34         (RK4, h = 0.05 always: SURVEY quirk q8)
+// The physical constants come from a parameter source (a further template argument, see ParamDefault / ParamPtr below): compile-time constants for
+// the controller's model, a vector for the true plant of a closed loop with parameter mismatch (pinned by tests/golden/dyn_*_params.npz: the
+// reference's ODEs after its `params` dict was changed).
 // Pinned by tests/golden/dyn_*.npz (values of ode/ddyn produced by the reference's own source; Jacobians by central
 // differences of the reference's ddyn).
 #pragma once
@@ -88,11 +91,46 @@ struct MathReplay {
 constexpr int MODEL_PENDULUM = 0, MODEL_QUADROTOR = 1, MODEL_ROCKET = 2;
 constexpr double RK4_H = 0.05;
 
+// ---- where an ODE evaluation gets its physical constants ----------------------------------------------------------------------------------
+// Parameter vectors (NP entries, Dims<MODEL>::NP; quadrotor and rocket in the order of the reference's `params` dicts, dyn/quadrotor.py:32-40,
+// dyn/rocket.py:25-39; the pendulum's are local to its ode, dyn/pendulum.py:26-44):
+//   pendulum  4: m1, m2, l, g
+//   quadrotor 7: m, g, l, Jx, Jy, Jz, kM
+//   rocket   13: mass, gravity_constant, inertia_xx, inertia_yy, inertia_zz, thrust_cog_offset, thrust_magnitude_time_constant,
+//                servo_angle_time_constant, gimbal_a, gimbal_b, gimbal_c, gimbal_d, gimbal_e
+// ParamDefault: the reference's values as compile-time constants -- the controller's model (linearisation, predicted tail of the shifted nominal,
+// nominal initialiser) and every instantiation that names no source.  ParamPtr: reads a vector in that order -- the plant step of a closed loop
+// whose plant differs from the controller's model (slsqp_cl_set_plant_params).
+constexpr int NP_MAX = 13;
+template <int MODEL> DYN_HD constexpr double param_default(int i) {
+    return MODEL == MODEL_PENDULUM ? (i == 0 ? 1.0 : i == 1 ? 0.1 : i == 2 ? 0.5 : 9.81)
+         : MODEL == MODEL_QUADROTOR ? (i == 0 ? 1.0 : i == 1 ? 9.81 : i == 2 ? 0.15 : i == 3 ? 0.02 : i == 4 ? 0.02 : i == 5 ? 0.04 : 0.01)
+         : (i == 0 ? 1.16 : i == 1 ? 9.81 : i == 2 ? 0.00210 : i == 3 ? 0.1 : i == 4 ? 0.1 : i == 5 ? 0.42 : i == 6 ? 0.06 : i == 7 ? 0.10
+            : i == 8 ? 5.0 : i == 9 ? 35.2 : i == 10 ? 33.0 : i == 11 ? 28.0 : 35.2);
+}
+struct ParamDefault {
+    template <int MODEL, int I> DYN_HD constexpr double get() const { constexpr double v = param_default<MODEL>(I); return v; }
+};
+struct ParamPtr {
+    const double *p;
+    DYN_HD explicit ParamPtr(const double *q) : p(q) {}
+    template <int MODEL, int I> DYN_HD double get() const { return p[I]; }
+};
+// b^2 - c^2 of the gimbal linkage as two rounded products and one rounded difference, whatever the source: the default source's value is folded at
+// compile time that way, and a vector holding the defaults must give its bits (a fused multiply-add would round once)
+DYN_HD double sq_diff(double b, double c) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double bb = b * b, cc = c * c;
+    return bb - cc;
+}
+
 // ---- ODEs ---------------------------------------------------------------------------------------------------------
-template <typename T, typename M>
-DYN_HD void ode_pendulum(const T *X, const T *U, T *dX, M &mf) {
+template <typename T, typename M, typename P = ParamDefault>
+DYN_HD void ode_pendulum(const T *X, const T *U, T *dX, M &mf, const P &pp = P()) {
     const T xd = X[1], th = X[2], thd = X[3], u = U[0];
-    const double m1 = 1.0, m2 = 0.1, l = 0.5, g = 9.81;
+    const double m1 = pp.template get<MODEL_PENDULUM, 0>(), m2 = pp.template get<MODEL_PENDULUM, 1>(), l = pp.template get<MODEL_PENDULUM, 2>(), g = pp.template get<MODEL_PENDULUM, 3>();
     T s, c;
     mf.sincos(th, s, c);
     const T den = T(m1) + T(m2) * (T(1.0) - c * c);
@@ -113,9 +151,11 @@ DYN_HD void rot_apply(T qw, T qx, T qy, T qz, T bx, T by, T bz, T &wx, T &wy, T 
     wz = r20 * bx + r21 * by + r22 * bz;
 }
 
-template <typename T, typename M>
-DYN_HD void ode_quadrotor(const T *X, const T *U, T *dX, M &) {
-    const double m = 1.0, g = 9.81, l = 0.15, Jx = 0.02, Jy = 0.02, Jz = 0.04, kM = 0.01;
+template <typename T, typename M, typename P = ParamDefault>
+DYN_HD void ode_quadrotor(const T *X, const T *U, T *dX, M &, const P &pp = P()) {
+    constexpr int Q = MODEL_QUADROTOR;
+    const double m = pp.template get<Q, 0>(), g = pp.template get<Q, 1>(), l = pp.template get<Q, 2>(), Jx = pp.template get<Q, 3>(), Jy = pp.template get<Q, 4>(),
+                 Jz = pp.template get<Q, 5>(), kM = pp.template get<Q, 6>();
     const T qw = X[6], qx = X[7], qy = X[8], qz = X[9], wx = X[10], wy = X[11], wz = X[12];
     const T f1 = U[0], f2 = U[1], f3 = U[2], f4 = U[3];
     const T Fz = f1 + f2 + f3 + f4;
@@ -136,30 +176,34 @@ DYN_HD void ode_quadrotor(const T *X, const T *U, T *dX, M &) {
     dX[12] = (tz - (wx * Jwy - wy * Jwx)) * T(1.0 / Jz);
 }
 
-template <typename T, typename M>
-DYN_HD T gimbal_angle(T servo, T cos_tilt, M &mf) {   // rocket.py:246-254; takes cos(tilt_axis_angle): the caller has it already
-    const double a = 5.0, b = 35.2, c = 33.0, d = 28.0, e = 35.2;
+template <typename T, typename M, typename P = ParamDefault>
+DYN_HD T gimbal_angle(T servo, T cos_tilt, M &mf, const P &pp = P()) {   // rocket.py:246-254; takes cos(tilt_axis_angle): the caller has it already
+    constexpr int R = MODEL_ROCKET;
+    const double a = pp.template get<R, 8>(), b = pp.template get<R, 9>(), c = pp.template get<R, 10>(), d = pp.template get<R, 11>(), e = pp.template get<R, 12>();
     T ss, cs;
     mf.sincos(servo, ss, cs);
     const T iv1 = T(d) + T(a) * cs;
     const T iv2 = T(e) - T(a) * ss;
-    const T u = T(b * b - c * c) - iv1 * iv1 - iv2 * iv2;
+    const T u = T(sq_diff(b, c)) - iv1 * iv1 - iv2 * iv2;
     const T v = T(2.0 * c) * cos_tilt * iv2;
     const T w = T(-2.0 * c) * iv1;
     const T iv3 = w * w + v * v - u * u;
     return T(2.0) * mf.atan((v - mf.sqrt(iv3)) / (u + w));
 }
 
-template <typename T, typename M>
-DYN_HD void ode_rocket(const T *X, const T *U, T *dX, M &mf) {
-    const double mass = 1.16, grav = 9.81, Jxx = 0.00210, Jyy = 0.1, Jzz = 0.1, off = 0.42, tau_t = 0.06, tau_s = 0.10, hover = 11.3796;
+template <typename T, typename M, typename P = ParamDefault>
+DYN_HD void ode_rocket(const T *X, const T *U, T *dX, M &mf, const P &pp = P()) {
+    constexpr int R = MODEL_ROCKET;
+    const double mass = pp.template get<R, 0>(), grav = pp.template get<R, 1>(), Jxx = pp.template get<R, 2>(), Jyy = pp.template get<R, 3>(), Jzz = pp.template get<R, 4>(),
+                 off = pp.template get<R, 5>(), tau_t = pp.template get<R, 6>(), tau_s = pp.template get<R, 7>();
+    const double hover = 11.3796;      // (a literal of the reference's ODE, rocket.py:173,179, not one of its parameters: a heavier rocket sags)
     const T qw = X[6], qx = X[7], qy = X[8], qz = X[9], wx = X[10], wy = X[11], wz = X[12];
     const T thrust = X[13] + T(hover), torque_x = X[14], sa1 = X[15], sa2 = X[16];
     const T thrust_in = U[0] + T(hover), torque_in = U[1], sa1_in = U[2], sa2_in = U[3];
     T s1, c1, s2, c2;
-    const T g1 = gimbal_angle(sa1, T(1.0), mf);
+    const T g1 = gimbal_angle(sa1, T(1.0), mf, pp);
     mf.sincos(g1, s1, c1);
-    const T g2 = gimbal_angle(sa2, c1, mf);
+    const T g2 = gimbal_angle(sa2, c1, mf, pp);
     mf.sincos(g2, s2, c2);
     const T Bx = -thrust * s1 * c2, By = thrust * s2, Bz = thrust * c1 * c2;
     T ax, ay, az;
@@ -184,33 +228,36 @@ DYN_HD void ode_rocket(const T *X, const T *U, T *dX, M &mf) {
 
 template <int MODEL> struct Dims;
 // NT: transcendental values one ODE evaluation puts on the tape (pendulum: sin, cos; rocket: 2 x (sin, cos, sqrt, atan) of the gimbal linkage + 2 x (sin, cos))
-template <> struct Dims<MODEL_PENDULUM> { static constexpr int NX = 4, NU = 1, NT = 2; };
-template <> struct Dims<MODEL_QUADROTOR> { static constexpr int NX = 13, NU = 4, NT = 0; };
-template <> struct Dims<MODEL_ROCKET> { static constexpr int NX = 17, NU = 4, NT = 12; };
+// NP: physical parameters (see ParamDefault above)
+template <> struct Dims<MODEL_PENDULUM> { static constexpr int NX = 4, NU = 1, NT = 2, NP = 4; };
+template <> struct Dims<MODEL_QUADROTOR> { static constexpr int NX = 13, NU = 4, NT = 0, NP = 7; };
+template <> struct Dims<MODEL_ROCKET> { static constexpr int NX = 17, NU = 4, NT = 12, NP = 13; };
 constexpr int NT_MAX = 12;
 
-template <int MODEL, typename T, typename M>
-DYN_HD void ode(const T *X, const T *U, T *dX, M &mf) {
-    if (MODEL == MODEL_PENDULUM) ode_pendulum<T, M>(X, U, dX, mf);
-    else if (MODEL == MODEL_QUADROTOR) ode_quadrotor<T, M>(X, U, dX, mf);
-    else ode_rocket<T, M>(X, U, dX, mf);
+template <int MODEL, typename T, typename M, typename P = ParamDefault>
+DYN_HD void ode(const T *X, const T *U, T *dX, M &mf, const P &pp = P()) {
+    if (MODEL == MODEL_PENDULUM) ode_pendulum<T, M, P>(X, U, dX, mf, pp);
+    else if (MODEL == MODEL_QUADROTOR) ode_quadrotor<T, M, P>(X, U, dX, mf, pp);
+    else ode_rocket<T, M, P>(X, U, dX, mf, pp);
 }
 template <int MODEL, typename T>
 DYN_HD void ode(const T *X, const T *U, T *dX) { MathPlain mf; ode<MODEL, T, MathPlain>(X, U, dX, mf); }
+template <int MODEL, typename T, typename P>
+DYN_HD void ode_with(const T *X, const T *U, T *dX, const P &pp) { MathPlain mf; ode<MODEL, T, MathPlain, P>(X, U, dX, mf, pp); }
 
 // x+ = RK4(x, u), h = 0.05   (dyn/model.py:27-32); k's are accumulated on the fly to keep the register footprint small
-template <int MODEL, typename T>
-DYN_HD void ddyn(const T *X, const T *U, T *Xp) {
+template <int MODEL, typename T, typename P = ParamDefault>
+DYN_HD void ddyn(const T *X, const T *U, T *Xp, const P &pp = P()) {
     constexpr int NX = Dims<MODEL>::NX;
     const T h(RK4_H);
     T k[NX], t[NX], acc[NX];
-    ode<MODEL, T>(X, U, k);
+    ode_with<MODEL, T, P>(X, U, k, pp);
     for (int i = 0; i < NX; i++) { acc[i] = k[i]; t[i] = X[i] + T(0.5) * h * k[i]; }
-    ode<MODEL, T>(t, U, k);
+    ode_with<MODEL, T, P>(t, U, k, pp);
     for (int i = 0; i < NX; i++) { acc[i] = acc[i] + T(2.0) * k[i]; t[i] = X[i] + T(0.5) * h * k[i]; }
-    ode<MODEL, T>(t, U, k);
+    ode_with<MODEL, T, P>(t, U, k, pp);
     for (int i = 0; i < NX; i++) { acc[i] = acc[i] + T(2.0) * k[i]; t[i] = X[i] + h * k[i]; }
-    ode<MODEL, T>(t, U, k);
+    ode_with<MODEL, T, P>(t, U, k, pp);
     for (int i = 0; i < NX; i++) Xp[i] = X[i] + T(1.0 / 6.0) * (acc[i] + k[i]) * h;
 }
 

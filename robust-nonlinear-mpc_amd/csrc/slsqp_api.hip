@@ -16,6 +16,7 @@
 #include "../../include/slsqp.h"
 #include "slsqp_kernels.hpp"
 #include "slsqp_mw.hpp"
+#include "plant_params.hpp"
 
 using namespace slsqp;
 
@@ -72,6 +73,9 @@ struct slsqp_handle {
     double x0_box_tol = 0.0;    // slsqp_set_x0_box_tol: the tolerance the following launches ask for
     int solve_waves = 1;        // slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = k_qp_solve_mw (one workgroup of that many waves per instance)
     double *ref_Y = nullptr; int ref_T = 0; size_t ref_stride = 0;      // slsqp_cl_set_reference: packed rows [x_ref; u_ref] (T, nz), per instance with ref_stride = T nz, shared with 0; ref_T = 0: none
+    // slsqp_cl_set_plant_params: one allocation [P (rows, np) | model_err (B, nx) | nz zeros]: parameter rows (pp_stride = np per instance, 0 shared; pp_P NULL: none),
+    // ddyn_p - ddyn of the last plant step, and the one-row zero reference the _pp persistent kernels take for a handle without a reference
+    double *pp_P = nullptr, *pp_merr = nullptr, *pp_zero_ref = nullptr, *lg_merr = nullptr; int pp_np = 0, pp_stride = 0; std::vector<double> pp_host;
     double *cr = nullptr;       // (B,N,3,nx,nx) scratch of the cyclic reduction (slsqp_mw.hpp), allocated by the first launch that needs it
     int ne_waves = 0;           // slsqp_ne_solve: the path whose factors the last factorising call left (0 = none)
     double x0_tol_dev = 0.0;    // the tolerance of the x0 gate the device currently holds (kkt[8 B]; written when a launch asks for another one)
@@ -100,6 +104,7 @@ struct slsqp_handle {
 };
 
 static RefArgs ref_args(slsqp_handle *h) { return RefArgs{h->ref_Y, h->ref_T, h->ref_stride}; }
+static PlantArgs plant_args(slsqp_handle *h) { return PlantArgs{h->pp_P, h->pp_stride, h->pp_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps}; }
 static Costs costs_of(slsqp_handle *h) {
     const int nx = h->d.nx, nu = h->d.nu;
     Costs c;
@@ -250,6 +255,7 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     if (h->stage) hipFree(h->stage);
     if (h->cl_W) hipFree(h->cl_W);
     if (h->ref_Y) hipFree(h->ref_Y);
+    if (h->pp_P) hipFree(h->pp_P);
     if (h->qplog) hipFree(h->qplog);
     if (h->x0vlog) hipFree(h->x0vlog);
     if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
@@ -761,8 +767,8 @@ __device__ CLW_FN void cl_step_begin(const LoopArgs &L, int b, int lane, const R
     CLSTAMP(6);
 }
 // nominal += delta, primal infeasibility, log entry, plant + noise, step counter; returns the instance's new step count while it has steps left, else 0
-template <int MODEL>
-__device__ CLW_FN int cl_step_end(const LoopArgs &L, int b, int lane) {
+template <int MODEL, bool PP = false>
+__device__ CLW_FN int cl_step_end(const LoopArgs &L, int b, int lane, const PlantArgs *pa = nullptr) {
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int s = L.stepno[b];
 #ifdef CL_LOOP_STAMP
@@ -782,7 +788,7 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L, int b, int lane) {
     }
     CLSTAMP(9);
     if (lane == 0) {
-        cl_plant_one<MODEL>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr);
+        cl_plant_one<MODEL, PP>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
         L.stepno[b] = s + 1;
         if (L.busy) { atomicAdd(L.busy, wall_clock64() - L.t_begin[b]); atomicAdd(L.busy + 2, 1ULL); }
     }
@@ -881,6 +887,45 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_ref(L
     }
 }
 
+// The same loop for a handle with plant parameters (slsqp_cl_set_plant_params): the only difference to k_cl_loop_ref is the plant step of cl_step_end
+// (the instance's own parameter row, model_err and its log).  Written once, on the body that takes a reference: a handle with parameters but without a
+// reference passes one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference.  Keep the bodies in step --
+// tests/test_gpu_plant_params.py holds this one to the step-by-step loop bit for bit.
+template <int MODEL>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_pp(LoopArgs L, RefArgs rf, PlantArgs pa) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    int lane = threadIdx.x;
+    extern __shared__ double sm[];
+    int b = -1;
+#pragma unroll 1
+    for (;;) {
+        asm volatile("" : "+v"(lane));
+        if (b < 0) {
+            b = clq_pop(L.Q, lane);
+            if (b < 0) break;
+            if (L.fence & 1) __threadfence();      // acquire: what the wave that ran this instance's previous step wrote (possibly through another XCD's L2)
+        }
+        cl_step_begin<MODEL, true>(L, b, lane, &rf);
+        b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
+        asm volatile("" : "+v"(lane));
+        rti_chain_dev<NX, NU>(L.c, b, lane, sm);
+        wla::wsync_mem();
+        asm volatile("" : "+v"(lane));
+        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, true>(L, b, lane, &pa));
+        b = __builtin_amdgcn_readfirstlane(b);
+        if (!next) { b = -1; continue; }
+        // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
+        // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
+        // waves are shared fairly among the instances that are level
+        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
+        if (behind && L.keep_laggards) continue;
+        if (L.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
+        clq_push(L.Q, b, lane);
+        b = -1;
+    }
+}
+
 // ---- the persistent loop for any SCP setting of slsqp_cl_step (slsqp_cl_run_scp) -------------------------------------------------------
 // One queue item is still one whole MPC step of one instance, but the step is the general one: max_it SCP iterations (SCP_SLS.solve,
 // SCP_SLS_jit.py:103-135), each a fast-SLS solve of rti_steps steps (fast_SLS.solve, fast_SLS_jit.py:278-296) -- what slsqp_cl_step and solve_impl
@@ -935,8 +980,8 @@ __device__ CLW_FN int cl_scp_iter_end(const LoopArgs &L, int b, int lane, int ii
     return L.scp_active[b];
 }
 // log entries, plant step + noise, step counter; returns the instance's new step count while it has steps left, else 0
-template <int MODEL>
-__device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S, int b, int lane, int nsolves) {
+template <int MODEL, bool PP = false>
+__device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S, int b, int lane, int nsolves, const PlantArgs *pa = nullptr) {
     const LoopArgs &L = S.L;
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int s = L.stepno[b];
@@ -950,7 +995,7 @@ __device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S, int b, int lane, int
         if (lane == 0) S.nsolves[(size_t)b * L.c.log_steps + s] = nsolves;
     }
     if (lane == 0) {
-        cl_plant_one<MODEL>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr);
+        cl_plant_one<MODEL, PP>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
         L.stepno[b] = s + 1;
         if (L.busy) { atomicAdd(L.busy, wall_clock64() - L.t_begin[b]); atomicAdd(L.busy + 2, 1ULL); }
     }
@@ -1085,6 +1130,50 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_r
         }
         asm volatile("" : "+v"(lane));
         const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL>(S, b, lane, nsolves));
+        b = __builtin_amdgcn_readfirstlane(b);
+        if (!next) { b = -1; continue; }
+        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
+        if (behind && L.keep_laggards) continue;
+        if (L.fence & 2) __threadfence();
+        clq_push(L.Q, b, lane);
+        b = -1;
+    }
+}
+// k_cl_loop_scp_ref for a handle with plant parameters: as k_cl_loop_pp above, the plant step of cl_scp_step_end is the only difference
+template <int MODEL>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_pp(ScpLoopArgs S, RefArgs rf, PlantArgs pa) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    const LoopArgs &L = S.L;
+    int lane = threadIdx.x;
+    extern __shared__ double sm[];
+    int b = -1;
+#pragma unroll 1
+    for (;;) {
+        asm volatile("" : "+v"(lane));
+        if (b < 0) {
+            b = clq_pop(L.Q, lane);
+            if (b < 0) break;
+            if (L.fence & 1) __threadfence();
+        }
+        cl_scp_step_begin<MODEL>(L, b, lane);
+        b = __builtin_amdgcn_readfirstlane(b);
+        int nsolves = 0;
+#pragma unroll 1
+        for (int ii = 0; ii < S.max_it; ii++) {
+            asm volatile("" : "+v"(lane));
+            cl_scp_iter_begin<MODEL, true>(L, b, lane, ii, &rf);
+            b = __builtin_amdgcn_readfirstlane(b);
+            asm volatile("" : "+v"(lane));
+            sls_solve_dev<NX, NU>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0);
+            asm volatile("" : "+v"(lane));
+            const int act = __builtin_amdgcn_readfirstlane(cl_scp_iter_end<MODEL>(L, b, lane, ii, S.converge));
+            b = __builtin_amdgcn_readfirstlane(b);
+            nsolves = ii + 1;
+            if (S.converge && !act) break;
+        }
+        asm volatile("" : "+v"(lane));
+        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL, true>(S, b, lane, nsolves, &pa));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
         const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1627,6 +1716,8 @@ extern "C" int slsqp_kernel_timing(slsqp_handle *h, double *out8, int len) {
 
 // bytes per instance of a named result (what slsqp_get copies for each instance), or -1 for an unknown name
 extern "C" long long slsqp_result_bytes(slsqp_handle *h, const char *name) {
+    if (!strcmp(name, "plant_params")) return h->model_id < 0 ? -1LL : (long long)sizeof(double) * plant_params::count(h->model_id);
+    if (!strcmp(name, "model_err")) return (long long)sizeof(double) * h->d.nx;
     auto it = h->named.find(name);
     return it == h->named.end() ? -1LL : (long long)it->second.second;
 }
@@ -1682,8 +1773,73 @@ extern "C" int slsqp_cl_set_reference(slsqp_handle *h, const double *Xref, const
     return 0;
 }
 
+// Plant parameters: names and defaults per model, and the setter -- validated on the host (plant_params.hpp), uploaded into a new buffer, and only
+// then the previous buffer is dropped: a refused call leaves the previous parameters in force.
+extern "C" int slsqp_plant_param_count(int model_id) { return plant_params::count(model_id); }
+extern "C" const char *slsqp_plant_param_name(int model_id, int i) { return plant_params::name(model_id, i); }
+extern "C" int slsqp_plant_param_defaults(int model_id, double *out, int len) {
+    const int np = plant_params::count(model_id);
+    if (np < 0) return fail("slsqp_plant_param_defaults: unknown model id (0 pendulum, 1 quadrotor, 2 rocket)");
+    if (!out || len < np) return fail("slsqp_plant_param_defaults: the buffer must hold slsqp_plant_param_count(model_id) doubles");
+    for (int i = 0; i < np; i++) out[i] = plant_params::default_value(model_id, i);
+    return np;
+}
+extern "C" int slsqp_cl_set_plant_params(slsqp_handle *h, const double *P, int np, int per_instance, int loc) {
+    hipSetDevice(h->dev);
+    if (h->model_id < 0) return fail("slsqp_cl_set_plant_params: slsqp_set_model must be called first");
+    if (per_instance != 0 && per_instance != 1) return fail("slsqp_cl_set_plant_params: per_instance must be 0 (one row for the batch) or 1 (P (B,np))");
+    if (loc != SLSQP_HOST && loc != SLSQP_DEVICE) return fail("slsqp_cl_set_plant_params: loc must be SLSQP_HOST or SLSQP_DEVICE");
+    if (np < 0) return fail("slsqp_cl_set_plant_params: np must be the model's parameter count (or 0 with P = NULL to clear the parameters)");
+    if (np == 0 && P) return fail("slsqp_cl_set_plant_params: np = 0 clears the parameters and takes P = NULL");
+    if (np > 0 && !P) return fail("slsqp_cl_set_plant_params: P is NULL with np > 0 (np = 0 clears the parameters)");
+    HIPCHK(hipStreamSynchronize(h->st));      // no launch may still read the buffer that is replaced
+    if (np == 0) {
+        if (h->pp_P) hipFree(h->pp_P);
+        h->pp_P = h->pp_merr = h->pp_zero_ref = nullptr; h->pp_np = 0; h->pp_stride = 0; h->pp_host.clear();
+        return 0;
+    }
+    if (np != plant_params::count(h->model_id)) { std::string why; plant_params::check(h->model_id, nullptr, 0, np, &why); return fail("slsqp_cl_set_plant_params: " + why); }
+    const size_t rows = per_instance ? (size_t)h->B : 1, nP = rows * np, nE = (size_t)h->B * h->d.nx, nZ = (size_t)h->nz;
+    std::vector<double> host(nP);
+    HIPCHK(hipMemcpy(host.data(), P, sizeof(double) * nP, loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost));
+    std::string why;
+    if (!plant_params::check(h->model_id, host.data(), rows, np, &why)) return fail("slsqp_cl_set_plant_params: " + why);
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (nP + nE + nZ) + 64));
+    if (hipMemset(buf, 0, sizeof(double) * (nP + nE + nZ)) != hipSuccess || hipMemcpy(buf, host.data(), sizeof(double) * nP, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(buf);
+        return fail("slsqp_cl_set_plant_params: upload failed");
+    }
+    if (h->pp_P) hipFree(h->pp_P);
+    h->pp_P = buf; h->pp_merr = buf + nP; h->pp_zero_ref = buf + nP + nE; h->pp_np = np; h->pp_stride = per_instance ? np : 0; h->pp_host.swap(host);
+    return 0;
+}
+// slsqp_get names that depend on the plant parameters: plant_params (B,np) (a shared row repeated; the defaults for a handle without parameters),
+// model_err (B,nx) (zeros without parameters).  Returns 1 when `name` was one of them and has been served, 0 when not, -1 on error.
+static int get_plant_named(slsqp_handle *h, const char *name, void *out, int loc) {
+    const bool is_P = !strcmp(name, "plant_params"), is_e = !strcmp(name, "model_err");
+    if (!is_P && !is_e) return 0;
+    if (h->model_id < 0) return fail(std::string(name) + ": slsqp_set_model must be called first");
+    const hipMemcpyKind kind = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice;
+    HIPCHK(hipStreamSynchronize(h->st));
+    if (is_e) {
+        const size_t n = (size_t)h->B * h->d.nx;
+        if (h->pp_P) HIPCHK(hipMemcpy(out, h->pp_merr, sizeof(double) * n, loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        else { std::vector<double> z(n, 0.0); HIPCHK(hipMemcpy(out, z.data(), sizeof(double) * n, kind)); }
+        return 1;
+    }
+    const int np = plant_params::count(h->model_id);
+    std::vector<double> v((size_t)h->B * np);
+    for (size_t b = 0; b < (size_t)h->B; b++)
+        for (int i = 0; i < np; i++) v[b * np + i] = h->pp_P ? h->pp_host[(h->pp_stride ? b * np : 0) + i] : plant_params::default_value(h->model_id, i);
+    HIPCHK(hipMemcpy(out, v.data(), sizeof(double) * v.size(), kind));
+    return 1;
+}
+
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
+    if (const int r = get_plant_named(h, name, out, loc)) return r < 0 ? -1 : 0;
+    if (!h->pp_P && h->lg_merr && !strcmp(name, "log_model_error")) HIPCHK(hipMemsetAsync(h->lg_merr, 0, sizeof(double) * (size_t)h->B * h->log_steps * h->d.nx, h->st));      // (a handle without parameters: all zeros, whatever an earlier run with parameters left)
     auto it = h->named.find(name);
     if (it == h->named.end()) return fail(std::string("unknown result name: ") + name);
     const size_t bytes = it->second.second * (size_t)h->B;
@@ -1894,9 +2050,9 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     HIPCHK(hipStreamSynchronize(h->st));
     h->log_steps = 0;
     free_all(h->log_owned);
-    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol"};
+    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error"};
     for (const char *nm : names) h->named.erase(nm);
-    h->lg_x0v = nullptr;
+    h->lg_x0v = nullptr; h->lg_merr = nullptr;
     h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr;
     const slsqp_dims &d = h->d;
     const size_t B = h->B, S = max_steps, nX = (size_t)(d.N + 1) * d.nx, nU = (size_t)d.N * d.nu;
@@ -1904,8 +2060,8 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     auto &ow = h->log_owned;
     rc |= dalloc(ow, &h->lg_x, B * S * nX); rc |= dalloc(ow, &h->lg_u, B * S * nU); rc |= dalloc(ow, &h->lg_bx, B * S * nX); rc |= dalloc(ow, &h->lg_bu, B * S * nU);
     rc |= dalloc(ow, &h->lg_state, B * S * d.nx); rc |= dalloc(ow, &h->lg_u0, B * S * d.nu); rc |= dalloc(ow, &h->lg_succ, B * S); rc |= dalloc(ow, &h->lg_it, B * S);
-    rc |= dalloc(ow, &h->lg_pinf, B * S); rc |= dalloc(ow, &h->lg_x0v, B * S * 2);
-    if (rc) { free_all(ow); h->lg_x0v = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
+    rc |= dalloc(ow, &h->lg_pinf, B * S); rc |= dalloc(ow, &h->lg_x0v, B * S * 2); rc |= dalloc(ow, &h->lg_merr, B * S * d.nx);
+    if (rc) { free_all(ow); h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
     h->log_steps = max_steps;
     auto reg = [&](const char *nm, void *p, size_t bytes) { h->named[nm] = {p, bytes}; };
     reg("log_nominal_x", h->lg_x, sizeof(double) * S * nX); reg("log_nominal_u", h->lg_u, sizeof(double) * S * nU);
@@ -1913,6 +2069,7 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     reg("log_state", h->lg_state, sizeof(double) * S * d.nx); reg("log_u0", h->lg_u0, sizeof(double) * S * d.nu);
     reg("log_success", h->lg_succ, sizeof(int) * S); reg("log_scp_iterations", h->lg_it, sizeof(int) * S);
     reg("log_primal_infeasibility", h->lg_pinf, sizeof(double) * S); reg("log_x0_viol", h->lg_x0v, sizeof(double) * S * 2);
+    reg("log_model_error", h->lg_merr, sizeof(double) * S * d.nx);      // ddyn_p - ddyn of every step's plant step (slsqp_cl_set_plant_params; zeros without parameters)
     return 0;
 }
 
@@ -1985,7 +2142,13 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
         hipLaunchKernelGGL(k_cl_log_x0v, dim3((2 * h->B + 255) / 256), dim3(256), 0, h->st, h->B, h->log_steps, h->cl_steps, h->x0viol, h->qpstat, h->lg_x0v);
         h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};      // (a slsqp_cl_run in between points the name at its own per-run buffer)
     }
-    if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
+    if (h->pp_P) {      // the plant has its own parameters
+        const PlantArgs pa = plant_args(h);
+        if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant_pp<0>), dim3(gb), dim3(64), 0, h->st, a, pa, h->cl_steps, nullptr, nullptr, nullptr);
+        else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant_pp<1>), dim3(gb), dim3(64), 0, h->st, a, pa, h->cl_steps, nullptr, nullptr, nullptr);
+        else hipLaunchKernelGGL((k_cl_shift_plant_pp<2>), dim3(gb), dim3(64), 0, h->st, a, pa, h->cl_steps, nullptr, nullptr, nullptr);
+    }
+    else if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
     else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant<1>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
     else hipLaunchKernelGGL((k_cl_shift_plant<2>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
     HIPCHK(hipGetLastError());
@@ -2014,7 +2177,13 @@ static int launch_loop_t(slsqp_handle *h, LoopArgs &L, const ScpLoopArgs *S = nu
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     hipEventRecord(h->ev[8], h->st);
-    if (h->ref_T > 0) {      // tracked cost: the kernels that take the reference
+    if (h->pp_P) {      // plant parameters: the kernels that take them (written on the tracked bodies: without a reference, one row of zeros)
+        const RefArgs rf = h->ref_T > 0 ? ref_args(h) : RefArgs{h->pp_zero_ref, 1, 0};
+        const PlantArgs pa = plant_args(h);
+        if (S) hipLaunchKernelGGL((k_cl_loop_scp_pp<MODEL>), dim3(grid), dim3(64), lds, h->st, *S, rf, pa);
+        else hipLaunchKernelGGL((k_cl_loop_pp<MODEL>), dim3(grid), dim3(64), lds, h->st, L, rf, pa);
+    }
+    else if (h->ref_T > 0) {      // tracked cost: the kernels that take the reference
         const RefArgs rf = ref_args(h);
         if (S) hipLaunchKernelGGL((k_cl_loop_scp_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, *S, rf);
         else hipLaunchKernelGGL((k_cl_loop_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, L, rf);
@@ -2214,7 +2383,13 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
                          h->pinf, h->lg_x, h->lg_u, h->lg_bx, h->lg_bu, h->lg_state, h->lg_u0, h->lg_pinf, h->lg_succ, h->lg_it};
             hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, la);
         }
-        if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
+        if (h->pp_P) {
+            const PlantArgs pa = plant_args(h);
+            if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant_pp<0>), dim3(gb), dim3(64), 0, h->st, a, pa, 0, h->cl_done, h->cl_stepno, dW);
+            else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant_pp<1>), dim3(gb), dim3(64), 0, h->st, a, pa, 0, h->cl_done, h->cl_stepno, dW);
+            else hipLaunchKernelGGL((k_cl_shift_plant_pp<2>), dim3(gb), dim3(64), 0, h->st, a, pa, 0, h->cl_done, h->cl_stepno, dW);
+        }
+        else if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
         else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant<1>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
         else hipLaunchKernelGGL((k_cl_shift_plant<2>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
         hipLaunchKernelGGL(k_cl_advance, dim3(gbi), dim3(256), 0, h->st, B, h->cl_done, h->cl_stepno, h->call_ids, h->cl_begin);

@@ -2444,14 +2444,43 @@ __global__ void k_cl_log(ClLogArgs a) {
 // plant step (expe/main_rocket...:180-182): x_meas <- ddyn(x_meas, u0) + E w.   One thread per instance.
 // slsqp_cl_run: mask (B) selects the instances; shift only those past their first step (stepno > 0); the disturbance sample of an instance is the one
 // of ITS step, W_all (steps, B, NX).
-template <int MODEL>
-__device__ __forceinline__ void cl_plant_one(const ClArgs &a, int b, const double *w /* (B,NX) sample or NULL */) {      // one thread
+// Plant parameters (slsqp_cl_set_plant_params): the true plant of instance b is the ODE with row b of P (NP entries in the order of
+// dyn::ParamDefault; stride 0: one row shared by the batch, stride NP: one per instance) while the controller keeps the constants.  model_err
+// (B,NX) receives ddyn_p(x,u0) - ddyn(x,u0) of the step, before the noise is added; lg (B,S,NX) or NULL its per-step log.  Only the kernels
+// launched for a handle WITH parameters take this argument (the PP = true instantiations); every other kernel keeps its arguments and its code.
+struct PlantArgs { const double *P; int stride; double *model_err; double *lg; int S; };
+template <int MODEL, bool PP = false>
+__device__ __forceinline__ void cl_plant_one(const ClArgs &a, int b, const double *w /* (B,NX) sample or NULL */, const PlantArgs *pa = nullptr, int step = 0) {      // one thread
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     const double *U = a.Un + (size_t)b * a.N * NU;
     double xm[NX], u[NU], xp[NX];
     for (int i = 0; i < NX; i++) xm[i] = a.xmeas[(size_t)b * NX + i];
     for (int i = 0; i < NU; i++) { u[i] = U[i]; a.u0[(size_t)b * NU + i] = u[i]; }
-    dyn::ddyn<MODEL, double>(xm, u, xp);
+    if constexpr (PP) {
+        constexpr int NP = dyn::Dims<MODEL>::NP;
+        double xc[NX], pr[NP];
+        dyn::ddyn<MODEL, double>(xm, u, xc);      // the controller's model at the same point ...
+#pragma unroll
+        for (int i = 0; i < NX; i++) asm volatile("" : "+v"(xc[i]));      // (... finished before the plant's step starts: two RK4 steps in turn, not interleaved, keep the registers of one)
+        // The plant's step gets (x, u0) as values the compiler knows nothing about: sharing subexpressions between the two evaluations (the rotation
+        // matrix of the first stage, ...) gives products a second use, and a product with two uses is no longer fused into a multiply-add -- the
+        // model's step above would then round differently from the same source in the kernels without parameters.
+#pragma unroll
+        for (int i = 0; i < NX; i++) asm volatile("" : "+v"(xm[i]));
+#pragma unroll
+        for (int i = 0; i < NU; i++) asm volatile("" : "+v"(u[i]));
+        bool is_model = true;
+        for (int i = 0; i < NP; i++) { pr[i] = pa->P[(size_t)b * pa->stride + i]; is_model = is_model && pr[i] == dyn::param_default<MODEL>(i); }
+        // A row that holds the model's constants bit for bit IS the model: it takes the model's step, so that explicit defaults give a model error of
+        // exactly zero (the pointer instantiation does not promise the folded constants' rounding on the device).
+        if (is_model) { for (int i = 0; i < NX; i++) xp[i] = xc[i]; }
+        else dyn::ddyn<MODEL, double, dyn::ParamPtr>(xm, u, xp, dyn::ParamPtr(pr));
+        for (int i = 0; i < NX; i++) {
+            const double e = xp[i] - xc[i];
+            pa->model_err[(size_t)b * NX + i] = e;
+            if (pa->lg && step < pa->S) pa->lg[((size_t)b * pa->S + step) * NX + i] = e;      // (past the log's last entry nothing is written, as slsqp_cl_step's other logs)
+        }
+    } else dyn::ddyn<MODEL, double>(xm, u, xp);
     for (int i = 0; i < NX; i++) {
         double s = xp[i];
         if (w) for (int j = 0; j < NX; j++) s += a.E[i * NX + j] * w[(size_t)b * NX + j];
@@ -2485,6 +2514,19 @@ __global__ void k_cl_shift_plant(ClArgs a, int do_shift, int do_plant, const int
         for (int k = 0; k + 1 < a.N; k++) for (int i = 0; i < NU; i++) U[(size_t)k * NU + i] = U[(size_t)(k + 1) * NU + i];
         for (int i = 0; i < NX; i++) X[(size_t)a.N * NX + i] = xp[i];
     }
+}
+// the plant step of a handle with plant parameters (slsqp_cl_step, the rounds of slsqp_cl_run); the shift stays k_cl_shift_plant's: it is the
+// controller's prediction.  step: the MPC step the instances are at, or stepno[b].  Launched with 64 threads a block: two RK4 steps of the rocket
+// fit the registers of a 64-thread block without scratch
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_cl_shift_plant_pp(ClArgs a, PlantArgs pa, int step, const int *mask, const int *stepno, const double *W_all) {
+    constexpr int NX = dyn::Dims<MODEL>::NX;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.B) return;
+    if (mask && !mask[b]) return;
+    if (stepno) step = stepno[b];
+    if (W_all) a.w = W_all + (size_t)step * a.B * NX;      // (mask[b] implies stepno[b] < steps, as in k_cl_shift_plant)
+    cl_plant_one<MODEL, true>(a, b, a.w, &pa, step);
 }
 // the same shift of ONE instance by one wave (k_cl_loop): the tail by lane 0, the copies by all lanes (read everything, then write)
 template <int MODEL>

@@ -101,6 +101,7 @@ class BatchedFastSLS:
         self._R_reg = _c(np.eye(nu) if R_reg is None else R_reg)
         self._Q_reg_f = _c(np.eye(nx) if Q_reg_f is None else Q_reg_f)
         self.solver_forward = _SolverForward(self)
+        self.plant_params = None
         self.dims = L.Dims(nx, nu, model.nw, self.N, model.ni, model.ni_f)
         self.n = model.nz * self.N + nx
         self.mb = self.N * (nx + model.ni) + model.ni_f
@@ -199,6 +200,22 @@ class BatchedFastSLS:
         if U is not None and U.shape != X.shape[:-1] + (self.m.nu,):
             raise ValueError(f"set_reference: Uref must be {X.shape[:-1] + (self.m.nu,)}, got {U.shape}")
         L.check(self.lib.slsqp_cl_set_reference(self.h, _ptr(X), _ptr(U), int(X.shape[-2]), int(X.ndim == 3), L.HOST))
+
+    def set_plant_params(self, spec):
+        """Physical parameters of the TRUE plant of the closed-loop entry points (slsqp_cl_set_plant_params): a dict {name: scalar or (B,)}, an
+        array (np,) shared by the batch or (B,np) per instance (models.pack_plant_params; names and order: models.plant_param_names).  Only the plant
+        step uses them; the controller keeps the model's constants.  None clears them.  Kept by the handle until replaced."""
+        if spec is None:
+            self.plant_params = None
+            L.check(self.lib.slsqp_cl_set_plant_params(self.h, None, 0, 0, L.HOST))
+            return
+        from .models import pack_plant_params
+        if self.m.model_id is None:      # no plant: the library refuses with its message
+            P = _c(np.atleast_1d(np.asarray(spec, dtype=float)))
+        else:
+            P = _c(pack_plant_params(self.m, self.B, spec))
+        L.check(self.lib.slsqp_cl_set_plant_params(self.h, _ptr(P), int(P.shape[-1]), int(P.ndim == 2), L.HOST))
+        self.plant_params = P
 
     def update_linear_cost(self, q):
         q = _c(q)

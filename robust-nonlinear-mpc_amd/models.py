@@ -124,6 +124,68 @@ def rocket():
     )
 
 
+# Physical constants of the plants in the order of csrc/dynamics.hpp (dyn::ParamDefault) and slsqp_cl_set_plant_params; quadrotor and rocket: the
+# reference's `params` dicts (dyn/quadrotor.py:32-40, dyn/rocket.py:25-39), pendulum: the locals of dyn/pendulum.py:26-44.  tests/test_plant_params_cpu.py
+# holds this table to the library's (slsqp_plant_param_name / slsqp_plant_param_defaults).
+PLANT_PARAMS = {
+    "pendulum": (("m1", 1.0), ("m2", 0.1), ("l", 0.5), ("g", 9.81)),
+    "quadrotor": (("m", 1.0), ("g", 9.81), ("l", 0.15), ("Jx", 0.02), ("Jy", 0.02), ("Jz", 0.04), ("kM", 0.01)),
+    "rocket": (("mass", 1.16), ("gravity_constant", 9.81), ("inertia_xx", 0.00210), ("inertia_yy", 0.1), ("inertia_zz", 0.1), ("thrust_cog_offset", 0.42),
+               ("thrust_magnitude_time_constant", 0.06), ("servo_angle_time_constant", 0.10), ("gimbal_a", 5.0), ("gimbal_b", 35.2), ("gimbal_c", 33.0),
+               ("gimbal_d", 28.0), ("gimbal_e", 35.2)),
+}
+
+
+def _plant_key(model):
+    name = model if isinstance(model, str) else model.name
+    name = "rocket" if name == "rockETH" else name
+    if name not in PLANT_PARAMS:
+        raise ValueError(f"no plant parameters for model {name!r}")
+    return name
+
+
+def plant_param_names(model):
+    """Names of the plant's physical parameters, in the order slsqp_cl_set_plant_params takes them.  model: a ModelData or its name."""
+    return tuple(k for k, _ in PLANT_PARAMS[_plant_key(model)])
+
+
+def plant_param_defaults(model):
+    """The controller's (and, without set_plant_params, the plant's) values, same order."""
+    return np.array([v for _, v in PLANT_PARAMS[_plant_key(model)]], dtype=float)
+
+
+def pack_plant_params(model, B, spec):
+    """Plant parameters as the array set_plant_params passes on: (np,) shared by the batch, or (B,np) per instance.
+    spec: a dict {name: scalar or (B,) array} (unnamed entries keep their defaults; per instance as soon as one entry is an array), an array (np,), or an array (B,np)."""
+    names, dflt = plant_param_names(model), plant_param_defaults(model)
+    n = len(names)
+    if isinstance(spec, dict):
+        unknown = [k for k in spec if k not in names]
+        if unknown:
+            raise ValueError(f"pack_plant_params: unknown parameter(s) {unknown} (known: {list(names)})")
+        vals = {k: np.asarray(v, dtype=float) for k, v in spec.items()}
+        for k, v in vals.items():
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != B):
+                raise ValueError(f"pack_plant_params: {k} must be a scalar or have shape ({B},), got {v.shape}")
+        if not any(v.ndim == 1 for v in vals.values()):
+            P = dflt.copy()
+            for k, v in vals.items():
+                P[names.index(k)] = float(v)
+            return P
+        P = np.tile(dflt, (B, 1))
+        for k, v in vals.items():
+            P[:, names.index(k)] = v
+        return P
+    P = np.ascontiguousarray(np.asarray(spec, dtype=float))
+    if P.ndim == 1 and P.shape[0] == n:
+        return P
+    if P.ndim == 2 and P.shape[1] == n:
+        if P.shape[0] != B:
+            raise ValueError(f"pack_plant_params: a per-instance array needs {B} rows, got {P.shape[0]}")
+        return P
+    raise ValueError(f"pack_plant_params: expected a dict, an array ({n},) or ({B},{n}), got shape {P.shape}")
+
+
 _MODELS = {"pendulum": pendulum, "quadrotor": quadrotor, "rocket": rocket, "rockETH": rocket}
 
 
