@@ -1243,6 +1243,18 @@ __global__ void k_zero_stale(int *stale, int bit, double *arr1, size_t n1, doubl
     __syncthreads();
     if (threadIdx.x == 0) stale[b] &= ~bit;
 }
+// beta[k,j] = 0 (j > k) for the instances whose beta holds a sweep's values (stale bit 8): the sweeps write the entries j <= k only and what lies above the
+// diagonal is still initialize_backoff's eps, where the reference returns the zeros of _backoff_from_phi (fast_SLS_jit.py:141).  Nothing on the device reads
+// those entries (evaluate_dual_eta and the back-off sums stop at j = k), so they are cleared only when the array is handed out.
+__global__ void k_beta_upper_zero(int N, int NI, const int *stale, double *beta) {
+    const int b = blockIdx.x;
+    if (!(stale[b] & 8)) return;
+    double *be = beta + (size_t)b * N * N * NI;
+    for (int o = threadIdx.x; o < N * N * NI; o += blockDim.x) {
+        const int j = (o / NI) % N, k = o / (NI * N);
+        if (j > k) be[o] = 0.0;
+    }
+}
 __global__ void k_copy_int(const int *src, int *dst, int n) { int i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) dst[i] = src[i]; }
 __global__ void k_split_lu(int B, int mb, int nx, const double *l, const double *u, double *lbg, double *ubg, double *x0val) {
     const int m = mb + nx;
@@ -1853,6 +1865,7 @@ extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) 
             hipLaunchKernelGGL(k_zero_stale, dim3(h->B), dim3(256), 0, h->st, h->stale, 2, h->K, (size_t)d.N * (d.N + 1) * d.nu * d.nx, (double *)nullptr, (size_t)0);
             hipLaunchKernelGGL(k_K_broadcast, dim3(h->B), dim3(256), 0, h->st, d.N, d.nu * d.nx, h->stale, h->Kc, h->K);
         }
+        else if (!strcmp(name, "beta")) hipLaunchKernelGGL(k_beta_upper_zero, dim3(h->B), dim3(256), 0, h->st, d.N, d.ni, h->stale, h->beta);
     }
     HIPCHK(hipMemcpyAsync(out, it->second.first, bytes, loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->st));
     HIPCHK(hipStreamSynchronize(h->st));
@@ -2525,7 +2538,10 @@ extern "C" int slsqp_sweep(slsqp_handle *h, const double *eta, const double *eta
     h->t_sweep = ev_ms(h->ev[0], h->ev[1]); h->t_total = ev_ms(h->ev[0], h->ev[2]); h->t_qp = 0;
     const hipMemcpyKind kd = loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     if (K) HIPCHK(hipMemcpyAsync(K, h->K, sizeof(double) * B * d.N * (d.N + 1) * d.nu * d.nx, kd, h->st));
-    if (beta) HIPCHK(hipMemcpyAsync(beta, h->beta, sizeof(double) * B * d.N * d.N * d.ni, kd, h->st));
+    if (beta) {
+        hipLaunchKernelGGL(k_beta_upper_zero, dim3(h->B), dim3(256), 0, h->st, d.N, d.ni, h->stale, h->beta);      // (a handle that has solved before: eps above the diagonal)
+        HIPCHK(hipMemcpyAsync(beta, h->beta, sizeof(double) * B * d.N * d.N * d.ni, kd, h->st));
+    }
     if (beta_f) HIPCHK(hipMemcpyAsync(beta_f, h->beta_f, sizeof(double) * B * (d.N + 1) * d.ni_f, kd, h->st));
     if (backoff) HIPCHK(hipMemcpyAsync(backoff, h->backoff, sizeof(double) * B * d.N * d.ni, kd, h->st));
     if (backoff_f) HIPCHK(hipMemcpyAsync(backoff_f, h->backoff_f, sizeof(double) * B * d.ni_f, kd, h->st));

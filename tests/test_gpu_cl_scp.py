@@ -20,18 +20,21 @@ def _final(cl):
     return {k: cl.f.get(k, shp) for k, shp in (("x_meas", (m.nx,)), ("nominal_x", (N + 1, m.nx)), ("nominal_u", (N, m.nu)), ("primal_vec", (cl.f.n,)))}
 
 
-def _make(m, N, B, rti, rti_steps, tune=None):
+def _make(m, N, B, rti, rti_steps, tune=None, setup=None):
+    """tune(opts) adjusts the handle's options, setup(cl) anything else on the freshly constructed loop (tests/test_gpu_sweep_routes.py: its E)."""
     from robust_nonlinear_mpc_amd import ClosedLoopMPC
     cl = ClosedLoopMPC(m, N, B, rti=rti, fast_sls_rti_steps=rti_steps)
     if tune:
         tune(cl.f.opts)
+    if setup:
+        setup(cl)
     return cl
 
 
-def _stepwise(m, N, B, steps, x0, W, rti, rti_steps, tune=None, **reset_kw):
-    """The reference side: one slsqp_cl_step per MPC step, qp_stats read after each."""
+def _stepwise(m, N, B, steps, x0, W, rti, rti_steps, tune=None, setup=None, inspect=None, **reset_kw):
+    """The reference side: one slsqp_cl_step per MPC step, qp_stats read after each.  inspect(cl) sees the loop after its last step, before it is closed."""
     L = __import__("robust_nonlinear_mpc_amd")._lib
-    cl = _make(m, N, B, rti, rti_steps, tune)
+    cl = _make(m, N, B, rti, rti_steps, tune, setup)
     assert L.load().slsqp_cl_log(cl.f.h, steps) == 0
     cl.reset(x0, **reset_kw)
     stats = []
@@ -41,12 +44,14 @@ def _stepwise(m, N, B, steps, x0, W, rti, rti_steps, tune=None, **reset_kw):
     ref = cl._log_result(steps, np.zeros((steps, 1)), np.zeros((steps, 1)), np.zeros((steps, 1)))
     ref["qp_stats"] = np.stack(stats, axis=1)
     fin = _final(cl)
+    if inspect:
+        inspect(cl)
     cl.close()
     return ref, fin
 
 
-def _persistent(m, N, B, steps, x0, W, rti, rti_steps, tune=None, waves=None, **reset_kw):
-    cl = _make(m, N, B, rti, rti_steps, tune)
+def _persistent(m, N, B, steps, x0, W, rti, rti_steps, tune=None, waves=None, setup=None, **reset_kw):
+    cl = _make(m, N, B, rti, rti_steps, tune, setup)
     if waves is not None:
         os.environ["SLSQP_LOOP_WAVES"] = str(waves)
     try:
