@@ -59,6 +59,7 @@ struct slsqp_handle {
     int *cl_stepno = nullptr, *cl_lag = nullptr, *cl_begin = nullptr, *cl_runm = nullptr, *cl_done = nullptr, *cl_skipb = nullptr, *cl_skip_begin = nullptr, *qplog = nullptr;
     double *call_ids = nullptr, *cl_W = nullptr; size_t cl_W_doubles = 0; unsigned long long *t0word = nullptr; int qplog_steps = 0, qplog_cap = 0, *qplog_nsolves = nullptr;      // qplog: capacity in steps, steps of the current run; solves per (instance, step) (k_cl_loop_scp)
     int *clq_slots = nullptr, *clq_ctl = nullptr; unsigned clq_cap = 0; int cl_loop_waves = 0; double cl_loop_ms = 0.0; unsigned long long *cl_busy = nullptr, *cl_tbegin = nullptr, cl_busy_host[16] = {};      // k_cl_loop: instance FIFO (slots; head, tail, avail, err), wave life-time counters
+    unsigned char *loop_blk = nullptr; std::vector<unsigned char> loop_blk_host;      // the persistent kernels' argument block (ScpLoopArgs) of this handle and what the host last wrote to it
     bool cl_round = false; unsigned long long cl_budget = 0; int cl_total_steps = 0; unsigned cl_cut_count = 0xFFFFFFFFu;
     unsigned long long *chain_times = nullptr, *chain_times_host = nullptr;   // (B,4) in-kernel wall-clock ticks per instance; pinned copy of instance 0's
     int *qp_diag = nullptr;     // QP_DIAG_SPAN builds only
@@ -187,7 +188,7 @@ extern "C" slsqp_handle *slsqp_create(const slsqp_dims *d, int batch, int device
     rc |= dalloc(h->owned, &h->mapA, (size_t)N * nx * nx); rc |= dalloc(h->owned, &h->mapB, (size_t)N * nx * nu);
     rc |= dalloc(h->owned, &h->inst_launches, (size_t)8); rc |= dalloc(h->owned, &h->chain_times, B * 4);
     rc |= dalloc(h->owned, &h->cl_stepno, B); rc |= dalloc(h->owned, &h->cl_lag, B); rc |= dalloc(h->owned, &h->cl_begin, B); rc |= dalloc(h->owned, &h->cl_runm, B); rc |= dalloc(h->owned, &h->cl_done, B);
-    { unsigned cap = 1; while (cap < 4u * (unsigned)B) cap <<= 1; h->clq_cap = cap; rc |= dalloc(h->owned, &h->clq_slots, (size_t)cap); rc |= dalloc(h->owned, &h->clq_ctl, (size_t)8); rc |= dalloc(h->owned, &h->cl_busy, (size_t)16); rc |= dalloc(h->owned, &h->cl_tbegin, (size_t)B); }
+    { unsigned cap = 1; while (cap < 4u * (unsigned)B) cap <<= 1; h->clq_cap = cap; rc |= dalloc(h->owned, &h->clq_slots, (size_t)cap); rc |= dalloc(h->owned, &h->clq_ctl, (size_t)8); rc |= dalloc(h->owned, &h->cl_busy, (size_t)16); rc |= dalloc(h->owned, &h->cl_tbegin, (size_t)B); rc |= dalloc(h->owned, &h->loop_blk, (size_t)4096); }
     rc |= dalloc(h->owned, &h->cl_skipb, B); rc |= dalloc(h->owned, &h->call_ids, B); rc |= dalloc(h->owned, &h->t0word, (size_t)2); rc |= dalloc(h->owned, &h->ct_part, B * (N + 1)); rc |= dalloc(h->owned, &h->cost_tube, B);
     rc |= dalloc(h->owned, &h->lin_stage, B * N * 3 * nx); rc |= dalloc(h->owned, &h->lin_tape, B * N * 4 * dyn::NT_MAX); rc |= dalloc(h->owned, &h->Kc, B * N * nu * nx); rc |= dalloc(h->owned, &h->Aclc, B * N * nx * nx); rc |= dalloc(h->owned, &h->qpstat, B * 16); rc |= dalloc(h->owned, &h->Gd, (size_t)ni * (nx + nu)); rc |= dalloc(h->owned, &h->Gfd, (size_t)nif * nx); h->general_G = false; h->beta_inited = false; rc |= dalloc(h->owned, &h->stale, B); rc |= dalloc(h->owned, &h->pinf, B); rc |= dalloc(h->owned, &h->scp_upd, B); h->t_jac = 0;
     h->log_steps = 0; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr;
@@ -575,7 +576,8 @@ __device__ __forceinline__ int after_qp_wave(const AfterQpArgs &a, int b, int la
 // followed by the interior point: 50-90 block solves against a mean of 10), so the step pays max(QP #1) + max(QP #2).  Here an instance that is
 // slow in one QP only delays itself and the step pays max over the instances of their own sums.  Same device functions, same arithmetic, same bits.
 struct ChainArgs {
-    QpArgs q1, q2;
+    QpArgs q;                       // QP #1's arguments; QP #2's are these with the three ints of q2 (qp_second_args)
+    Qp2Ints q2;
     AfterQpArgs aq;
     SweepSharedArgs sw;
     TightenArgs ta;
@@ -592,11 +594,16 @@ struct ChainArgs {
     int *qplog; const int *stepno; int log_steps;      // (B, log_steps, 16) per-step copy of the instance's qp_stats, entry stepno[b]
     double *x0vlog;                 // (B, log_steps, 2) per-step copy of the instance's x0_viol, kept wherever qplog is
 };
-template <int NX, int NU>
-__device__ __forceinline__ int rti_chain_dev(const ChainArgs &c, int b, int lane, double *sm) {
+// BLK: c_ lies in the argument block of a persistent closed-loop kernel (args_here, slsqp_kernels.hpp): the head of the chain, of each pass, of the
+// part behind QP #1 and of the tail read what they use afresh.
+template <int NX, int NU, bool BLK = false>
+__device__ __forceinline__ int rti_chain_dev(const ChainArgs &c_, int b, int lane, double *sm) {
+    const ChainArgs *cp = &c_;
     unsigned long long t0 = wall_clock64(), t1 = t0, t2 = t0, deadline = ~0ULL;
     int lg = 0;
-    if (c.lag) {
+    const int have_lag = args_here<BLK>(cp).lag ? 1 : 0;
+    if (have_lag) {
+        const ChainArgs &c = args_here<BLK>(cp);
         lg = __builtin_amdgcn_readfirstlane(c.lag[b]);
         unsigned long long first = 0ULL;
         if (lane == 0) { first = atomicCAS(c.t0word, 0ULL, t0); if (first == 0ULL) first = t0; }
@@ -608,8 +615,15 @@ __device__ __forceinline__ int rti_chain_dev(const ChainArgs &c, int b, int lane
 #pragma unroll 1
     for (int pass = (lg == 2 ? 1 : 0); pass < 2; pass++) {
         asm volatile("" : "+v"(lane));
-        fin = __builtin_amdgcn_readfirstlane(qp_solve_dev<NX, NU, false>(pass == 0 ? c.q1 : c.q2, b, lane, sm, c.max_ticks, (lg == pass + 1) ? 1 : 0, deadline, c.lag ? c.fin_count : nullptr, c.cut_count));
+        {
+            const ChainArgs &c = args_here<BLK>(cp);
+            Qp2Ints qi{c.q.warm, c.q.stat_slot, c.q.snap_use};
+            if (pass) qi = c.q2;
+            if constexpr (BLK) fin = __builtin_amdgcn_readfirstlane(qp_solve_dev<NX, NU, false, true>(c.q, b, lane, sm, c.max_ticks, (lg == pass + 1) ? 1 : 0, deadline, c.lag ? c.fin_count : nullptr, c.cut_count, qi));
+            else fin = __builtin_amdgcn_readfirstlane(qp_solve_dev<NX, NU, false>(qp_second_args(c.q, qi), b, lane, sm, c.max_ticks, (lg == pass + 1) ? 1 : 0, deadline, c.lag ? c.fin_count : nullptr, c.cut_count));
+        }
         wla::wsync_mem();
+        const ChainArgs &c = args_here<BLK>(cp);
         if (!fin) { if (lane == 0) c.lag[b] = pass + 1; break; }      // suspended at the deadline: the next launch resumes this solve
         if (pass == 1) break;
         t1 = wall_clock64();
@@ -632,21 +646,22 @@ __device__ __forceinline__ int rti_chain_dev(const ChainArgs &c, int b, int lane
         t2 = wall_clock64();
     }
     if (!fin) return 0;
+    const ChainArgs &c = args_here<BLK>(cp);
     if (lane == 0) {
         if (c.active && !c.active[b]) c.success[b] = 0;
         else c.success[b] = (!c.infeas[b]) || c.success[b];           // fast_SLS_jit.py:295 (k_finish, RTI)
         if (c.times) { const unsigned long long t3 = wall_clock64(); unsigned long long *t = c.times + (size_t)b * 4; t[0] = t1 - t0; t[1] = t2 - t1; t[2] = t3 - t2; t[3] = t3 - t0; }
         if (c.lag) { c.lag[b] = 0; c.done[b] = 1; atomicAdd(c.fin_count, 1u); }
     }
-    if (c.qplog && lane < 16) c.qplog[((size_t)b * c.log_steps + min(c.stepno[b], c.log_steps - 1)) * 16 + lane] = c.q1.qpstat[(size_t)b * 16 + lane];
+    if (c.qplog && lane < 16) c.qplog[((size_t)b * c.log_steps + min(c.stepno[b], c.log_steps - 1)) * 16 + lane] = c.q.qpstat[(size_t)b * 16 + lane];
     if (c.qplog && lane >= 16 && lane < 18)      // per-step copy of x0_viol; a QP that took no part (qp_stats status -1) records 0
-        c.x0vlog[((size_t)b * c.log_steps + min(c.stepno[b], c.log_steps - 1)) * 2 + lane - 16] = c.q1.qpstat[(size_t)b * 16 + (lane - 16) * 8 + 6] == -1 ? 0.0 : x0_record(c.q1.kkt, c.q1.B)[2 + (size_t)b * 2 + lane - 16];
+        c.x0vlog[((size_t)b * c.log_steps + min(c.stepno[b], c.log_steps - 1)) * 2 + lane - 16] = c.q.qpstat[(size_t)b * 16 + (lane - 16) * 8 + 6] == -1 ? 0.0 : x0_record(c.q.kkt, c.q.B)[2 + (size_t)b * 2 + lane - 16];
     return 1;
 }
 template <int NX, int NU>
 __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_rti_chain(ChainArgs c) {
     int b = blockIdx.x, lane = threadIdx.x;
-    if (b >= c.q1.B) return;
+    if (b >= c.q.B) return;
     if (c.runm && !c.runm[b]) return;
     extern __shared__ double sm[];
     rti_chain_dev<NX, NU>(c, b, lane, sm);
@@ -734,10 +749,22 @@ struct LoopArgs {
     ClQueue Q;
     unsigned long long *busy, *t_begin;      // busy[0] sum over the MPC steps of the time a wave spent on them (100 MHz ticks), [2] MPC steps run; t_begin (B): start of the instance's current step
 };
+// The argument block of the six persistent kernels (k_cl_loop* use L only; the fields behind it are k_cl_loop_scp*'s, described there).  It lives in
+// device memory, one block per handle (slsqp_handle::loop_blk), written by cl_run_persistent on the handle's stream before every launch; the kernels
+// take its address and read it through args_here<true> (slsqp_kernels.hpp): the heads of cl_step_begin, of the chain's parts, of cl_step_end and of
+// every part of qp_solve_dev's tick loop each read the fields they use.  What may go into it: anything -- a field costs a scalar load where it is
+// used, not a register for the life of the kernel.
+struct ScpLoopArgs {
+    LoopArgs L;
+    int max_it, converge, rti_steps;
+    int *nsolves;
+};
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
 template <int MODEL, bool REF = false>
-__device__ CLW_FN void cl_step_begin(const LoopArgs &L, int b, int lane, const RefArgs *rf = nullptr) {
+__device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const RefArgs *rf = nullptr) {
+    const LoopArgs *Lp = &L_;
+    const LoopArgs &L = args_here<true>(Lp);
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int s = L.stepno[b];
     if (lane == 0) L.t_begin[b] = wall_clock64();
@@ -768,7 +795,9 @@ __device__ CLW_FN void cl_step_begin(const LoopArgs &L, int b, int lane, const R
 }
 // nominal += delta, primal infeasibility, log entry, plant + noise, step counter; returns the instance's new step count while it has steps left, else 0
 template <int MODEL, bool PP = false>
-__device__ CLW_FN int cl_step_end(const LoopArgs &L, int b, int lane, const PlantArgs *pa = nullptr) {
+__device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const PlantArgs *pa = nullptr) {
+    const LoopArgs *Lp = &L_;
+    const LoopArgs &L = args_here<true>(Lp);
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int s = L.stepno[b];
 #ifdef CL_LOOP_STAMP
@@ -797,18 +826,19 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L, int b, int lane, const Plan
     return (s + 1 < L.steps) ? s + 1 : 0;
 }
 template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(LoopArgs L) {
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const ScpLoopArgs *blk) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     int lane = threadIdx.x;
     extern __shared__ double sm[];
     int b = -1;
 #ifdef CL_LOOP_STAMP
     const unsigned long long tw0_ = wall_clock64();
-    if (lane == 0) atomicMin(L.busy + 14, tw0_);
+    if (lane == 0) atomicMin(args_here<true>(blk).L.busy + 14, tw0_);
 #endif
 #pragma unroll 1
     for (;;) {
         asm volatile("" : "+v"(lane));
+        const LoopArgs &L = args_here<true>(blk).L;
         if (b < 0) {
 #ifdef CL_LOOP_STAMP
             const unsigned long long tp_ = wall_clock64();
@@ -823,37 +853,38 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(LoopA
         cl_step_begin<MODEL>(L, b, lane);
         b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
         asm volatile("" : "+v"(lane));
-        rti_chain_dev<NX, NU>(L.c, b, lane, sm);
+        rti_chain_dev<NX, NU, true>(L.c, b, lane, sm);
         wla::wsync_mem();
         asm volatile("" : "+v"(lane));
         const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL>(L, b, lane));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
+        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
         // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
         // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
         // waves are shared fairly among the instances that are level
-        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
-        if (behind && L.keep_laggards) continue;
+        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
+        if (behind && Lt.keep_laggards) continue;
 #ifdef CL_LOOP_STAMP
         const unsigned long long tq_ = wall_clock64();
 #endif
-        if (L.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
-        clq_push(L.Q, b, lane);
+        if (Lt.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
+        clq_push(Lt.Q, b, lane);
         b = -1;
 #ifdef CL_LOOP_STAMP
         if (lane == 0) atomicAdd(L.busy + 12, wall_clock64() - tq_);
 #endif
     }
 #ifdef CL_LOOP_STAMP
-    if (lane == 0) { const unsigned long long te_ = wall_clock64(); atomicAdd(L.busy + 13, te_ - tw0_); atomicMax(L.busy + 15, te_); atomicAdd(L.busy + 1, 1ULL); }
+    if (lane == 0) { const LoopArgs &L = args_here<true>(blk).L; const unsigned long long te_ = wall_clock64(); atomicAdd(L.busy + 13, te_ - tw0_); atomicMax(L.busy + 15, te_); atomicAdd(L.busy + 1, 1ULL); }
 #endif
 }
 // The same loop for a handle with a reference (slsqp_cl_set_reference): the only difference is the tracked linear cost of cl_step_begin.  A kernel of
 // its own, so that k_cl_loop keeps its arguments and its code object (profiles/r07/resource_usage.txt); keep the two bodies in step --
 // tests/test_gpu_reference.py holds this one to the step-by-step loop bit for bit.  (No CL_LOOP_STAMP instrumentation here.)
 template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_ref(LoopArgs L, RefArgs rf) {
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_ref(const ScpLoopArgs *blk, RefArgs rf) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     int lane = threadIdx.x;
     extern __shared__ double sm[];
@@ -861,6 +892,7 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_ref(L
 #pragma unroll 1
     for (;;) {
         asm volatile("" : "+v"(lane));
+        const LoopArgs &L = args_here<true>(blk).L;
         if (b < 0) {
             b = clq_pop(L.Q, lane);
             if (b < 0) break;
@@ -869,20 +901,21 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_ref(L
         cl_step_begin<MODEL, true>(L, b, lane, &rf);
         b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
         asm volatile("" : "+v"(lane));
-        rti_chain_dev<NX, NU>(L.c, b, lane, sm);
+        rti_chain_dev<NX, NU, true>(L.c, b, lane, sm);
         wla::wsync_mem();
         asm volatile("" : "+v"(lane));
         const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL>(L, b, lane));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
+        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
         // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
         // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
         // waves are shared fairly among the instances that are level
-        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
-        if (behind && L.keep_laggards) continue;
-        if (L.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
-        clq_push(L.Q, b, lane);
+        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
+        if (behind && Lt.keep_laggards) continue;
+        if (Lt.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
+        clq_push(Lt.Q, b, lane);
         b = -1;
     }
 }
@@ -892,7 +925,7 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_ref(L
 // reference passes one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference.  Keep the bodies in step --
 // tests/test_gpu_plant_params.py holds this one to the step-by-step loop bit for bit.
 template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_pp(LoopArgs L, RefArgs rf, PlantArgs pa) {
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_pp(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     int lane = threadIdx.x;
     extern __shared__ double sm[];
@@ -900,6 +933,7 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_pp(Lo
 #pragma unroll 1
     for (;;) {
         asm volatile("" : "+v"(lane));
+        const LoopArgs &L = args_here<true>(blk).L;
         if (b < 0) {
             b = clq_pop(L.Q, lane);
             if (b < 0) break;
@@ -908,20 +942,21 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_pp(Lo
         cl_step_begin<MODEL, true>(L, b, lane, &rf);
         b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
         asm volatile("" : "+v"(lane));
-        rti_chain_dev<NX, NU>(L.c, b, lane, sm);
+        rti_chain_dev<NX, NU, true>(L.c, b, lane, sm);
         wla::wsync_mem();
         asm volatile("" : "+v"(lane));
         const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, true>(L, b, lane, &pa));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
+        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
         // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
         // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
         // waves are shared fairly among the instances that are level
-        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
-        if (behind && L.keep_laggards) continue;
-        if (L.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
-        clq_push(L.Q, b, lane);
+        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
+        if (behind && Lt.keep_laggards) continue;
+        if (Lt.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
+        clq_push(Lt.Q, b, lane);
         b = -1;
     }
 }
@@ -936,14 +971,11 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_pp(Lo
 //   converge mode (rti <= 0): an instance leaves as soon as cl_scp_update_wave clears its scp_active (converged or failed) -- the batch-wide
 //     launches go on until the last instance has left and, for the ones that left earlier, only rewrite their qp_stats slots as "took no part".
 //     nsolves (B, steps) keeps the number of solves each step of each instance ran, from which k_cl_qplog_masked reproduces that afterwards.
-struct ScpLoopArgs {
-    LoopArgs L;
-    int max_it, converge, rti_steps;
-    int *nsolves;
-};
 // shift + solver reset past the first step, SCP flags of the step (slsqp_cl_step's preamble)
 template <int MODEL>
-__device__ CLW_FN void cl_scp_step_begin(const LoopArgs &L, int b, int lane) {
+__device__ CLW_FN void cl_scp_step_begin(const LoopArgs &L_, int b, int lane) {
+    const LoopArgs *Lp = &L_;
+    const LoopArgs &L = args_here<true>(Lp);
     const int s = L.stepno[b];
     if (lane == 0) L.t_begin[b] = wall_clock64();
     if (s > 0) {
@@ -958,7 +990,9 @@ __device__ CLW_FN void cl_scp_step_begin(const LoopArgs &L, int b, int lane) {
 }
 // start of SCP iteration ii: linearisation (instances still iterating), x0 pin, call id, solve start
 template <int MODEL, bool REF = false>
-__device__ CLW_FN void cl_scp_iter_begin(const LoopArgs &L, int b, int lane, int ii, const RefArgs *rf = nullptr) {
+__device__ CLW_FN void cl_scp_iter_begin(const LoopArgs &L_, int b, int lane, int ii, const RefArgs *rf = nullptr) {
+    const LoopArgs *Lp = &L_;
+    const LoopArgs &L = args_here<true>(Lp);
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int act = __builtin_amdgcn_readfirstlane(L.scp_active[b]);
     if (ii == 0 || act) lin_wave<MODEL, REF>(L.lin, L.ba, b, lane, rf, REF ? L.stepno[b] : 0);      // (REF: every iteration of the step uses the window of the instance's own step count)
@@ -970,7 +1004,9 @@ __device__ CLW_FN void cl_scp_iter_begin(const LoopArgs &L, int b, int lane, int
 }
 // end of SCP iteration ii: nominal += delta / the instance leaves the loop, primal infeasibility; returns 1 while the instance is still iterating
 template <int MODEL>
-__device__ CLW_FN int cl_scp_iter_end(const LoopArgs &L, int b, int lane, int ii, int converge) {
+__device__ CLW_FN int cl_scp_iter_end(const LoopArgs &L_, int b, int lane, int ii, int converge) {
+    const LoopArgs *Lp = &L_;
+    const LoopArgs &L = args_here<true>(Lp);
     ScpArgs sa = L.sa;
     sa.ii = ii; sa.converge = converge;
     cl_scp_update_wave(L.cl, sa, b, lane);
@@ -981,7 +1017,9 @@ __device__ CLW_FN int cl_scp_iter_end(const LoopArgs &L, int b, int lane, int ii
 }
 // log entries, plant step + noise, step counter; returns the instance's new step count while it has steps left, else 0
 template <int MODEL, bool PP = false>
-__device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S, int b, int lane, int nsolves, const PlantArgs *pa = nullptr) {
+__device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S_, int b, int lane, int nsolves, const PlantArgs *pa = nullptr) {
+    const ScpLoopArgs *Sp = &S_;
+    const ScpLoopArgs &S = args_here<true>(Sp);
     const LoopArgs &L = S.L;
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int s = L.stepno[b];
@@ -990,8 +1028,8 @@ __device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S, int b, int lane, int
         for (int o = lane; o < per; o += 64) cl_log_item(L.lg, b, o);
     }
     if (L.c.qplog && s < L.c.log_steps) {
-        if (lane < 16) L.c.qplog[((size_t)b * L.c.log_steps + s) * 16 + lane] = L.c.q1.qpstat[(size_t)b * 16 + lane];
-        else if (lane < 18) L.c.x0vlog[((size_t)b * L.c.log_steps + s) * 2 + lane - 16] = L.c.q1.qpstat[(size_t)b * 16 + (lane - 16) * 8 + 6] == -1 ? 0.0 : x0_record(L.c.q1.kkt, L.c.q1.B)[2 + (size_t)b * 2 + lane - 16];
+        if (lane < 16) L.c.qplog[((size_t)b * L.c.log_steps + s) * 16 + lane] = L.c.q.qpstat[(size_t)b * 16 + lane];
+        else if (lane < 18) L.c.x0vlog[((size_t)b * L.c.log_steps + s) * 2 + lane - 16] = L.c.q.qpstat[(size_t)b * 16 + (lane - 16) * 8 + 6] == -1 ? 0.0 : x0_record(L.c.q.kkt, L.c.q.B)[2 + (size_t)b * 2 + lane - 16];
         if (lane == 0) S.nsolves[(size_t)b * L.c.log_steps + s] = nsolves;
     }
     if (lane == 0) {
@@ -1006,21 +1044,24 @@ __device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S, int b, int lane, int
 // arguments launch_qp builds for it: the first one q1's (warm per opts.warm_start, slot 0, no iterate copy to restart from), the middle ones warm,
 // slot 0, restart allowed, the last one q2's; the horizon shift only reaches the first and the last QP of the first solve after the shift
 template <int NX, int NU>
-__device__ __forceinline__ void sls_solve_dev(const ChainArgs &c, int b, int lane, double *sm, int rti_steps, int shifted) {
+__device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int lane, double *sm, int rti_steps, int shifted) {
+    const ChainArgs *cp = &c_;
 #pragma unroll 1
     for (int i = 0; i <= rti_steps; i++) {
         asm volatile("" : "+v"(lane));
         {
-            QpArgs q = c.q1;
-            q.warm = i > 0 ? 1 : c.q1.warm;
+            const ChainArgs &c = args_here<true>(cp);
+            QpArgs q = c.q;
+            q.warm = i > 0 ? 1 : c.q.warm;
             q.stat_slot = i == rti_steps ? 1 : 0;
             q.snap_use = i > 0 ? c.q2.snap_use : 0;
-            q.warm_shift = (shifted && (i == 0 || i == rti_steps)) ? c.q1.warm_shift : 0;
+            q.warm_shift = (shifted && (i == 0 || i == rti_steps)) ? c.q.warm_shift : 0;
             qp_solve_dev<NX, NU, false>(q, b, lane, sm, c.max_ticks);
         }
         wla::wsync_mem();
         if (i == rti_steps) break;
         asm volatile("" : "+v"(lane));
+        const ChainArgs &c = args_here<true>(cp);
         AfterQpArgs aq = c.aq;
         aq.first_iter = i == 0 ? 1 : 0; aq.ea.first_iter = aq.first_iter;
         const int m = __builtin_amdgcn_readfirstlane(after_qp_wave(aq, b, lane));
@@ -1047,6 +1088,7 @@ __device__ __forceinline__ void sls_solve_dev(const ChainArgs &c, int b, int lan
         tighten_dev(c.ta, b, lane, 64);
         wla::wsync_mem();
     }
+    const ChainArgs &c = args_here<true>(cp);
     if (lane == 0) {
         if (c.active && !c.active[b]) c.success[b] = 0;
         else c.success[b] = (!c.infeas[b]) || c.success[b];           // fast_SLS_jit.py:295 (k_finish, RTI)
@@ -1054,15 +1096,16 @@ __device__ __forceinline__ void sls_solve_dev(const ChainArgs &c, int b, int lan
     wla::wsync_mem();
 }
 template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(ScpLoopArgs S) {
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(const ScpLoopArgs *blk) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    const LoopArgs &L = S.L;
     int lane = threadIdx.x;
     extern __shared__ double sm[];
     int b = -1;
 #pragma unroll 1
     for (;;) {
         asm volatile("" : "+v"(lane));
+        const ScpLoopArgs &S = args_here<true>(blk);
+        const LoopArgs &L = S.L;
         if (b < 0) {
             b = clq_pop(L.Q, lane);
             if (b < 0) break;
@@ -1088,25 +1131,27 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(S
         const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL>(S, b, lane, nsolves));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
-        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
-        if (behind && L.keep_laggards) continue;
-        if (L.fence & 2) __threadfence();
-        clq_push(L.Q, b, lane);
+        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
+        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
+        if (behind && Lt.keep_laggards) continue;
+        if (Lt.fence & 2) __threadfence();
+        clq_push(Lt.Q, b, lane);
         b = -1;
     }
 }
 // k_cl_loop_scp for a handle with a reference: as k_cl_loop_ref above, the tracked linear cost in cl_scp_iter_begin is the only difference
 template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_ref(ScpLoopArgs S, RefArgs rf) {
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_ref(const ScpLoopArgs *blk, RefArgs rf) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    const LoopArgs &L = S.L;
     int lane = threadIdx.x;
     extern __shared__ double sm[];
     int b = -1;
 #pragma unroll 1
     for (;;) {
         asm volatile("" : "+v"(lane));
+        const ScpLoopArgs &S = args_here<true>(blk);
+        const LoopArgs &L = S.L;
         if (b < 0) {
             b = clq_pop(L.Q, lane);
             if (b < 0) break;
@@ -1132,25 +1177,27 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_r
         const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL>(S, b, lane, nsolves));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
-        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
-        if (behind && L.keep_laggards) continue;
-        if (L.fence & 2) __threadfence();
-        clq_push(L.Q, b, lane);
+        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
+        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
+        if (behind && Lt.keep_laggards) continue;
+        if (Lt.fence & 2) __threadfence();
+        clq_push(Lt.Q, b, lane);
         b = -1;
     }
 }
 // k_cl_loop_scp_ref for a handle with plant parameters: as k_cl_loop_pp above, the plant step of cl_scp_step_end is the only difference
 template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_pp(ScpLoopArgs S, RefArgs rf, PlantArgs pa) {
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_pp(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    const LoopArgs &L = S.L;
     int lane = threadIdx.x;
     extern __shared__ double sm[];
     int b = -1;
 #pragma unroll 1
     for (;;) {
         asm volatile("" : "+v"(lane));
+        const ScpLoopArgs &S = args_here<true>(blk);
+        const LoopArgs &L = S.L;
         if (b < 0) {
             b = clq_pop(L.Q, lane);
             if (b < 0) break;
@@ -1176,11 +1223,12 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_p
         const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL, true>(S, b, lane, nsolves, &pa));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
-        const unsigned long long done_steps = __hip_atomic_load(L.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)L.cl.B < done_steps) ? 1 : 0);
-        if (behind && L.keep_laggards) continue;
-        if (L.fence & 2) __threadfence();
-        clq_push(L.Q, b, lane);
+        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
+        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
+        if (behind && Lt.keep_laggards) continue;
+        if (Lt.fence & 2) __threadfence();
+        clq_push(Lt.Q, b, lane);
         b = -1;
     }
 }
@@ -1364,6 +1412,7 @@ static void set_x0_tol(slsqp_handle *h, double tol) {
 static QpArgs make_qp_args(slsqp_handle *h, const int *run, const slsqp_opts *o, int warm, const double *prox = nullptr, int stat_slot = 0, int snap_take = 0, int snap_use = 0,
                            int warm_shift = 0) {
     QpArgs a;
+    memset(&a, 0, sizeof a);      // (padding too: the closed-loop kernels' argument block is compared and copied as bytes)
     a.qpstat = h->qpstat; a.stat_slot = stat_slot; a.diag = h->qp_diag;
     set_x0_tol(h, prox ? 0.0 : h->x0_box_tol);      // (prox: the nominal initialiser's QPs stay strict)
     static const double snap_mu = getenv("SLSQP_SNAP_MU") ? atof(getenv("SLSQP_SNAP_MU")) : 1e-3;
@@ -1524,14 +1573,18 @@ static int launch_sweep(slsqp_handle *h, const int *run, const double *eta, cons
     return -1;
 }
 
+// what the last QP of a call changes in the first one's arguments: warm, statistics slot 1, restart from the first QP's iterate copy (make_qp_args
+// with warm = 1, stat_slot = 1, snap_use = 1 and everything else as for the first)
+static Qp2Ints qp_second_ints(const slsqp_opts &o) { return Qp2Ints{1, 1, o.ipm_restart ? 1 : 0}; }
 // arguments of one RTI chain (k_rti_chain / k_cl_loop): QP #1, what follows it, the sweep, the tightening, QP #2
 static int qp_max_ticks(const QpArgs &a, int max_iter);
 static ChainArgs make_chain_args(slsqp_handle *h, const slsqp_opts &o, const int *active, int wshift) {
     const slsqp_dims &d = h->d;
     const int B = h->B;
     ChainArgs c;
-    c.q1 = make_qp_args(h, h->alive, &o, o.warm_start ? 1 : 0, nullptr, 0, 1, 0, wshift);
-    c.q2 = make_qp_args(h, h->alive, &o, 1, nullptr, 1, 1, 1, wshift);
+    memset(&c, 0, sizeof c);
+    c.q = make_qp_args(h, h->alive, &o, o.warm_start ? 1 : 0, nullptr, 0, 1, 0, wshift);
+    c.q2 = qp_second_ints(o);
     EtaArgs ea{B, d.N, d.nx, d.ni, d.ni_f, h->dual, h->beta, h->beta_f, h->alive, h->eta, h->eta_f, o.eps_backoff, h->stale, 1};
     ConvArgs ca{B, h->n, h->primal, h->prev_primal, h->has_prev, h->alive, h->conv, o.conv_tol};
     c.aq = AfterQpArgs{B, 1, 1, h->status, active, h->alive, h->infeas, h->mask, h->success, h->itnum, h->counter, h->stale, h->conv, ea, ca, h->beta, h->beta_f};
@@ -1541,7 +1594,7 @@ static ChainArgs make_chain_args(slsqp_handle *h, const slsqp_opts &o, const int
     c.sw = SweepSharedArgs{sa, h->Kc, h->Aclc, h->stale};
     c.ta = TightenArgs{B, d.N, d.nx, d.nu, d.ni, d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, h->mask, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, 1, h->ct_part, h->cost_tube};
     c.active = active; c.success = h->success; c.infeas = h->infeas; c.times = h->chain_times;
-    c.max_ticks = qp_max_ticks(c.q1, o.qp_max_iter);
+    c.max_ticks = qp_max_ticks(c.q, o.qp_max_iter);
     c.lag = nullptr; c.runm = nullptr; c.done = nullptr; c.t0word = nullptr; c.budget = 0; c.qplog = nullptr; c.x0vlog = nullptr; c.stepno = nullptr; c.log_steps = 0; c.fin_count = nullptr; c.cut_count = 0xFFFFFFFFu;
     return c;
 }
@@ -2178,7 +2231,7 @@ __global__ void k_cl_begin_flags(int B, const int *begin, int *scp_success, int 
 }
 // the persistent closed-loop launch (k_cl_loop): as many waves as the GPU holds at the kernel's occupancy (or as there are instances)
 template <int MODEL>
-static int launch_loop_t(slsqp_handle *h, LoopArgs &L, const ScpLoopArgs *S = nullptr) {
+static int launch_loop_t(slsqp_handle *h, bool S) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     const size_t lds = sizeof(double) * std::max({(size_t)qp_lds_doubles<NX, NU>(h->d.N), (size_t)(2 * h->n + 8), (size_t)sweep_lds_doubles<NX, NU>(), (size_t)sweep_prop_lds_doubles<NX, NU>()});
     int cu = 0;
@@ -2187,43 +2240,40 @@ static int launch_loop_t(slsqp_handle *h, LoopArgs &L, const ScpLoopArgs *S = nu
     const int slots = env_waves > 0 ? env_waves : cu * 4 * QP_PERSIST_WAVES_PER_SIMD;
     const int grid = std::max(1, std::min(h->B, slots));
     h->cl_loop_waves = grid;
+    const ScpLoopArgs *blk = (const ScpLoopArgs *)h->loop_blk;
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     hipEventRecord(h->ev[8], h->st);
     if (h->pp_P) {      // plant parameters: the kernels that take them (written on the tracked bodies: without a reference, one row of zeros)
         const RefArgs rf = h->ref_T > 0 ? ref_args(h) : RefArgs{h->pp_zero_ref, 1, 0};
         const PlantArgs pa = plant_args(h);
-        if (S) hipLaunchKernelGGL((k_cl_loop_scp_pp<MODEL>), dim3(grid), dim3(64), lds, h->st, *S, rf, pa);
-        else hipLaunchKernelGGL((k_cl_loop_pp<MODEL>), dim3(grid), dim3(64), lds, h->st, L, rf, pa);
+        if (S) hipLaunchKernelGGL((k_cl_loop_scp_pp<MODEL>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);
+        else hipLaunchKernelGGL((k_cl_loop_pp<MODEL>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);
     }
     else if (h->ref_T > 0) {      // tracked cost: the kernels that take the reference
         const RefArgs rf = ref_args(h);
-        if (S) hipLaunchKernelGGL((k_cl_loop_scp_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, *S, rf);
-        else hipLaunchKernelGGL((k_cl_loop_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, L, rf);
+        if (S) hipLaunchKernelGGL((k_cl_loop_scp_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, blk, rf);
+        else hipLaunchKernelGGL((k_cl_loop_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, blk, rf);
     }
-    else if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL>), dim3(grid), dim3(64), lds, h->st, *S);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
-    else hipLaunchKernelGGL((k_cl_loop<MODEL>), dim3(grid), dim3(64), lds, h->st, L);
+    else if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL>), dim3(grid), dim3(64), lds, h->st, blk);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
+    else hipLaunchKernelGGL((k_cl_loop<MODEL>), dim3(grid), dim3(64), lds, h->st, blk);
     hipEventRecord(h->ev[9], h->st);
     if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
     HIPCHK(hipGetLastError());
     return 0;
 }
-// scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp)
-static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out, bool scp = false, int scp_rti = 1) {
+// the argument block of one persistent launch (every byte defined: the block is copied and compared as bytes); no HIP call in here
+static ScpLoopArgs make_loop_block(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, bool scp, int scp_rti) {
     const int max_it = !scp ? 1 : (scp_rti > 0 ? scp_rti : o.max_scp_iter);
     const slsqp_dims &d = h->d;
     const int B = h->B;
-    if (!h->beta_inited) {      // what the handle's first solve does once: beta = eps everywhere (later solves only repair swept instances)
-        hipLaunchKernelGGL(k_fill_doubles, dim3(1024), dim3(256), 0, h->st, h->beta, o.eps_backoff, (size_t)B * d.N * d.N * d.ni);
-        hipLaunchKernelGGL(k_fill_doubles, dim3(1024), dim3(256), 0, h->st, h->beta_f, o.eps_backoff, (size_t)B * (d.N + 1) * d.ni_f);
-        h->beta_inited = true;
-    }
-    h->time_kernels = o.time_kernels != 0;
-    LoopArgs L;
+    ScpLoopArgs S;
+    memset(&S, 0, sizeof S);
+    LoopArgs &L = S.L;
     const int *active = scp ? h->scp_active : nullptr;      // (k_cl_loop_scp masks an instance whose step failed for the rest of its MPC step, as slsqp_cl_step does)
     L.c = make_chain_args(h, o, active, 1);
-    L.c.q1.call_ids = L.c.q2.call_ids = h->call_ids;
-    L.c.q1.shift_stepno = L.c.q2.shift_stepno = h->cl_stepno;      // the horizon has moved for the instances past their first step
+    L.c.q.call_ids = h->call_ids;
+    L.c.q.shift_stepno = h->cl_stepno;      // the horizon has moved for the instances past their first step
     L.c.qplog = h->qplog; L.c.x0vlog = h->x0vlog; L.c.stepno = h->cl_stepno; L.c.log_steps = h->qplog_steps;
     L.cl = cl_args(h, nullptr);
     L.lin = LinArgs{B, d.N, h->Xn, h->Un, h->g_raw, h->gf_raw, costs_of(h), h->A, h->Bm, h->c, h->g, h->gN, h->q, nullptr, h->lin_stage, h->lin_tape};
@@ -2241,17 +2291,45 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     L.W_all = dW; L.pinf = h->pinf;
     L.Q = ClQueue{h->clq_slots, h->clq_cap - 1u, (unsigned *)h->clq_ctl, (unsigned *)h->clq_ctl + 1, h->clq_ctl + 2, h->clq_ctl + 3};
     L.busy = h->cl_busy; L.t_begin = h->cl_tbegin;
+    S.max_it = max_it; S.converge = scp_rti <= 0 ? 1 : 0; S.rti_steps = o.rti_steps; S.nsolves = h->qplog_nsolves;
+    return S;
+}
+// the block goes to the handle's device buffer on the handle's stream, ahead of the launch that reads it (and behind the previous launch, which may
+// still be reading the previous contents: stream order).  loop_blk_host keeps the bytes in memory the handle owns; every persistent run ends with a
+// synchronisation of the stream, so the previous copy out of it has been taken
+static void stage_loop_block(slsqp_handle *h, const ScpLoopArgs &S) {
+    static_assert(sizeof(ScpLoopArgs) <= 4096, "slsqp_handle::loop_blk is 4096 bytes");
+    h->loop_blk_host.resize(sizeof S);
+    memcpy(h->loop_blk_host.data(), &S, sizeof S);
+}
+static int write_loop_block(slsqp_handle *h, const ScpLoopArgs &S) {
+    stage_loop_block(h, S);
+    HIPCHK(hipMemcpyAsync(h->loop_blk, h->loop_blk_host.data(), sizeof S, hipMemcpyHostToDevice, h->st));
+    return 0;
+}
+// scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp)
+static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out, bool scp = false, int scp_rti = 1) {
+    const int max_it = !scp ? 1 : (scp_rti > 0 ? scp_rti : o.max_scp_iter);
+    const slsqp_dims &d = h->d;
+    const int B = h->B;
+    if (!h->beta_inited) {      // what the handle's first solve does once: beta = eps everywhere (later solves only repair swept instances)
+        hipLaunchKernelGGL(k_fill_doubles, dim3(1024), dim3(256), 0, h->st, h->beta, o.eps_backoff, (size_t)B * d.N * d.N * d.ni);
+        hipLaunchKernelGGL(k_fill_doubles, dim3(1024), dim3(256), 0, h->st, h->beta_f, o.eps_backoff, (size_t)B * (d.N + 1) * d.ni_f);
+        h->beta_inited = true;
+    }
+    h->time_kernels = o.time_kernels != 0;
+    const ScpLoopArgs S = make_loop_block(h, steps, dW, o, scp, scp_rti);
+    const LoopArgs &L = S.L;
+    if (write_loop_block(h, S)) return -1;
     hipLaunchKernelGGL(k_clq_init, dim3(64), dim3(256), 0, h->st, B, L.Q);
     HIPCHK(hipMemsetAsync(h->cl_busy, 0, 16 * sizeof(unsigned long long), h->st));
     HIPCHK(hipMemsetAsync(h->cl_busy + 14, 0xFF, sizeof(unsigned long long), h->st));      // (CL_LOOP_STAMP builds: earliest wave start)
     HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
     const int tl_tot = tl_begin(h, 2), tl_c = tl_begin(h, 4);
     int rc = -1;
-    ScpLoopArgs S{L, max_it, scp_rti <= 0 ? 1 : 0, o.rti_steps, h->qplog_nsolves};
-    const ScpLoopArgs *Sp = scp ? &S : nullptr;
-    if (h->model_id == 0) rc = launch_loop_t<0>(h, L, Sp);
-    else if (h->model_id == 1) rc = launch_loop_t<1>(h, L, Sp);
-    else rc = launch_loop_t<2>(h, L, Sp);
+    if (h->model_id == 0) rc = launch_loop_t<0>(h, scp);
+    else if (h->model_id == 1) rc = launch_loop_t<1>(h, scp);
+    else rc = launch_loop_t<2>(h, scp);
     if (rc) return -1;
     if (scp && S.converge) hipLaunchKernelGGL(k_cl_qplog_masked, dim3(steps), dim3(256), 0, h->st, B, steps, h->qplog_steps, h->qplog_nsolves, h->qplog, h->x0vlog);
     tl_end(h, tl_c); tl_end(h, tl_tot);

@@ -111,9 +111,43 @@ struct QpArgs {
     double early_ctol;        // tolerance (relative to max(1,|q|inf)) of the look at the un-refined polish solve: its accuracy class
 };
 
-// The x0 gate's tolerance and record live in device memory BEHIND the kkt block, not in QpArgs: k_rti_chain / k_cl_loop keep both QpArgs of a call in
-// scalar registers (selected field by field between QP #1 and QP #2), and two more fields there cost the closed-loop kernel 5 % (SGPR spills into VGPR
-// lanes).  Layout: kkt[8 B] = tolerance (the pinned x_0 may lie that far outside its own stage-0 box before the solve is refused
+// The last QP of a fast-SLS call (the tightened one) runs on the arguments of the first with three ints of its own: the fused kernels carry ONE QpArgs
+// and these (ChainArgs), so only three values are selected on the pass instead of two whole structs field by field.
+struct Qp2Ints { int warm, stat_slot, snap_use; };
+__host__ __device__ inline QpArgs qp_second_args(const QpArgs &q, const Qp2Ints &s) {
+    QpArgs r = q;
+    r.warm = s.warm; r.stat_slot = s.stat_slot; r.snap_use = s.snap_use;
+    return r;
+}
+
+// The persistent closed-loop kernels read their arguments from a block in device memory (one per handle, written by the host before the launch and
+// never by a kernel) instead of taking 600 dwords by value: by value they are all live in scalar registers from the kernel's entry, far more than a
+// wave has, and the hot loops pay a v_readlane for every use of a spilled one.  args_here<true> gives the reference back
+// through the CONSTANT address space, so that wave-uniform fields are read with scalar loads, after laundering the pointer through an empty asm
+// statement: nothing read through it is loop-invariant or available from an earlier part for the compiler then, so every part of the code loads the
+// few fields it uses at its own head and keeps them no longer.  args_here<false>: the arguments are kernel parameters, nothing changes.
+template <bool BLK, class T>
+__device__ __forceinline__ const T &args_here(const T *p) {      // (p by value: the caller's pointer is never redefined, so it stays a scalar, loop-invariant value)
+    if constexpr (BLK) {
+        // (laundered AS a constant-address-space pointer: what comes out of the asm statement then still has that address space, the loads through it
+        // are scalar loads, and the pointers they load are taken to be global ones, as those of kernel parameters are -- global_load, not flat_load)
+        const __attribute__((address_space(4))) T *k = (const __attribute__((address_space(4))) T *)p;
+        asm volatile("" : "+s"(k));
+        return *(const T *)k;
+    } else return *p;
+}
+// the QpArgs of this part of qp_solve_dev: the block's with the three ints of the QP at hand, or the kernel parameter as it is
+template <bool BLK>
+__device__ __forceinline__ QpArgs qp_args_here(const QpArgs *p, const Qp2Ints &qi) {
+    if constexpr (BLK) return qp_second_args(args_here<true>(p), qi);
+    else return *p;
+}
+
+// The x0 gate's tolerance and record live in device memory BEHIND the kkt block, not in QpArgs.  When they were added, k_rti_chain / k_cl_loop kept
+// both QpArgs of a call in scalar registers (selected field by field between QP #1 and QP #2), and two more fields there cost the closed-loop kernel
+// 5 % (SGPR spills into VGPR lanes).  Since then a chain carries one QpArgs (qp_second_args) and the persistent kernels read theirs
+// from a block in memory (args_here), where a field costs a scalar load at its use; k_qp_solve and k_rti_chain still take QpArgs by value, so the
+// record stays where it is.  Layout: kkt[8 B] = tolerance (the pinned x_0 may lie that far outside its own stage-0 box before the solve is refused
 // with status 2: the gate is max(1e-9, tolerance), +inf = the stage-0 state rows never gate, a NaN / infinite state is refused whatever the value),
 // kkt[8 B + 1] unused, then x0_viol (B,2): the largest stage-0 violation of the instance's last first / last QP (<= 0 inside the box, +inf for a NaN
 // state), written by one lane for accepted and refused solves alike; the slot of a QP that took no part keeps its previous value (qp_stats says -1).
@@ -554,7 +588,7 @@ struct QpState {   // per instance, 40 doubles
 static_assert(sizeof(QpState) == 40 * sizeof(double), "QpState size");
 
 #ifndef LAUNDER_B
-#define LAUNDER_B(b) asm volatile("" : "+s"(b))
+#define LAUNDER_B(b) do { b = __builtin_amdgcn_readfirstlane(b); asm volatile("" : "+s"(b)); } while (0)      // (wave-uniform by construction; said so, or the back end may hold it in a vector register)
 #endif
 template <int NX, int NU>
 __device__ __forceinline__ NeG<NX, NU> make_neg(const QpArgs &a, int b) {
@@ -1300,15 +1334,19 @@ __device__ __forceinline__ void phase_update(const QpArgs &a, int first, int b, 
 #define QP_PERSIST_WAVES_PER_SIMD 3
 #endif
 
-template <int NX, int NU, bool MX = false>     // MX: the mixed-precision sweeps (ne_forward_mx / ne_backward_mx, section 2.4 of DESIGN.md), same loop and phase logic
+template <int NX, int NU, bool MX = false, bool BLK = false>     // MX: the mixed-precision sweeps (ne_forward_mx / ne_backward_mx, section 2.4 of DESIGN.md), same loop and phase logic
 // resume != 0: the solve was suspended by an earlier launch at its deadline (state in HBM: QpState, workspace) and continues where it stopped.
 // deadline: wall-clock tick (100 MHz) after which the solve suspends itself between two block solves (~0: never).  Returns 1 when the solve has
 // ended (or took no part), 0 when it was suspended.
 // fin_count / cut_count (slsqp_cl_run): the solve also suspends itself once cut_count chains of its launch have ended (the few solves still running
 // then are the ones that would keep the launch alive on their own).
-__device__ __forceinline__ int qp_solve_dev(const QpArgs &a, int b, int lane, double *sm, int max_ticks, int resume = 0, unsigned long long deadline = ~0ULL,
-                                            const unsigned *fin_count = nullptr, unsigned cut_count = 0xFFFFFFFFu) {
+// BLK: a_ lies in the argument block of a persistent closed-loop kernel and qi holds the three ints of this QP (args_here above); every part of the
+// solve reads the fields it uses at its own head.
+__device__ __forceinline__ int qp_solve_dev(const QpArgs &a_, int b, int lane, double *sm, int max_ticks, int resume = 0, unsigned long long deadline = ~0ULL,
+                                            const unsigned *fin_count = nullptr, unsigned cut_count = 0xFFFFFFFFu, const Qp2Ints qi = Qp2Ints{0, 0, 0}) {
+    const QpArgs *ap = &a_;
     if (!resume) {
+        const QpArgs a = qp_args_here<BLK>(ap, qi);
         if (a.run && !a.run[b]) {       // not part of this solve: its statistics slot says so (status -1)
             if (a.qpstat && lane < 8) a.qpstat[((size_t)b * 2 + a.stat_slot) * 8 + lane] = (lane == 6) ? -1 : 0;
             return 1;
@@ -1331,6 +1369,7 @@ __device__ __forceinline__ int qp_solve_dev(const QpArgs &a, int b, int lane, do
         // the tick loop and keep them in registers across the sweeps (256 VGPRs + 118 spilled when it does; 168-194 like this).
         LAUNDER_B(b);
         asm volatile("" : "+v"(lane));
+        const QpArgs a = qp_args_here<BLK>(ap, qi);
         QpState *st = (QpState *)a.state + b;
         const int phase = (int)st->phase;
         if (phase == P_DONE) break;
@@ -1362,17 +1401,19 @@ __device__ __forceinline__ int qp_solve_dev(const QpArgs &a, int b, int lane, do
         LAUNDER_B(b);
         asm volatile("" : "+v"(lane));
         if (!res_only_done) {
-            if constexpr (MX) ne_backward_mx<NX, NU>(sm, make_neg<NX, NU>(a, b), lane);
-            else ne_backward<NX, NU>(sm, make_neg<NX, NU>(a, b), lane);
+            const QpArgs ab = qp_args_here<BLK>(ap, qi);
+            if constexpr (MX) ne_backward_mx<NX, NU>(sm, make_neg<NX, NU>(ab, b), lane);
+            else ne_backward<NX, NU>(sm, make_neg<NX, NU>(ab, b), lane);
         }
         wla::wsync_mem();
         QSTAMP(c_bwd);
         LAUNDER_B(b);
         asm volatile("" : "+v"(lane));
-        phase_update<NX, NU>(a, 0, b, lane, sm);
+        phase_update<NX, NU>(qp_args_here<BLK>(ap, qi), 0, b, lane, sm);
         wla::wsync_mem();
         QSTAMP(c_ph);
     }
+    const QpArgs a = qp_args_here<BLK>(ap, qi);
 #ifdef QP_STAMP
     if (lane == 0) { double *kk = a.kkt + (size_t)b * 8; kk[2] = (double)c_fwdf; kk[3] = (double)(double)n_fstages; kk[4] = (double)c_fwd; kk[5] = (double)c_bwd; kk[6] = (double)c_ph; kk[7] = (double)(__builtin_readcyclecounter() - c_t0); }
 #endif
