@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/slsqp.h"
@@ -106,6 +107,22 @@ struct slsqp_handle {
 
 static RefArgs ref_args(slsqp_handle *h) { return RefArgs{h->ref_Y, h->ref_T, h->ref_stride}; }
 static PlantArgs plant_args(slsqp_handle *h) { return PlantArgs{h->pp_P, h->pp_stride, h->pp_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps}; }
+// A run-time choice among three as a template argument: f(std::integral_constant<int, i>) for i in 0..2, false for any other i.  f is a generic
+// lambda and names the constant as M() / V(); an instantiation that is missing stops the build.
+template <class F>
+static bool dispatch3(int i, F &&f) {
+    switch (i) {
+    case 0: f(std::integral_constant<int, 0>{}); return true;
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    }
+    return false;
+}
+// the handle's plant model (0 pendulum, 1 quadrotor, 2 rocket): every launch of a kernel that is a template of the model goes through here
+template <class F>
+static int with_model(const slsqp_handle *h, F &&f) {
+    return dispatch3(h->model_id, f) ? 0 : fail("no kernels for model id " + std::to_string(h->model_id) + " (0 pendulum, 1 quadrotor, 2 rocket)");
+}
 static Costs costs_of(slsqp_handle *h) {
     const int nx = h->d.nx, nu = h->d.nu;
     Costs c;
@@ -749,8 +766,8 @@ struct LoopArgs {
     ClQueue Q;
     unsigned long long *busy, *t_begin;      // busy[0] sum over the MPC steps of the time a wave spent on them (100 MHz ticks), [2] MPC steps run; t_begin (B): start of the instance's current step
 };
-// The argument block of the six persistent kernels (k_cl_loop* use L only; the fields behind it are k_cl_loop_scp*'s, described there).  It lives in
-// device memory, one block per handle (slsqp_handle::loop_blk), written by cl_run_persistent on the handle's stream before every launch; the kernels
+// The argument block of the two persistent kernels, whatever their variant (k_cl_loop uses L only; the fields behind it are k_cl_loop_scp's).  It lives in device
+// memory, one block per handle (slsqp_handle::loop_blk), written by cl_run_persistent on the handle's stream before every launch; the kernels
 // take its address and read it through args_here<true> (slsqp_kernels.hpp): the heads of cl_step_begin, of the chain's parts, of cl_step_end and of
 // every part of qp_solve_dev's tick loop each read the fields they use.  What may go into it: anything -- a field costs a scalar load where it is
 // used, not a register for the life of the kernel.
@@ -825,8 +842,13 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
     CLSTAMP(10);
     return (s + 1 < L.steps) ? s + 1 : 0;
 }
-template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const ScpLoopArgs *blk) {
+// The persistent closed loop, ONE body with three variants.  VAR 0: plain; 1: tracks a reference (slsqp_cl_set_reference: the linear cost of
+// cl_step_begin reads rf); 2: tracks a reference and steps the plant with the instance's own parameters (slsqp_cl_set_plant_params: cl_step_end reads
+// pa; without a reference rf is one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference).  A variant is passed empty
+// rf / pa where it reads none.  The two calls that name VAR are all that depends on it.  The statements stand in the kernel, not in a function it
+// calls, and the next per-handle option is a further VAR value, not a further kernel.
+template <int MODEL, int VAR>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     int lane = threadIdx.x;
     extern __shared__ double sm[];
@@ -850,13 +872,13 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const
             if (lane == 0) atomicAdd(L.busy + 11, wall_clock64() - tp_);
 #endif
         }
-        cl_step_begin<MODEL>(L, b, lane);
+        cl_step_begin<MODEL, (VAR > 0)>(L, b, lane, VAR > 0 ? &rf : nullptr);
         b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
         asm volatile("" : "+v"(lane));
         rti_chain_dev<NX, NU, true>(L.c, b, lane, sm);
         wla::wsync_mem();
         asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL>(L, b, lane));
+        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, (VAR > 1)>(L, b, lane, VAR > 1 ? &pa : nullptr));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
         const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
@@ -879,86 +901,6 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const
 #ifdef CL_LOOP_STAMP
     if (lane == 0) { const LoopArgs &L = args_here<true>(blk).L; const unsigned long long te_ = wall_clock64(); atomicAdd(L.busy + 13, te_ - tw0_); atomicMax(L.busy + 15, te_); atomicAdd(L.busy + 1, 1ULL); }
 #endif
-}
-// The same loop for a handle with a reference (slsqp_cl_set_reference): the only difference is the tracked linear cost of cl_step_begin.  A kernel of
-// its own, so that k_cl_loop keeps its arguments and its code object (profiles/r07/resource_usage.txt); keep the two bodies in step --
-// tests/test_gpu_reference.py holds this one to the step-by-step loop bit for bit.  (No CL_LOOP_STAMP instrumentation here.)
-template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_ref(const ScpLoopArgs *blk, RefArgs rf) {
-    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    int lane = threadIdx.x;
-    extern __shared__ double sm[];
-    int b = -1;
-#pragma unroll 1
-    for (;;) {
-        asm volatile("" : "+v"(lane));
-        const LoopArgs &L = args_here<true>(blk).L;
-        if (b < 0) {
-            b = clq_pop(L.Q, lane);
-            if (b < 0) break;
-            if (L.fence & 1) __threadfence();      // acquire: what the wave that ran this instance's previous step wrote (possibly through another XCD's L2)
-        }
-        cl_step_begin<MODEL, true>(L, b, lane, &rf);
-        b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
-        asm volatile("" : "+v"(lane));
-        rti_chain_dev<NX, NU, true>(L.c, b, lane, sm);
-        wla::wsync_mem();
-        asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL>(L, b, lane));
-        b = __builtin_amdgcn_readfirstlane(b);
-        if (!next) { b = -1; continue; }
-        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
-        // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
-        // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
-        // waves are shared fairly among the instances that are level
-        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
-        if (behind && Lt.keep_laggards) continue;
-        if (Lt.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
-        clq_push(Lt.Q, b, lane);
-        b = -1;
-    }
-}
-
-// The same loop for a handle with plant parameters (slsqp_cl_set_plant_params): the only difference to k_cl_loop_ref is the plant step of cl_step_end
-// (the instance's own parameter row, model_err and its log).  Written once, on the body that takes a reference: a handle with parameters but without a
-// reference passes one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference.  Keep the bodies in step --
-// tests/test_gpu_plant_params.py holds this one to the step-by-step loop bit for bit.
-template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_pp(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
-    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    int lane = threadIdx.x;
-    extern __shared__ double sm[];
-    int b = -1;
-#pragma unroll 1
-    for (;;) {
-        asm volatile("" : "+v"(lane));
-        const LoopArgs &L = args_here<true>(blk).L;
-        if (b < 0) {
-            b = clq_pop(L.Q, lane);
-            if (b < 0) break;
-            if (L.fence & 1) __threadfence();      // acquire: what the wave that ran this instance's previous step wrote (possibly through another XCD's L2)
-        }
-        cl_step_begin<MODEL, true>(L, b, lane, &rf);
-        b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
-        asm volatile("" : "+v"(lane));
-        rti_chain_dev<NX, NU, true>(L.c, b, lane, sm);
-        wla::wsync_mem();
-        asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, true>(L, b, lane, &pa));
-        b = __builtin_amdgcn_readfirstlane(b);
-        if (!next) { b = -1; continue; }
-        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
-        // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
-        // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
-        // waves are shared fairly among the instances that are level
-        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
-        if (behind && Lt.keep_laggards) continue;
-        if (Lt.fence & 2) __threadfence();      // release: the next step of this instance may run anywhere
-        clq_push(Lt.Q, b, lane);
-        b = -1;
-    }
 }
 
 // ---- the persistent loop for any SCP setting of slsqp_cl_step (slsqp_cl_run_scp) -------------------------------------------------------
@@ -1095,8 +1037,10 @@ __device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int la
     }
     wla::wsync_mem();
 }
-template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(const ScpLoopArgs *blk) {
+// one body for the three variants, as k_cl_loop above: VAR > 0 reads the tracked linear cost in cl_scp_iter_begin, VAR > 1 the plant parameters in
+// cl_scp_step_end
+template <int MODEL, int VAR>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     int lane = threadIdx.x;
     extern __shared__ double sm[];
@@ -1117,7 +1061,7 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(c
 #pragma unroll 1
         for (int ii = 0; ii < S.max_it; ii++) {
             asm volatile("" : "+v"(lane));
-            cl_scp_iter_begin<MODEL>(L, b, lane, ii);
+            cl_scp_iter_begin<MODEL, (VAR > 0)>(L, b, lane, ii, VAR > 0 ? &rf : nullptr);
             b = __builtin_amdgcn_readfirstlane(b);
             asm volatile("" : "+v"(lane));
             sls_solve_dev<NX, NU>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0);
@@ -1128,99 +1072,7 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(c
             if (S.converge && !act) break;
         }
         asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL>(S, b, lane, nsolves));
-        b = __builtin_amdgcn_readfirstlane(b);
-        if (!next) { b = -1; continue; }
-        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
-        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
-        if (behind && Lt.keep_laggards) continue;
-        if (Lt.fence & 2) __threadfence();
-        clq_push(Lt.Q, b, lane);
-        b = -1;
-    }
-}
-// k_cl_loop_scp for a handle with a reference: as k_cl_loop_ref above, the tracked linear cost in cl_scp_iter_begin is the only difference
-template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_ref(const ScpLoopArgs *blk, RefArgs rf) {
-    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    int lane = threadIdx.x;
-    extern __shared__ double sm[];
-    int b = -1;
-#pragma unroll 1
-    for (;;) {
-        asm volatile("" : "+v"(lane));
-        const ScpLoopArgs &S = args_here<true>(blk);
-        const LoopArgs &L = S.L;
-        if (b < 0) {
-            b = clq_pop(L.Q, lane);
-            if (b < 0) break;
-            if (L.fence & 1) __threadfence();
-        }
-        cl_scp_step_begin<MODEL>(L, b, lane);
-        b = __builtin_amdgcn_readfirstlane(b);
-        int nsolves = 0;
-#pragma unroll 1
-        for (int ii = 0; ii < S.max_it; ii++) {
-            asm volatile("" : "+v"(lane));
-            cl_scp_iter_begin<MODEL, true>(L, b, lane, ii, &rf);
-            b = __builtin_amdgcn_readfirstlane(b);
-            asm volatile("" : "+v"(lane));
-            sls_solve_dev<NX, NU>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0);
-            asm volatile("" : "+v"(lane));
-            const int act = __builtin_amdgcn_readfirstlane(cl_scp_iter_end<MODEL>(L, b, lane, ii, S.converge));
-            b = __builtin_amdgcn_readfirstlane(b);
-            nsolves = ii + 1;
-            if (S.converge && !act) break;
-        }
-        asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL>(S, b, lane, nsolves));
-        b = __builtin_amdgcn_readfirstlane(b);
-        if (!next) { b = -1; continue; }
-        const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
-        const unsigned long long done_steps = __hip_atomic_load(Lt.busy + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int behind = __builtin_amdgcn_readfirstlane(((unsigned long long)next * (unsigned long long)Lt.cl.B < done_steps) ? 1 : 0);
-        if (behind && Lt.keep_laggards) continue;
-        if (Lt.fence & 2) __threadfence();
-        clq_push(Lt.Q, b, lane);
-        b = -1;
-    }
-}
-// k_cl_loop_scp_ref for a handle with plant parameters: as k_cl_loop_pp above, the plant step of cl_scp_step_end is the only difference
-template <int MODEL>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp_pp(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
-    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    int lane = threadIdx.x;
-    extern __shared__ double sm[];
-    int b = -1;
-#pragma unroll 1
-    for (;;) {
-        asm volatile("" : "+v"(lane));
-        const ScpLoopArgs &S = args_here<true>(blk);
-        const LoopArgs &L = S.L;
-        if (b < 0) {
-            b = clq_pop(L.Q, lane);
-            if (b < 0) break;
-            if (L.fence & 1) __threadfence();
-        }
-        cl_scp_step_begin<MODEL>(L, b, lane);
-        b = __builtin_amdgcn_readfirstlane(b);
-        int nsolves = 0;
-#pragma unroll 1
-        for (int ii = 0; ii < S.max_it; ii++) {
-            asm volatile("" : "+v"(lane));
-            cl_scp_iter_begin<MODEL, true>(L, b, lane, ii, &rf);
-            b = __builtin_amdgcn_readfirstlane(b);
-            asm volatile("" : "+v"(lane));
-            sls_solve_dev<NX, NU>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0);
-            asm volatile("" : "+v"(lane));
-            const int act = __builtin_amdgcn_readfirstlane(cl_scp_iter_end<MODEL>(L, b, lane, ii, S.converge));
-            b = __builtin_amdgcn_readfirstlane(b);
-            nsolves = ii + 1;
-            if (S.converge && !act) break;
-        }
-        asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL, true>(S, b, lane, nsolves, &pa));
+        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL, (VAR > 1)>(S, b, lane, nsolves, VAR > 1 ? &pa : nullptr));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
         const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
@@ -1992,19 +1844,12 @@ static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int
     LinArgs a{h->B, d.N, dX, dU, h->g_raw, h->gf_raw, costs_of(h), h->A, h->Bm, h->c, h->g, h->gN, h->q, run, h->lin_stage, h->lin_tape};
     const int grid = 2048, blk = 128;
     const int gval = (int)((B * d.N + blk - 1) / blk);
-    if (h->model_id == 0) {
-        hipLaunchKernelGGL((k_lin_val<0>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<0>), dim3(grid), dim3(blk), 0, h->st, a);
-        if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<4, 1>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
-        else hipLaunchKernelGGL((k_lin_vec<4, 1>), dim3(grid), dim3(256), 0, h->st, a);
-    } else if (h->model_id == 1) {
-        hipLaunchKernelGGL((k_lin_val<1>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<1>), dim3(grid), dim3(blk), 0, h->st, a);
-        if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<13, 4>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
-        else hipLaunchKernelGGL((k_lin_vec<13, 4>), dim3(grid), dim3(256), 0, h->st, a);
-    } else {
-        hipLaunchKernelGGL((k_lin_val<2>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<2>), dim3(grid), dim3(blk), 0, h->st, a);
-        if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<17, 4>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
-        else hipLaunchKernelGGL((k_lin_vec<17, 4>), dim3(grid), dim3(256), 0, h->st, a);
-    }
+    if (with_model(h, [&](auto M) {
+            constexpr int NX = dyn::Dims<M()>::NX, NU = dyn::Dims<M()>::NU;
+            hipLaunchKernelGGL((k_lin_val<M()>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<M()>), dim3(grid), dim3(blk), 0, h->st, a);
+            if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<NX, NU>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
+            else hipLaunchKernelGGL((k_lin_vec<NX, NU>), dim3(grid), dim3(256), 0, h->st, a);
+        })) return -1;
     BoundsArgs ba{h->B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, run};
     hipLaunchKernelGGL(k_set_bounds, dim3(1024), dim3(256), 0, h->st, ba);
     HIPCHK(hipGetLastError());
@@ -2038,9 +1883,7 @@ extern "C" int slsqp_cl_init(slsqp_handle *h, const double *x_meas, const double
         HIPCHK(hipMemcpy(h->u_init, ui.data(), sizeof(double) * d.nu, hipMemcpyHostToDevice));
         ClArgs a = cl_args(h, nullptr);
         const int gb = (h->B + 63) / 64;
-        if (h->model_id == 0) hipLaunchKernelGGL((k_cl_rollout<0>), dim3(gb), dim3(64), 0, h->st, a);
-        else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_rollout<1>), dim3(gb), dim3(64), 0, h->st, a);
-        else hipLaunchKernelGGL((k_cl_rollout<2>), dim3(gb), dim3(64), 0, h->st, a);
+        if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_rollout<M()>), dim3(gb), dim3(64), 0, h->st, a); })) return -1;
         HIPCHK(hipGetLastError());
     }
     h->cl_steps = 0;
@@ -2070,19 +1913,15 @@ extern "C" int slsqp_nominal_solve(slsqp_handle *h, int max_qp, double tol, doub
     na.B = B; na.N = d.N; na.Xn = h->Xn; na.Un = h->Un; na.xmeas = h->xmeas; na.primal = h->primal; na.qp_status = h->status; na.g_raw = h->g_raw; na.gf_raw = h->gf_raw;
     na.cst = costs_of(h); na.st = h->nom_st; na.active = active; na.need_lin = h->nom_need_lin; na.status = h->nom_status; na.iters = h->nom_iters;
     na.n_active = h->counter + 2; na.rho = rho; na.tol = tol; na.w_max = 1e8;
+    const RefArgs rf = h->ref_T > 0 ? ref_args(h) : RefArgs{};      // the tracked objective, window of step 0
     auto eval = [&](int mode) {
         na.mode = mode;
-        if (h->ref_T > 0) {      // the tracked objective, window of step 0
-            const RefArgs rf = ref_args(h);
-            if (h->model_id == 0) hipLaunchKernelGGL((k_nom_eval_ref<0>), dim3(B), dim3(128), 0, h->st, na, rf);
-            else if (h->model_id == 1) hipLaunchKernelGGL((k_nom_eval_ref<1>), dim3(B), dim3(128), 0, h->st, na, rf);
-            else hipLaunchKernelGGL((k_nom_eval_ref<2>), dim3(B), dim3(128), 0, h->st, na, rf);
-        }
-        else if (h->model_id == 0) hipLaunchKernelGGL((k_nom_eval<0>), dim3(B), dim3(128), 0, h->st, na);
-        else if (h->model_id == 1) hipLaunchKernelGGL((k_nom_eval<1>), dim3(B), dim3(128), 0, h->st, na);
-        else hipLaunchKernelGGL((k_nom_eval<2>), dim3(B), dim3(128), 0, h->st, na);
+        return with_model(h, [&](auto M) {
+            if (h->ref_T > 0) hipLaunchKernelGGL((k_nom_eval<M(), true>), dim3(B), dim3(128), 0, h->st, na, rf);
+            else hipLaunchKernelGGL((k_nom_eval<M(), false>), dim3(B), dim3(128), 0, h->st, na, rf);
+        });
     };
-    eval(0);
+    if (eval(0)) return -1;
     double tq = 0;
     for (int it = 0; it < max_qp; it++) {
         if (linearize_impl(h, h->Xn, h->Un, SLSQP_DEVICE, h->nom_need_lin, 0)) return -1;     // accepted instances only; the others re-solve
@@ -2093,7 +1932,7 @@ extern "C" int slsqp_nominal_solve(slsqp_handle *h, int max_qp, double tol, doub
         if (launch_qp(h, active, &o, it > 0 ? 1 : 0, h->nom_st /* S[0] = w: stride 12 */)) return -1;
         HIPCHK(hipEventRecord(h->ev[7], h->st));
         HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
-        eval(1);
+        if (eval(1)) return -1;
         int nact = 0;
         HIPCHK(hipMemcpyAsync(&nact, h->counter + 2, sizeof(int), hipMemcpyDeviceToHost, h->st));
         HIPCHK(hipStreamSynchronize(h->st));
@@ -2157,9 +1996,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     if (w) { if (put(h, h->wbuf, w, sizeof(double) * (size_t)h->B * d.nx, loc)) return -1; dw = h->wbuf; }
     ClArgs a = cl_args(h, dw);
     if (h->cl_steps > 0) {
-        if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 1, 0);
-        else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant<1>), dim3(gb), dim3(64), 0, h->st, a, 1, 0);
-        else hipLaunchKernelGGL((k_cl_shift_plant<2>), dim3(gb), dim3(64), 0, h->st, a, 1, 0);
+        if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 1, 0); })) return -1;
         if (slsqp_reset(h)) return -1;
         h->horizon_shifted = 1;
     }
@@ -2185,9 +2022,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
         HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
         ScpArgs sa{ii, converge ? 1 : 0, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
         hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, sa);
-        if (h->model_id == 0) hipLaunchKernelGGL((k_cl_infeas<0>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf);
-        else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_infeas<1>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf);
-        else hipLaunchKernelGGL((k_cl_infeas<2>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf);
+        if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_infeas<M()>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf); })) return -1;
         if (ii + 1 == max_it) break;
         if (converge) {     // the host decides whether anyone is still iterating; RTI mode runs its rti iterations without looking (the instances that
                             // failed are masked on the device), so a whole RTI step is one burst of launches on the stream
@@ -2208,15 +2043,10 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
         hipLaunchKernelGGL(k_cl_log_x0v, dim3((2 * h->B + 255) / 256), dim3(256), 0, h->st, h->B, h->log_steps, h->cl_steps, h->x0viol, h->qpstat, h->lg_x0v);
         h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};      // (a slsqp_cl_run in between points the name at its own per-run buffer)
     }
-    if (h->pp_P) {      // the plant has its own parameters
-        const PlantArgs pa = plant_args(h);
-        if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant_pp<0>), dim3(gb), dim3(64), 0, h->st, a, pa, h->cl_steps, nullptr, nullptr, nullptr);
-        else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant_pp<1>), dim3(gb), dim3(64), 0, h->st, a, pa, h->cl_steps, nullptr, nullptr, nullptr);
-        else hipLaunchKernelGGL((k_cl_shift_plant_pp<2>), dim3(gb), dim3(64), 0, h->st, a, pa, h->cl_steps, nullptr, nullptr, nullptr);
-    }
-    else if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
-    else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant<1>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
-    else hipLaunchKernelGGL((k_cl_shift_plant<2>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
+    if (with_model(h, [&](auto M) {
+            if (h->pp_P) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, plant_args(h), h->cl_steps, nullptr, nullptr, nullptr);      // the plant has its own parameters
+            else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
+        })) return -1;
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->st));
     tl_take(h);
@@ -2244,19 +2074,14 @@ static int launch_loop_t(slsqp_handle *h, bool S) {
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     hipEventRecord(h->ev[8], h->st);
-    if (h->pp_P) {      // plant parameters: the kernels that take them (written on the tracked bodies: without a reference, one row of zeros)
-        const RefArgs rf = h->ref_T > 0 ? ref_args(h) : RefArgs{h->pp_zero_ref, 1, 0};
-        const PlantArgs pa = plant_args(h);
-        if (S) hipLaunchKernelGGL((k_cl_loop_scp_pp<MODEL>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);
-        else hipLaunchKernelGGL((k_cl_loop_pp<MODEL>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);
-    }
-    else if (h->ref_T > 0) {      // tracked cost: the kernels that take the reference
-        const RefArgs rf = ref_args(h);
-        if (S) hipLaunchKernelGGL((k_cl_loop_scp_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, blk, rf);
-        else hipLaunchKernelGGL((k_cl_loop_ref<MODEL>), dim3(grid), dim3(64), lds, h->st, blk, rf);
-    }
-    else if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL>), dim3(grid), dim3(64), lds, h->st, blk);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
-    else hipLaunchKernelGGL((k_cl_loop<MODEL>), dim3(grid), dim3(64), lds, h->st, blk);
+    // the kernels' variant: 2 plant parameters (which track a reference: without one, one row of zeros), 1 a reference, 0 neither (rf, pa empty, unread)
+    const int var = h->pp_P ? 2 : (h->ref_T > 0 ? 1 : 0);
+    const RefArgs rf = h->ref_T > 0 ? ref_args(h) : (var == 2 ? RefArgs{h->pp_zero_ref, 1, 0} : RefArgs{});
+    const PlantArgs pa = var == 2 ? plant_args(h) : PlantArgs{};
+    dispatch3(var, [&](auto V) {
+        if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
+        else hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);
+    });
     hipEventRecord(h->ev[9], h->st);
     if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
     HIPCHK(hipGetLastError());
@@ -2327,10 +2152,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
     const int tl_tot = tl_begin(h, 2), tl_c = tl_begin(h, 4);
     int rc = -1;
-    if (h->model_id == 0) rc = launch_loop_t<0>(h, scp);
-    else if (h->model_id == 1) rc = launch_loop_t<1>(h, scp);
-    else rc = launch_loop_t<2>(h, scp);
-    if (rc) return -1;
+    if (with_model(h, [&](auto M) { rc = launch_loop_t<M()>(h, scp); }) || rc) return -1;
     if (scp && S.converge) hipLaunchKernelGGL(k_cl_qplog_masked, dim3(steps), dim3(256), 0, h->st, B, steps, h->qplog_steps, h->qplog_nsolves, h->qplog, h->x0vlog);
     tl_end(h, tl_c); tl_end(h, tl_tot);
     int ctl[4] = {0, 0, 0, 0};
@@ -2443,9 +2265,7 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         h->cl_cut_count = (cut_frac > 0.0 && cut_frac < 1.0) ? (unsigned)std::max(1.0, std::ceil(cut_frac * unfinished)) : 0xFFFFFFFFu;
         if (rounds >= max_rounds) { h->cl_round = false; h->cl_skip_begin = nullptr; return fail("slsqp_cl_run: round limit reached"); }
         // begin: reset_warm_start (shift + solver reset) for the instances past their first step
-        if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 1, 0, h->cl_begin, h->cl_stepno, nullptr);
-        else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant<1>), dim3(gb), dim3(64), 0, h->st, a, 1, 0, h->cl_begin, h->cl_stepno, nullptr);
-        else hipLaunchKernelGGL((k_cl_shift_plant<2>), dim3(gb), dim3(64), 0, h->st, a, 1, 0, h->cl_begin, h->cl_stepno, nullptr);
+        if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 1, 0, h->cl_begin, h->cl_stepno, nullptr); })) return -1;
         hipLaunchKernelGGL(k_cl_reset_masked, dim3(B), dim3(256), 0, h->st, B, h->n, h->cl_begin, h->cl_stepno, h->stale, h->itnum, h->pending_reset, h->q);
         hipLaunchKernelGGL(k_cl_bump_call, dim3(gbi), dim3(256), 0, h->st, B, h->cl_begin, h->call_ids);
         hipLaunchKernelGGL(k_cl_begin_flags, dim3(gbi), dim3(256), 0, h->st, B, h->cl_begin, h->scp_success, h->scp_iters);
@@ -2466,23 +2286,16 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
         ScpArgs sa{0, 0, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
         hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, sa);
-        if (h->model_id == 0) hipLaunchKernelGGL((k_cl_infeas<0>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf);
-        else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_infeas<1>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf);
-        else hipLaunchKernelGGL((k_cl_infeas<2>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf);
+        if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_infeas<M()>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf); })) return -1;
         if (h->log_steps > 0) {
             ClLogArgs la{h->cl_stepno, h->cl_done, h->B, d.N, d.nx, d.nu, h->log_steps, 0, h->Xn, h->Un, h->backoff_x, h->backoff_u, h->scp_success, h->scp_iters,
                          h->pinf, h->lg_x, h->lg_u, h->lg_bx, h->lg_bu, h->lg_state, h->lg_u0, h->lg_pinf, h->lg_succ, h->lg_it};
             hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, la);
         }
-        if (h->pp_P) {
-            const PlantArgs pa = plant_args(h);
-            if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant_pp<0>), dim3(gb), dim3(64), 0, h->st, a, pa, 0, h->cl_done, h->cl_stepno, dW);
-            else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant_pp<1>), dim3(gb), dim3(64), 0, h->st, a, pa, 0, h->cl_done, h->cl_stepno, dW);
-            else hipLaunchKernelGGL((k_cl_shift_plant_pp<2>), dim3(gb), dim3(64), 0, h->st, a, pa, 0, h->cl_done, h->cl_stepno, dW);
-        }
-        else if (h->model_id == 0) hipLaunchKernelGGL((k_cl_shift_plant<0>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
-        else if (h->model_id == 1) hipLaunchKernelGGL((k_cl_shift_plant<1>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
-        else hipLaunchKernelGGL((k_cl_shift_plant<2>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
+        if (with_model(h, [&](auto M) {
+                if (h->pp_P) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, plant_args(h), 0, h->cl_done, h->cl_stepno, dW);
+                else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
+            })) return -1;
         hipLaunchKernelGGL(k_cl_advance, dim3(gbi), dim3(256), 0, h->st, B, h->cl_done, h->cl_stepno, h->call_ids, h->cl_begin);
         HIPCHK(hipGetLastError());
     }
