@@ -9,6 +9,7 @@ fast_sls_rti_steps, step counts and (rocket) seed-s disturbance streams; B indep
     ... --persistent 1                                                     # the same loop as ONE persistent launch (same bits)
     ... --reference neutral | figure8                                      # track the plant's neutral point / a figure of eight in x, y
     ... --plant-scale mass=1.15 --plant-spread 10                          # a true plant that differs from the controller's model (see --help)
+    ... --model quadrotor --bound 5=-1.2:inf@3                             # a box that changes during the run: descent rate >= -1.2 from step 3 on
 
 The first nominal comes from the GPU initialiser (slsqp_nominal_solve) in place of IPOPT."""
 import argparse
@@ -19,7 +20,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from robust_nonlinear_mpc_amd import ClosedLoopMPC, disturbance_stream, get_model, plant_param_names  # noqa: E402
+from robust_nonlinear_mpc_amd import ClosedLoopMPC, box_bounds, disturbance_stream, get_model, plant_param_names  # noqa: E402
 from robust_nonlinear_mpc_amd._plant_cli import parse_plant_scale, sample_plant_params  # noqa: E402
 
 
@@ -43,6 +44,9 @@ def main():
                     help="the TRUE plant's parameter NAME is FACTOR x the controller's value, for every run (repeatable; names: plant_param_names(model))")
     ap.add_argument("--plant-spread", type=float, default=None, metavar="PCT",
                     help="every parameter of the true plant of run s uniform within +-PCT %% of its default, drawn from a generator seeded with s (gimbal lengths excluded)")
+    ap.add_argument("--bound", action="append", default=[], metavar="IDX=LO:HI[@ROW]",
+                    help="component IDX of [x; u] is held to [LO, HI] from MPC step ROW on (default 0), inside the model's own box; inf / -inf: that side keeps "
+                    "the model's bound (repeatable)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -78,7 +82,25 @@ def main():
         Xref = np.tile(np.asarray(m.x_ref, dtype=float), (T, 1))
         Xref[:, 0], Xref[:, 1] = 0.3 * np.sin(2.0 * t), 0.3 * (1.0 - np.cos(2.0 * t))
         Uref = np.tile(np.asarray(m.u_ref, dtype=float), (T, 1))
-    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P)
+    bounds = None
+    if a.bound:
+        Tb = steps + N + 1
+        spec = {}
+        for item in a.bound:
+            try:
+                idx, rest = item.split("=", 1)
+                rng_, _, row = rest.partition("@")
+                lo_s, hi_s = rng_.split(":", 1)
+                idx, lo_v, hi_v, row = int(idx), float(lo_s), float(hi_s), int(row or 0)
+            except ValueError:
+                ap.error(f"--bound {item!r}: expected IDX=LO:HI[@ROW]")
+            on = np.arange(Tb) >= row
+            spec[idx] = (np.where(on, lo_v, -np.inf), np.where(on, hi_v, np.inf))      # (before ROW and on an infinite side: the model's own bound)
+        try:
+            bounds = box_bounds(m, Tb, spec)
+        except ValueError as e:
+            ap.error(str(e))
+    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P, bounds=bounds)
     t0 = time.perf_counter()
     run = cl.run_decoupled if a.persistent else cl.run_on_device
     out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1)
@@ -91,6 +113,9 @@ def main():
         du = out["disturbance_used"]
         print(f"plant mismatch: steps with disturbance_used > 1 (model error + noise outside the box the tubes assume): {np.mean(du > 1.0):.3f}; "
               f"largest {np.nanmax(du):.2f}; largest |model error| {np.abs(out['model_error']).max():.3e}")
+    if bounds is not None:
+        print(f"bounds {' '.join(a.bound)}: MPC steps solved {out['success'].mean():.3f}; smallest constraint_margin {out['constraint_margin'].min():.3e} "
+              f"(negative: the measured state or applied input left the box in force at that step)")
     if Xref is not None:
         rows = np.minimum(np.arange(steps), len(Xref) - 1)
         err = np.linalg.norm(out["state_trajectory"].transpose(0, 2, 1) - Xref[rows][None], axis=2).mean(axis=0)      # (steps,)

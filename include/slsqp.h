@@ -215,6 +215,29 @@ int slsqp_plant_param_count(int model_id);
 const char *slsqp_plant_param_name(int model_id, int i);
 int slsqp_plant_param_defaults(int model_id, double *out, int len);
 int slsqp_cl_set_plant_params(slsqp_handle *h, const double *P, int np, int per_instance, int loc);
+
+/* Box bounds over MPC time in the on-device closed loops: a property of the handle (like the reference and the plant parameters: slsqp_opts keeps its
+   layout).  slsqp_set_model / slsqp_set_constraints give ONE box for the batch that never changes; this call gives its right-hand sides as rows over
+   MPC time, shared by the batch or one set per instance: an actuator limit per vehicle, a corridor along a tracked path, a rate limit that closes in
+   near touchdown -- the reference's update_dynamics_list(..., g_list, ...) hook.  G = [I; -I] stays; the rows are in the model's own layout:
+       g  (T, ni)   = [hi; -lo] over [x; u]      gf (T, ni_f) = [hi; -lo] over x        (per_instance = 0)
+       g  (B,T,ni), gf (B,T,ni_f)                                                      (per_instance = 1)
+   host or device (`loc`), copied by the call.  gf = NULL: every terminal row is the model's own gf.  Row t belongs to MPC time t counted from
+   slsqp_cl_init: at MPC step s stage k < N uses g row min(s + k, T - 1) and the terminal stage gf row min(s + N, T - 1) -- the last row is held, so
+   T = 1 is a constant box (per instance: a parameter study) -- and all SCP iterations of one step use the same window.  What changes: the stage rows
+   g_k = g_row - G [x_k; u_k], the terminal row g_N = gf_row - Gf x_N of QP #1, and the terminal row gf_row - backoff_f of the tightened QP (un-shifted,
+   as the model's gf is today).  H, q, A, B, c, E, the sweeps and the QP kernels do not see it; the stage-0 gate (slsqp_set_x0_box_tol, "x0_viol")
+   reads the stage-0 rows of the step's own window.  Honoured by slsqp_linearize (the handle's step count), slsqp_cl_step, slsqp_cl_run (persistent and
+   round-based), slsqp_cl_run_scp and slsqp_nominal_solve (window of step 0); slsqp_solve, slsqp_update_dynamics and slsqp_qp_* bring their own g and
+   are not affected.  Survives slsqp_cl_init; may be replaced between runs and between two slsqp_cl_step calls (the setter waits for the handle's stream; the step
+   count goes on), not while a call is in flight; T = 0 with g = NULL clears (the default: the model's box,
+   and the kernels of a handle that never had bounds).  With gf = NULL the model's gf is read at the call: set the constraints first.
+   Errors (< 0, slsqp_last_error; the previous bounds stay in force): no slsqp_set_model yet, a handle with a general G, T < 0, T = 0 with g, T > 0
+   without g, per_instance outside {0, 1}, a NaN or -inf entry, a row with hi < lo in any component (g[i] + g[nz+i] < 0, likewise gf).  +inf is
+   allowed and is "no bound", exactly as 1e20 is.
+   Results (slsqp_get, slsqp_result_bytes): "bounds_g" (T, ni) and "bounds_gf" (T, ni_f) per instance (a shared set repeated; without bounds the model's
+   box with T = 1). */
+int slsqp_cl_set_bounds(slsqp_handle *h, const double *g, const double *gf, int T, int per_instance, int loc);
 int slsqp_sync(slsqp_handle *h);
 
 /* ---- the step in front of the path: batched linearisation (SCP_SLS.update_jacobian, solver/SCP_SLS_jit.py:251-366) ---------

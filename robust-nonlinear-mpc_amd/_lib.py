@@ -55,7 +55,7 @@ EXPORTS = [
     "slsqp_sync", "slsqp_qp_nnz", "slsqp_qp_update_data_mat", "slsqp_qp_update_data_vec", "slsqp_qp_solve", "slsqp_sweep",
     "slsqp_last_timing", "slsqp_kernel_timing", "slsqp_stream", "slsqp_set_model", "slsqp_set_E", "slsqp_linearize", "slsqp_cl_init", "slsqp_cl_step", "slsqp_nominal_solve", "slsqp_set", "slsqp_cl_log", "slsqp_selftest", "slsqp_result_bytes", "slsqp_cl_run", "slsqp_cl_run_stats", "slsqp_cl_run_scp", "slsqp_set_x0_box_tol", "slsqp_get_x0_box_tol",
     "slsqp_set_solve_waves", "slsqp_get_solve_waves", "slsqp_ne_solve", "slsqp_cl_set_reference",
-    "slsqp_plant_param_count", "slsqp_plant_param_name", "slsqp_plant_param_defaults", "slsqp_cl_set_plant_params",
+    "slsqp_plant_param_count", "slsqp_plant_param_name", "slsqp_plant_param_defaults", "slsqp_cl_set_plant_params", "slsqp_cl_set_bounds",
 ]
 
 _lib = None
@@ -123,6 +123,7 @@ def load():
     lib.slsqp_plant_param_name.restype = C.c_char_p
     lib.slsqp_plant_param_defaults.argtypes = [C.c_int, dp, C.c_int]
     lib.slsqp_cl_set_plant_params.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
+    lib.slsqp_cl_set_bounds.argtypes = [vp, dp, dp, C.c_int, C.c_int, C.c_int]
     lib.slsqp_ne_solve.argtypes = [vp, C.c_int, C.c_int, dp, dp, C.c_double, dp, dp, dp, ip, C.c_int]
     lib.slsqp_selftest.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, C.c_int]
     lib.slsqp_stream.argtypes = [vp]

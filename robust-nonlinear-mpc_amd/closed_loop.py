@@ -22,14 +22,15 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
         state never fails a step on its own (slsqp_set_x0_box_tol).
         solve_waves: 1, or 2 / 4 / 8 waves per instance for the QP solves (slsqp_set_solve_waves: for one plant or a handful); run_decoupled then
         takes the step-by-step loop, the persistent kernels being one wave per instance.
         reference: see set_reference (None: the cost is around the origin of the raw state, as in the reference's scripts).
-        plant_params: see set_plant_params (None: the true plant is the controller's model)."""
+        plant_params: see set_plant_params (None: the true plant is the controller's model).
+        bounds: see set_bounds (None: the model's box, the same for every instance and every step)."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -47,6 +48,25 @@ class ClosedLoopMPC:
             self.set_reference(reference)
         if plant_params is not None:
             self.set_plant_params(plant_params)
+        if bounds is not None:
+            self.set_bounds(bounds)
+
+    def set_bounds(self, bounds, gf=None):
+        """The box in force from the next reset() on: a pair (g, gf) (tuple or list) or g, gf -- rows over MPC time in the model's layout [hi; -lo], (T,ni) / (T,ni_f)
+        shared by the batch or (B,T,ni) / (B,T,ni_f) per instance, row t for MPC step t after reset(), last row held (BatchedFastSLS.set_bounds;
+        bounds.box_bounds builds them from per-component limits); gf None: the model's terminal box; None: the model's box again.  Logged runs then
+        hold `constraint_margin` (steps, B): the smallest distance of the measured state and applied input to the box in force at that time (negative:
+        outside)."""
+        if isinstance(bounds, (tuple, list)) and len(bounds) == 2 and gf is None and np.ndim(bounds[0]) >= 2:      # (a pair, not two rows of one g)
+            bounds, gf = bounds
+        self.f.set_bounds(bounds, gf)
+
+    def _add_margin(self, out):
+        if self.f.bounds is not None:
+            from .bounds import constraint_margin
+            out.update(constraint_margin=constraint_margin(self.m, self.f.bounds[0], out["state_trajectory"], out["input_trajectory"]),
+                       bounds_g=np.array(self.f.bounds[0]), bounds_gf=np.array(self.f.bounds[1]))
+        return out
 
     def set_plant_params(self, plant_params):
         """Physical parameters of the TRUE plant from the next step on: a dict {name: scalar or (B,)}, an array (np,) or (B,np)
@@ -150,7 +170,7 @@ class ClosedLoopMPC:
         if f.plant_params is not None:
             me = f.get("log_model_error", (steps, m.nx))
             out.update(model_error=me.transpose(0, 2, 1).copy(), disturbance_used=self._disturbance_used(me), plant_params=np.array(f.plant_params))
-        return out
+        return self._add_margin(out)
 
     def _disturbance_used(self, me):
         """me (B,steps,nx): ddyn_p - ddyn of every plant step.  (steps,B): max_i |(E^-1 me)_i + w_i|, how much of the unit box the tubes assume the
@@ -237,7 +257,7 @@ class ClosedLoopMPC:
                 out.setdefault("model_error", np.zeros((B, m.nx, steps)))[:, :, i] = self.f.get("model_err", (m.nx,))
         if "model_error" in out:
             out.update(disturbance_used=self._disturbance_used(out["model_error"].transpose(0, 2, 1)), plant_params=np.array(self.f.plant_params))
-        return out
+        return self._add_margin(out)
 
     def save_npz(self, path, out, b=0):
         """Write instance b with exactly the key set the reference's plot()/loaders read (main_rocket...:189-206, 218-241); what the result
@@ -251,4 +271,7 @@ class ClosedLoopMPC:
                  t_jac=out["t_jac"], t_qp=out["t_qp"], t_riccati=out["t_riccati"],
                  **({} if "model_error" not in out else dict(      # (only a run with plant parameters: the key set of every other run is unchanged)
                      plant_params=out["plant_params"] if out["plant_params"].ndim == 1 else out["plant_params"][b], model_error=out["model_error"][b],
-                     disturbance_used=out["disturbance_used"][:, b])))
+                     disturbance_used=out["disturbance_used"][:, b])),
+                 **({} if "constraint_margin" not in out else dict(      # (only a run with bounds, likewise)
+                     constraint_margin=out["constraint_margin"][:, b], bounds_g=out["bounds_g"] if out["bounds_g"].ndim == 2 else out["bounds_g"][b],
+                     bounds_gf=out["bounds_gf"] if out["bounds_gf"].ndim == 2 else out["bounds_gf"][b])))

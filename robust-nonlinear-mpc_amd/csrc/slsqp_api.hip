@@ -18,6 +18,7 @@
 #include "slsqp_kernels.hpp"
 #include "slsqp_mw.hpp"
 #include "plant_params.hpp"
+#include "cl_bounds.hpp"
 
 using namespace slsqp;
 
@@ -78,6 +79,10 @@ struct slsqp_handle {
     // slsqp_cl_set_plant_params: one allocation [P (rows, np) | model_err (B, nx) | nz zeros]: parameter rows (pp_stride = np per instance, 0 shared; pp_P NULL: none),
     // ddyn_p - ddyn of the last plant step, and the one-row zero reference the _pp persistent kernels take for a handle without a reference
     double *pp_P = nullptr, *pp_merr = nullptr, *pp_zero_ref = nullptr, *lg_merr = nullptr; int pp_np = 0, pp_stride = 0; std::vector<double> pp_host;
+    // slsqp_cl_set_bounds: one allocation [rows (sets, T, ni + ni_f) | nz zeros]: the packed rows (bnd_stride = T (ni + ni_f) per instance, 0 shared;
+    // bnd_rows NULL: none) and the one-row zero reference variant 3 of the persistent kernels takes for a handle without a reference.  bnd_host: the packed
+    // rows on the host (slsqp_get "bounds_g" / "bounds_gf"); g_raw_host / gf_raw_host: the model's box, served where no bounds are set.
+    double *bnd_rows = nullptr, *bnd_zero_ref = nullptr; int bnd_T = 0; size_t bnd_stride = 0; std::vector<double> bnd_host, g_raw_host, gf_raw_host;
     double *cr = nullptr;       // (B,N,3,nx,nx) scratch of the cyclic reduction (slsqp_mw.hpp), allocated by the first launch that needs it
     int ne_waves = 0;           // slsqp_ne_solve: the path whose factors the last factorising call left (0 = none)
     double x0_tol_dev = 0.0;    // the tolerance of the x0 gate the device currently holds (kkt[8 B]; written when a launch asks for another one)
@@ -106,6 +111,7 @@ struct slsqp_handle {
 };
 
 static RefArgs ref_args(slsqp_handle *h) { return RefArgs{h->ref_Y, h->ref_T, h->ref_stride}; }
+static BndArgs bnd_args(slsqp_handle *h, int step, const int *stepno) { return BndArgs{h->bnd_rows, h->bnd_T, h->bnd_stride, stepno, step}; }
 static PlantArgs plant_args(slsqp_handle *h) { return PlantArgs{h->pp_P, h->pp_stride, h->pp_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps}; }
 // A run-time choice among three as a template argument: f(std::integral_constant<int, i>) for i in 0..2, false for any other i.  f is a generic
 // lambda and names the constant as M() / V(); an instantiation that is missing stops the build.
@@ -117,6 +123,13 @@ static bool dispatch3(int i, F &&f) {
     case 2: f(std::integral_constant<int, 2>{}); return true;
     }
     return false;
+}
+// the same among five (the variants of the persistent kernels)
+template <class F>
+static bool dispatch5(int i, F &&f) {
+    if (i == 3) { f(std::integral_constant<int, 3>{}); return true; }
+    if (i == 4) { f(std::integral_constant<int, 4>{}); return true; }
+    return dispatch3(i, f);
 }
 // the handle's plant model (0 pendulum, 1 quadrotor, 2 rocket): every launch of a kernel that is a template of the model goes through here
 template <class F>
@@ -274,6 +287,7 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     if (h->cl_W) hipFree(h->cl_W);
     if (h->ref_Y) hipFree(h->ref_Y);
     if (h->pp_P) hipFree(h->pp_P);
+    if (h->bnd_rows) hipFree(h->bnd_rows);
     if (h->qplog) hipFree(h->qplog);
     if (h->x0vlog) hipFree(h->x0vlog);
     if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
@@ -369,6 +383,7 @@ extern "C" int slsqp_set_constraints(slsqp_handle *h, const double *G, const dou
     HIPCHK(hipMemcpy(h->Gd, G, sizeof(double) * (size_t)ni * nz, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->Gfd, Gf, sizeof(double) * (size_t)nif * nx, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->gf_raw, gf, sizeof(double) * nif, hipMemcpyHostToDevice));
+    h->gf_raw_host.assign(gf, gf + nif);
     h->have_cons = true;
     return 0;
 }
@@ -613,8 +628,9 @@ struct ChainArgs {
 };
 // BLK: c_ lies in the argument block of a persistent closed-loop kernel (args_here, slsqp_kernels.hpp): the head of the chain, of each pass, of the
 // part behind QP #1 and of the tail read what they use afresh.
-template <int NX, int NU, bool BLK = false>
-__device__ __forceinline__ int rti_chain_dev(const ChainArgs &c_, int b, int lane, double *sm) {
+// BND: the tightening reads the terminal row of the instance's window of the bounds (bdp: in the block too with BLK, else the kernel's parameter).
+template <int NX, int NU, bool BLK = false, bool BND = false>
+__device__ __forceinline__ int rti_chain_dev(const ChainArgs &c_, int b, int lane, double *sm, const BndArgs *bdp = nullptr) {
     const ChainArgs *cp = &c_;
     unsigned long long t0 = wall_clock64(), t1 = t0, t2 = t0, deadline = ~0ULL;
     int lg = 0;
@@ -657,7 +673,7 @@ __device__ __forceinline__ int rti_chain_dev(const ChainArgs &c_, int b, int lan
                 wla::wsync();
             }
             wla::wsync_mem();
-            tighten_dev(c.ta, b, lane, 64);
+            tighten_dev<BND, BLK>(c.ta, b, lane, 64, bdp);
             wla::wsync_mem();
         }
         t2 = wall_clock64();
@@ -682,6 +698,15 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_rti_chain(Cha
     if (c.runm && !c.runm[b]) return;
     extern __shared__ double sm[];
     rti_chain_dev<NX, NU>(c, b, lane, sm);
+}
+// the same for a handle with bounds (slsqp_cl_step at large batches, the rounds of slsqp_cl_run)
+template <int NX, int NU>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_rti_chain_bnd(ChainArgs c, BndArgs bd) {
+    int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= c.q.B) return;
+    if (c.runm && !c.runm[b]) return;
+    extern __shared__ double sm[];
+    rti_chain_dev<NX, NU, false, true>(c, b, lane, sm, &bd);
 }
 
 // ---- the whole closed loop as ONE persistent launch (slsqp_cl_run, opts.cl_persistent) ------------------------------------------------
@@ -775,11 +800,12 @@ struct ScpLoopArgs {
     LoopArgs L;
     int max_it, converge, rti_steps;
     int *nsolves;
+    BndArgs bd;      // slsqp_cl_set_bounds (variants 3 and 4 only; behind everything else, so no other field moves)
 };
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
-template <int MODEL, bool REF = false>
-__device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const RefArgs *rf = nullptr) {
+template <int MODEL, bool REF = false, bool BND = false>
+__device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const RefArgs *rf = nullptr, const BndArgs *bd = nullptr) {
     const LoopArgs *Lp = &L_;
     const LoopArgs &L = args_here<true>(Lp);
     constexpr int NX = dyn::Dims<MODEL>::NX;
@@ -802,7 +828,7 @@ __device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const 
     if (lane == 0) { L.call_ids[b] += 1.0; L.sa.scp_success[b] = 0; L.sa.scp_iters[b] = 0; }
     wla::wsync_mem();
     CLSTAMP(4);
-    lin_wave<MODEL, REF>(L.lin, L.ba, b, lane, rf, s);      // (REF: the window of the instance's OWN step count)
+    lin_wave<MODEL, REF, BND>(L.lin, L.ba, b, lane, rf, s, bd);      // (REF, BND: the window of the instance's OWN step count)
     CLSTAMP(5);
     if (lane < NX) L.cl.x0arg[(size_t)b * NX + lane] = L.cl.Xn[(size_t)b * (L.cl.N + 1) * NX + lane] - L.cl.xmeas[(size_t)b * NX + lane];
     wla::wsync_mem();
@@ -842,11 +868,16 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
     CLSTAMP(10);
     return (s + 1 < L.steps) ? s + 1 : 0;
 }
-// The persistent closed loop, ONE body with three variants.  VAR 0: plain; 1: tracks a reference (slsqp_cl_set_reference: the linear cost of
+// The persistent closed loop, ONE body with five variants.  VAR 0: plain; 1: tracks a reference (slsqp_cl_set_reference: the linear cost of
 // cl_step_begin reads rf); 2: tracks a reference and steps the plant with the instance's own parameters (slsqp_cl_set_plant_params: cl_step_end reads
-// pa; without a reference rf is one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference).  A variant is passed empty
-// rf / pa where it reads none.  The two calls that name VAR are all that depends on it.  The statements stand in the kernel, not in a function it
+// pa; without a reference rf is one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference); 3 and 4: variants 1 and 2
+// with the box bounds of slsqp_cl_set_bounds (the linearisation's g_k / g_N and the chain's terminal tightened row read blk->bd; a handle with bounds
+// but no reference passes the zero row, as variant 2 does).  A variant is passed empty rf / pa where it reads none.  The three calls that name VAR,
+// through the constants below, are all that depends on it.  The statements stand in the kernel, not in a function it
 // calls, and the next per-handle option is a further VAR value, not a further kernel.
+constexpr bool var_ref(int VAR) { return VAR > 0; }
+constexpr bool var_pp(int VAR) { return VAR == 2 || VAR == 4; }
+constexpr bool var_bnd(int VAR) { return VAR > 2; }
 template <int MODEL, int VAR>
 __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
@@ -872,13 +903,13 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const
             if (lane == 0) atomicAdd(L.busy + 11, wall_clock64() - tp_);
 #endif
         }
-        cl_step_begin<MODEL, (VAR > 0)>(L, b, lane, VAR > 0 ? &rf : nullptr);
+        cl_step_begin<MODEL, var_ref(VAR), var_bnd(VAR)>(L, b, lane, var_ref(VAR) ? &rf : nullptr, var_bnd(VAR) ? &blk->bd : nullptr);
         b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
         asm volatile("" : "+v"(lane));
-        rti_chain_dev<NX, NU, true>(L.c, b, lane, sm);
+        rti_chain_dev<NX, NU, true, var_bnd(VAR)>(L.c, b, lane, sm, var_bnd(VAR) ? &blk->bd : nullptr);
         wla::wsync_mem();
         asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, (VAR > 1)>(L, b, lane, VAR > 1 ? &pa : nullptr));
+        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, var_pp(VAR)>(L, b, lane, var_pp(VAR) ? &pa : nullptr));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
         const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
@@ -931,13 +962,13 @@ __device__ CLW_FN void cl_scp_step_begin(const LoopArgs &L_, int b, int lane) {
     wla::wsync_mem();
 }
 // start of SCP iteration ii: linearisation (instances still iterating), x0 pin, call id, solve start
-template <int MODEL, bool REF = false>
-__device__ CLW_FN void cl_scp_iter_begin(const LoopArgs &L_, int b, int lane, int ii, const RefArgs *rf = nullptr) {
+template <int MODEL, bool REF = false, bool BND = false>
+__device__ CLW_FN void cl_scp_iter_begin(const LoopArgs &L_, int b, int lane, int ii, const RefArgs *rf = nullptr, const BndArgs *bd = nullptr) {
     const LoopArgs *Lp = &L_;
     const LoopArgs &L = args_here<true>(Lp);
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int act = __builtin_amdgcn_readfirstlane(L.scp_active[b]);
-    if (ii == 0 || act) lin_wave<MODEL, REF>(L.lin, L.ba, b, lane, rf, REF ? L.stepno[b] : 0);      // (REF: every iteration of the step uses the window of the instance's own step count)
+    if (ii == 0 || act) lin_wave<MODEL, REF, BND>(L.lin, L.ba, b, lane, rf, (REF || BND) ? L.stepno[b] : 0, bd);      // (REF, BND: every iteration of the step uses the window of the instance's own step count)
     if (lane < NX) L.cl.x0arg[(size_t)b * NX + lane] = L.cl.Xn[(size_t)b * (L.cl.N + 1) * NX + lane] - L.cl.xmeas[(size_t)b * NX + lane];
     if (lane == 0) L.call_ids[b] += 1.0;
     wla::wsync_mem();
@@ -985,8 +1016,8 @@ __device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S_, int b, int lane, in
 // one fast-SLS solve of rti_steps steps of one instance by one wave: what solve_impl launches (fast_SLS_jit.py:278-296).  QP i of the call gets the
 // arguments launch_qp builds for it: the first one q1's (warm per opts.warm_start, slot 0, no iterate copy to restart from), the middle ones warm,
 // slot 0, restart allowed, the last one q2's; the horizon shift only reaches the first and the last QP of the first solve after the shift
-template <int NX, int NU>
-__device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int lane, double *sm, int rti_steps, int shifted) {
+template <int NX, int NU, bool BND = false>
+__device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int lane, double *sm, int rti_steps, int shifted, const BndArgs *bdp = nullptr) {
     const ChainArgs *cp = &c_;
 #pragma unroll 1
     for (int i = 0; i <= rti_steps; i++) {
@@ -1027,7 +1058,7 @@ __device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int la
             }
         }
         wla::wsync_mem();
-        tighten_dev(c.ta, b, lane, 64);
+        tighten_dev<BND, true>(c.ta, b, lane, 64, bdp);
         wla::wsync_mem();
     }
     const ChainArgs &c = args_here<true>(cp);
@@ -1037,8 +1068,8 @@ __device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int la
     }
     wla::wsync_mem();
 }
-// one body for the three variants, as k_cl_loop above: VAR > 0 reads the tracked linear cost in cl_scp_iter_begin, VAR > 1 the plant parameters in
-// cl_scp_step_end
+// one body for the five variants, as k_cl_loop above: var_ref reads the tracked linear cost in cl_scp_iter_begin, var_pp the plant parameters in
+// cl_scp_step_end, var_bnd the bounds in cl_scp_iter_begin and sls_solve_dev
 template <int MODEL, int VAR>
 __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
@@ -1061,10 +1092,10 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(c
 #pragma unroll 1
         for (int ii = 0; ii < S.max_it; ii++) {
             asm volatile("" : "+v"(lane));
-            cl_scp_iter_begin<MODEL, (VAR > 0)>(L, b, lane, ii, VAR > 0 ? &rf : nullptr);
+            cl_scp_iter_begin<MODEL, var_ref(VAR), var_bnd(VAR)>(L, b, lane, ii, var_ref(VAR) ? &rf : nullptr, var_bnd(VAR) ? &blk->bd : nullptr);
             b = __builtin_amdgcn_readfirstlane(b);
             asm volatile("" : "+v"(lane));
-            sls_solve_dev<NX, NU>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0);
+            sls_solve_dev<NX, NU, var_bnd(VAR)>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0, var_bnd(VAR) ? &blk->bd : nullptr);
             asm volatile("" : "+v"(lane));
             const int act = __builtin_amdgcn_readfirstlane(cl_scp_iter_end<MODEL>(L, b, lane, ii, S.converge));
             b = __builtin_amdgcn_readfirstlane(b);
@@ -1072,7 +1103,7 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(c
             if (S.converge && !act) break;
         }
         asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL, (VAR > 1)>(S, b, lane, nsolves, VAR > 1 ? &pa : nullptr));
+        const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL, var_pp(VAR)>(S, b, lane, nsolves, var_pp(VAR) ? &pa : nullptr));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
         const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
@@ -1453,12 +1484,13 @@ static ChainArgs make_chain_args(slsqp_handle *h, const slsqp_opts &o, const int
 
 // the fused RTI chain (k_rti_chain): one launch for QP #1 -> eta -> shared Riccati + propagation -> tightened bounds -> QP #2
 template <int NX, int NU>
-static int launch_chain_t(slsqp_handle *h, ChainArgs &c) {
+static int launch_chain_t(slsqp_handle *h, ChainArgs &c, const BndArgs *bd) {
     const size_t lds = sizeof(double) * std::max({(size_t)qp_lds_doubles<NX, NU>(h->d.N), (size_t)(2 * h->n + 8), (size_t)sweep_lds_doubles<NX, NU>(), (size_t)sweep_prop_lds_doubles<NX, NU>()});
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     h->ne_waves = 0;      // (slsqp_ne_solve's factors do not survive a QP solve)
-    hipLaunchKernelGGL((k_rti_chain<NX, NU>), dim3(h->B), dim3(64), lds, h->st, c);
+    if (bd) hipLaunchKernelGGL((k_rti_chain_bnd<NX, NU>), dim3(h->B), dim3(64), lds, h->st, c, *bd);
+    else hipLaunchKernelGGL((k_rti_chain<NX, NU>), dim3(h->B), dim3(64), lds, h->st, c);
     if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1497,7 +1529,9 @@ static void tl_take(slsqp_handle *h) {     // accumulators -> the handle's timin
 }
 
 // no_sync: return with the launches queued (the caller synchronises the stream later and then calls tl_take)
-static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_opts *opts, const int *active, bool no_sync = false) {
+// bd: the bounds whose window gives the tightening's terminal row (the closed-loop entry points of a handle with bounds), or NULL: the model's gf
+// (slsqp_solve brings its own g and always passes NULL)
+static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_opts *opts, const int *active, bool no_sync = false, const BndArgs *bd = nullptr) {
     hipSetDevice(h->dev);
     if (h->general_G) return fail("general G: only the sweep-level boundary (slsqp_sweep) is available; the QP solver needs box constraints G = [I;-I]");
     if (!h->have_costs || !h->have_cons || !h->have_dyn) return fail("set_costs, set_constraints and update_dynamics must be called first");
@@ -1563,7 +1597,7 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
         } else flag_nonfinite(h, active, h->alive, h->infeas);      // (slsqp_cl_run's rounds and k_cl_loop linearise their own data; the NaN-keeping certificate guards them)
         const int tl_c = tl_begin(h, 4);
         int rc = -1;
-#define X(NX_, NU_) if (d.nx == NX_ && d.nu == NU_) rc = launch_chain_t<NX_, NU_>(h, c);
+#define X(NX_, NU_) if (d.nx == NX_ && d.nu == NU_) rc = launch_chain_t<NX_, NU_>(h, c, bd);
         SLSQP_DIM_LIST
 #undef X
         if (rc) return -1;
@@ -1590,7 +1624,8 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
         if (launch_sweep(h, h->mask, h->eta, h->eta_f, o.eps_backoff, /* beta == eps for every column right after initialize_backoff */ i == 0)) return -1;
         tl_end(h, tl_s);
         TightenArgs ta{B, d.N, d.nx, d.nu, d.ni, d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, h->mask, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, 1, h->ct_part, h->cost_tube};
-        hipLaunchKernelGGL(k_tighten, dim3(B), dim3(128), 0, h->st, ta);
+        if (bd) hipLaunchKernelGGL(k_tighten_bnd, dim3(B), dim3(128), 0, h->st, ta, *bd);
+        else hipLaunchKernelGGL(k_tighten, dim3(B), dim3(128), 0, h->st, ta);
         if (rti) continue;      // RTI mode (every closed-loop script): nothing to decide on the host, the stream runs on
         int nmask = 0;
         HIPCHK(hipMemcpyAsync(&nmask, h->counter, sizeof(int), hipMemcpyDeviceToHost, h->st));
@@ -1635,6 +1670,8 @@ extern "C" int slsqp_kernel_timing(slsqp_handle *h, double *out8, int len) {
 extern "C" long long slsqp_result_bytes(slsqp_handle *h, const char *name) {
     if (!strcmp(name, "plant_params")) return h->model_id < 0 ? -1LL : (long long)sizeof(double) * plant_params::count(h->model_id);
     if (!strcmp(name, "model_err")) return (long long)sizeof(double) * h->d.nx;
+    if (!strcmp(name, "bounds_g")) return (long long)sizeof(double) * h->d.ni * (h->bnd_rows ? h->bnd_T : 1);
+    if (!strcmp(name, "bounds_gf")) return (long long)sizeof(double) * h->d.ni_f * (h->bnd_rows ? h->bnd_T : 1);
     auto it = h->named.find(name);
     return it == h->named.end() ? -1LL : (long long)it->second.second;
 }
@@ -1753,9 +1790,60 @@ static int get_plant_named(slsqp_handle *h, const char *name, void *out, int loc
     return 1;
 }
 
+// Box bounds over MPC time (include/slsqp.h): validated and packed on the host (cl_bounds.hpp) into rows [g(t); gf(t)], uploaded into a new buffer,
+// and only then the previous buffer is dropped: a refused call leaves the previous bounds in force.
+extern "C" int slsqp_cl_set_bounds(slsqp_handle *h, const double *g, const double *gf, int T, int per_instance, int loc) {
+    hipSetDevice(h->dev);
+    if (h->general_G) return fail("slsqp_cl_set_bounds: general G: the bounds are the right-hand sides of a box G = [I;-I]");
+    if (h->model_id < 0) return fail("slsqp_cl_set_bounds: slsqp_set_model must be called first");
+    if (loc != SLSQP_HOST && loc != SLSQP_DEVICE) return fail("slsqp_cl_set_bounds: loc must be SLSQP_HOST or SLSQP_DEVICE");
+    std::string why;
+    if (!cl_bounds::check_call(g, T, per_instance, &why)) return fail("slsqp_cl_set_bounds: " + why);
+    HIPCHK(hipStreamSynchronize(h->st));      // no launch may still read the buffer that is replaced
+    if (T == 0) {
+        if (h->bnd_rows) hipFree(h->bnd_rows);
+        h->bnd_rows = h->bnd_zero_ref = nullptr; h->bnd_T = 0; h->bnd_stride = 0; h->bnd_host.clear();
+        return 0;
+    }
+    if (!gf && !h->have_cons) return fail("slsqp_cl_set_bounds: gf = NULL repeats the model's gf: slsqp_set_constraints must be called first");
+    const size_t ni = h->d.ni, nif = h->d.ni_f, sets = per_instance ? (size_t)h->B : 1, rows = sets * (size_t)T;
+    std::vector<double> hg(rows * ni), hgf(gf ? rows * nif : 0), packed;
+    const hipMemcpyKind kind = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
+    HIPCHK(hipMemcpy(hg.data(), g, sizeof(double) * hg.size(), kind));
+    if (gf) HIPCHK(hipMemcpy(hgf.data(), gf, sizeof(double) * hgf.size(), kind));
+    if (!cl_bounds::pack(hg.data(), gf ? hgf.data() : nullptr, h->gf_raw_host.data(), sets, T, (int)ni, (int)nif, &packed, &why)) return fail("slsqp_cl_set_bounds: " + why);
+    const size_t nR = packed.size(), nZ = (size_t)h->nz;
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (nR + nZ) + 64));
+    if (hipMemset(buf, 0, sizeof(double) * (nR + nZ)) != hipSuccess || hipMemcpy(buf, packed.data(), sizeof(double) * nR, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(buf);
+        return fail("slsqp_cl_set_bounds: upload failed");
+    }
+    if (h->bnd_rows) hipFree(h->bnd_rows);
+    h->bnd_rows = buf; h->bnd_zero_ref = buf + nR;
+    h->bnd_T = T; h->bnd_stride = per_instance ? (size_t)T * (ni + nif) : 0; h->bnd_host.swap(packed);
+    return 0;
+}
+// slsqp_get names of the bounds: bounds_g (B, T, ni), bounds_gf (B, T, ni_f) (a shared set repeated; without bounds the model's box with T = 1).
+// Returns 1 when `name` was one of them and has been served, 0 when not, -1 on error.
+static int get_bounds_named(slsqp_handle *h, const char *name, void *out, int loc) {
+    const bool is_g = !strcmp(name, "bounds_g"), is_f = !strcmp(name, "bounds_gf");
+    if (!is_g && !is_f) return 0;
+    if (h->model_id < 0 || !h->have_cons) return fail(std::string(name) + ": slsqp_set_model and slsqp_set_constraints must be called first");
+    const size_t ni = h->d.ni, nif = h->d.ni_f, W = ni + nif, T = h->bnd_rows ? (size_t)h->bnd_T : 1, w = is_g ? ni : nif, off = is_g ? 0 : ni;
+    std::vector<double> v((size_t)h->B * T * w);
+    for (size_t b = 0; b < (size_t)h->B; b++)
+        for (size_t t = 0; t < T; t++)
+            for (size_t i = 0; i < w; i++)
+                v[(b * T + t) * w + i] = h->bnd_rows ? h->bnd_host[(h->bnd_stride ? b * T * W : 0) + t * W + off + i] : (is_g ? h->g_raw_host[i] : h->gf_raw_host[i]);
+    HIPCHK(hipMemcpy(out, v.data(), sizeof(double) * v.size(), loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice));
+    return 1;
+}
+
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
     if (const int r = get_plant_named(h, name, out, loc)) return r < 0 ? -1 : 0;
+    if (const int r = get_bounds_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (!h->pp_P && h->lg_merr && !strcmp(name, "log_model_error")) HIPCHK(hipMemsetAsync(h->lg_merr, 0, sizeof(double) * (size_t)h->B * h->log_steps * h->d.nx, h->st));      // (a handle without parameters: all zeros, whatever an earlier run with parameters left)
     auto it = h->named.find(name);
     if (it == h->named.end()) return fail(std::string("unknown result name: ") + name);
@@ -1817,6 +1905,7 @@ extern "C" int slsqp_set_model(slsqp_handle *h, int model_id, const double *g_ra
     const int want_nx = model_id == 0 ? 4 : (model_id == 1 ? 13 : (model_id == 2 ? 17 : -1));
     if (want_nx != h->d.nx || h->d.nw != h->d.nx) return fail("model id does not match the handle's dimensions (0 pendulum, 1 quadrotor, 2 rocket; nw = nx)");
     HIPCHK(hipMemcpy(h->g_raw, g_raw, sizeof(double) * h->d.ni, hipMemcpyHostToDevice));
+    h->g_raw_host.assign(g_raw, g_raw + h->d.ni);
     h->model_id = model_id;
     return 0;
 }
@@ -1826,7 +1915,7 @@ extern "C" int slsqp_set_E(slsqp_handle *h, const double *E, int loc) {
     return put_E(h, E, loc);
 }
 
-// step / stepno: the MPC step whose window of the reference forms q (a handle with a reference only): `step` for every instance, or stepno[b]
+// step / stepno: the MPC step whose window of the reference forms q and whose window of the bounds forms g, gN (a handle with a reference / with bounds only): `step` for every instance, or stepno[b]
 static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int loc, const int *run, int step, const int *stepno = nullptr) {
     hipSetDevice(h->dev);
     if (h->model_id < 0 || !h->have_costs || !h->have_cons) return fail("set_model, set_costs and set_constraints must be called first");
@@ -1847,7 +1936,9 @@ static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int
     if (with_model(h, [&](auto M) {
             constexpr int NX = dyn::Dims<M()>::NX, NU = dyn::Dims<M()>::NU;
             hipLaunchKernelGGL((k_lin_val<M()>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<M()>), dim3(grid), dim3(blk), 0, h->st, a);
-            if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<NX, NU>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
+            if (h->bnd_rows && h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_bnd<NX, NU, true>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), bnd_args(h, step, stepno));
+            else if (h->bnd_rows) hipLaunchKernelGGL((k_lin_vec_bnd<NX, NU, false>), dim3(grid), dim3(256), 0, h->st, a, RefArgs{}, bnd_args(h, step, stepno));
+            else if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<NX, NU>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
             else hipLaunchKernelGGL((k_lin_vec<NX, NU>), dim3(grid), dim3(256), 0, h->st, a);
         })) return -1;
     BoundsArgs ba{h->B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, run};
@@ -1917,7 +2008,9 @@ extern "C" int slsqp_nominal_solve(slsqp_handle *h, int max_qp, double tol, doub
     auto eval = [&](int mode) {
         na.mode = mode;
         return with_model(h, [&](auto M) {
-            if (h->ref_T > 0) hipLaunchKernelGGL((k_nom_eval<M(), true>), dim3(B), dim3(128), 0, h->st, na, rf);
+            if (h->bnd_rows && h->ref_T > 0) hipLaunchKernelGGL((k_nom_eval_bnd<M(), true>), dim3(B), dim3(128), 0, h->st, na, rf, bnd_args(h, 0, nullptr));      // the box, window of step 0
+            else if (h->bnd_rows) hipLaunchKernelGGL((k_nom_eval_bnd<M(), false>), dim3(B), dim3(128), 0, h->st, na, rf, bnd_args(h, 0, nullptr));
+            else if (h->ref_T > 0) hipLaunchKernelGGL((k_nom_eval<M(), true>), dim3(B), dim3(128), 0, h->st, na, rf);
             else hipLaunchKernelGGL((k_nom_eval<M(), false>), dim3(B), dim3(128), 0, h->st, na, rf);
         });
     };
@@ -2018,7 +2111,8 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     }
     for (int ii = 0; ii < max_it; ii++) {
         hipLaunchKernelGGL(k_cl_x0arg, dim3(64), dim3(256), 0, h->st, a);
-        if (solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->scp_active, /* no_sync */ true)) return -1;
+        const BndArgs bd = bnd_args(h, h->cl_steps, nullptr);      // (the tightening's terminal row: the window of this step)
+        if (solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->scp_active, /* no_sync */ true, h->bnd_rows ? &bd : nullptr)) return -1;
         HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
         ScpArgs sa{ii, converge ? 1 : 0, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
         hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, sa);
@@ -2074,11 +2168,12 @@ static int launch_loop_t(slsqp_handle *h, bool S) {
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     hipEventRecord(h->ev[8], h->st);
-    // the kernels' variant: 2 plant parameters (which track a reference: without one, one row of zeros), 1 a reference, 0 neither (rf, pa empty, unread)
-    const int var = h->pp_P ? 2 : (h->ref_T > 0 ? 1 : 0);
-    const RefArgs rf = h->ref_T > 0 ? ref_args(h) : (var == 2 ? RefArgs{h->pp_zero_ref, 1, 0} : RefArgs{});
-    const PlantArgs pa = var == 2 ? plant_args(h) : PlantArgs{};
-    dispatch3(var, [&](auto V) {
+    // the kernels' variant: 2 plant parameters (which track a reference: without one, one row of zeros), 1 a reference, 0 neither (rf, pa empty, unread);
+    // with bounds 4 / 3 in place of 2 / 1 (3 also for a handle without a reference: the zero row).  The bounds themselves are in the block (make_loop_block)
+    const int var = h->bnd_rows ? (h->pp_P ? 4 : 3) : (h->pp_P ? 2 : (h->ref_T > 0 ? 1 : 0));
+    const RefArgs rf = h->ref_T > 0 ? ref_args(h) : (var >= 2 ? RefArgs{h->pp_P ? h->pp_zero_ref : h->bnd_zero_ref, 1, 0} : RefArgs{});
+    const PlantArgs pa = h->pp_P ? plant_args(h) : PlantArgs{};
+    dispatch5(var, [&](auto V) {
         if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
         else hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);
     });
@@ -2117,6 +2212,7 @@ static ScpLoopArgs make_loop_block(slsqp_handle *h, int steps, const double *dW,
     L.Q = ClQueue{h->clq_slots, h->clq_cap - 1u, (unsigned *)h->clq_ctl, (unsigned *)h->clq_ctl + 1, h->clq_ctl + 2, h->clq_ctl + 3};
     L.busy = h->cl_busy; L.t_begin = h->cl_tbegin;
     S.max_it = max_it; S.converge = scp_rti <= 0 ? 1 : 0; S.rti_steps = o.rti_steps; S.nsolves = h->qplog_nsolves;
+    if (h->bnd_rows) { S.bd.rows = h->bnd_rows; S.bd.T = h->bnd_T; S.bd.stride = h->bnd_stride; S.bd.stepno = h->cl_stepno; S.bd.step = 0; }      // (field by field: the padding stays zero; all zero bytes without bounds, and never read)
     return S;
 }
 // the block goes to the handle's device buffer on the handle's stream, ahead of the launch that reads it (and behind the previous launch, which may
@@ -2278,7 +2374,8 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         hipLaunchKernelGGL(k_cl_x0arg, dim3(64), dim3(256), 0, h->st, a, h->cl_begin);
         h->horizon_shifted = rounds > 0 ? 1 : 0;
         h->cl_round = true; h->cl_skip_begin = h->cl_skipb;
-        const int rc = solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->cl_runm, /* no_sync */ true);
+        const BndArgs bd = bnd_args(h, 0, h->cl_stepno);
+        const int rc = solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->cl_runm, /* no_sync */ true, h->bnd_rows ? &bd : nullptr);
         h->cl_round = false; h->cl_skip_begin = nullptr;
         if (rc) return -1;
         // end of the step for the instances whose chain is done: nominal += delta, primal_infeasibility, log entry, plant + noise, step counter

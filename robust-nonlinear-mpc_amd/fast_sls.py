@@ -102,6 +102,7 @@ class BatchedFastSLS:
         self._Q_reg_f = _c(np.eye(nx) if Q_reg_f is None else Q_reg_f)
         self.solver_forward = _SolverForward(self)
         self.plant_params = None
+        self.bounds = None
         self.dims = L.Dims(nx, nu, model.nw, self.N, model.ni, model.ni_f)
         self.n = model.nz * self.N + nx
         self.mb = self.N * (nx + model.ni) + model.ni_f
@@ -216,6 +217,23 @@ class BatchedFastSLS:
             P = _c(pack_plant_params(self.m, self.B, spec))
         L.check(self.lib.slsqp_cl_set_plant_params(self.h, _ptr(P), int(P.shape[-1]), int(P.ndim == 2), L.HOST))
         self.plant_params = P
+
+    def set_bounds(self, g, gf=None):
+        """Box bounds over MPC time of the closed-loop entry points (slsqp_cl_set_bounds): g (T,ni), gf (T,ni_f) shared by the batch or (B,T,ni),
+        (B,T,ni_f) per instance, rows [hi; -lo] in the model's layout (bounds.pack_bounds / bounds.box_bounds build them); row t belongs to MPC time t
+        counted from the reset that starts a run, the last row is held (T = 1: a constant box).  gf None: the model's own terminal box.  g None clears
+        the bounds (the model's box, the default).  Kept by the handle until replaced; linearize(), the closed-loop steps / runs and the nominal
+        initialiser then use the window of their MPC step.  self.bounds holds (g, gf) as set, or None."""
+        if g is None:
+            if gf is not None:
+                raise ValueError("set_bounds: gf without g")
+            L.check(self.lib.slsqp_cl_set_bounds(self.h, None, None, 0, 0, L.HOST))
+            self.bounds = None
+            return
+        from .bounds import pack_bounds
+        g, gf = pack_bounds(self.m, g, gf, self.B)
+        L.check(self.lib.slsqp_cl_set_bounds(self.h, _ptr(g), _ptr(gf), int(g.shape[-2]), int(g.ndim == 3), L.HOST))
+        self.bounds = (g, gf)
 
     def update_linear_cost(self, q):
         q = _c(q)

@@ -46,10 +46,10 @@ PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
 
 
 def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1,
-               reference=None, plant_params=None):
+               reference=None, plant_params=None, bounds=None):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
-    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params)
+    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds)
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
     rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
     want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
@@ -64,7 +64,7 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 
 
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
-                    budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None):
+                    budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
@@ -78,6 +78,9 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     plant_params: the true plant of every seed (ClosedLoopMPC.set_plant_params: a dict, an array (np,), or per seed: an array (S,np) or a dict with
     (S,) entries, S = len(seeds)); what is per seed is cut with the seeds into shards and slices, exactly as a per-seed reference.  The result then
     holds `model_error` (seeds, nx, steps), `disturbance_used` (steps, seeds) and `plant_params` as given.
+    bounds: the box of every seed over MPC time (ClosedLoopMPC.set_bounds: g or (g, gf)); arrays with a leading axis of len(seeds) ((S,T,ni),
+    (S,T,ni_f)) are per seed and are cut with the seeds into shards and slices, as a per-seed reference is.  The result then holds
+    `constraint_margin` (steps, seeds) and `bounds_g` / `bounds_gf` as given.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -108,6 +111,13 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
         if isinstance(plant_params, dict):
             return {k: cut(v, k) for k, v in plant_params.items()}
         return cut(plant_params, None)
+    def bound_rows(a, b):      # the same for per-seed bounds
+        gb, gfb = bounds if isinstance(bounds, (tuple, list)) and len(bounds) == 2 and np.ndim(bounds[0]) >= 2 else (bounds, None)
+        if np.ndim(gb) != 3:
+            return bounds
+        if len(gb) != S:
+            raise ValueError(f"run_monte_carlo: per-seed bounds need {S} leading rows, got {len(gb)}")
+        return (np.asarray(gb)[lo + a:lo + b], None if gfb is None else np.asarray(gfb)[lo + a:lo + b])
     cuts = [(B * k // K, B * (k + 1) // K) for k in range(K)]
     parts, err = [None] * K, []
 
@@ -122,6 +132,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["reference"] = ref_rows(*cuts[k])
             if plant_params is not None:
                 kw["plant_params"] = param_rows(*cuts[k])
+            if bounds is not None:
+                kw["bounds"] = bound_rows(*cuts[k])
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:
             err.append(e)
@@ -140,10 +152,12 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     for key, v in parts[0].items():
         if key in ("rounds", "loop_stats"):
             out[key] = [p[key] for p in parts]
-        elif key == "disturbance_used":      # (steps, seeds)
+        elif key in ("disturbance_used", "constraint_margin"):      # (steps, seeds)
             out[key] = np.concatenate([p[key] for p in parts], axis=1)
         elif key == "plant_params":      # as given: one vector, or a row per seed
             out[key] = v if v.ndim == 1 else np.concatenate([p[key] for p in parts], axis=0)
+        elif key in ("bounds_g", "bounds_gf"):      # as given: shared rows, or a set per seed
+            out[key] = v if v.ndim == 2 else np.concatenate([p[key] for p in parts], axis=0)
         elif isinstance(v, np.ndarray) and v.ndim >= 1 and v.shape[0] == cuts[0][1] - cuts[0][0] and key not in ("t_jac", "t_qp", "t_riccati"):
             out[key] = np.concatenate([p[key] for p in parts], axis=0)
         elif key in ("t_qp", "t_riccati", "t_jac"):
