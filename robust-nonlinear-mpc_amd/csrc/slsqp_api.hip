@@ -76,13 +76,13 @@ struct slsqp_handle {
     double x0_box_tol = 0.0;    // slsqp_set_x0_box_tol: the tolerance the following launches ask for
     int solve_waves = 1;        // slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = k_qp_solve_mw (one workgroup of that many waves per instance)
     double *ref_Y = nullptr; int ref_T = 0; size_t ref_stride = 0;      // slsqp_cl_set_reference: packed rows [x_ref; u_ref] (T, nz), per instance with ref_stride = T nz, shared with 0; ref_T = 0: none
-    // slsqp_cl_set_plant_params: one allocation [P (rows, np) | model_err (B, nx) | nz zeros]: parameter rows (pp_stride = np per instance, 0 shared; pp_P NULL: none),
-    // ddyn_p - ddyn of the last plant step, and the one-row zero reference the _pp persistent kernels take for a handle without a reference
-    double *pp_P = nullptr, *pp_merr = nullptr, *pp_zero_ref = nullptr, *lg_merr = nullptr; int pp_np = 0, pp_stride = 0; std::vector<double> pp_host;
-    // slsqp_cl_set_bounds: one allocation [rows (sets, T, ni + ni_f) | nz zeros]: the packed rows (bnd_stride = T (ni + ni_f) per instance, 0 shared;
-    // bnd_rows NULL: none) and the one-row zero reference variant 3 of the persistent kernels takes for a handle without a reference.  bnd_host: the packed
+    double *zero_ref = nullptr;      // (nz) zeros: the one-row reference the persistent kernels take for a handle with parameters or bounds and no reference (cl_options)
+    // slsqp_cl_set_plant_params: one allocation [P (rows, np) | model_err (B, nx)]: parameter rows (pp_stride = np per instance, 0 shared; pp_P NULL: none)
+    // and ddyn_p - ddyn of the last plant step
+    double *pp_P = nullptr, *pp_merr = nullptr, *lg_merr = nullptr; int pp_np = 0, pp_stride = 0; std::vector<double> pp_host;
+    // slsqp_cl_set_bounds: the packed rows (sets, T, ni + ni_f) (bnd_stride = T (ni + ni_f) per instance, 0 shared; bnd_rows NULL: none).  bnd_host: the packed
     // rows on the host (slsqp_get "bounds_g" / "bounds_gf"); g_raw_host / gf_raw_host: the model's box, served where no bounds are set.
-    double *bnd_rows = nullptr, *bnd_zero_ref = nullptr; int bnd_T = 0; size_t bnd_stride = 0; std::vector<double> bnd_host, g_raw_host, gf_raw_host;
+    double *bnd_rows = nullptr; int bnd_T = 0; size_t bnd_stride = 0; std::vector<double> bnd_host, g_raw_host, gf_raw_host;
     double *cr = nullptr;       // (B,N,3,nx,nx) scratch of the cyclic reduction (slsqp_mw.hpp), allocated by the first launch that needs it
     int ne_waves = 0;           // slsqp_ne_solve: the path whose factors the last factorising call left (0 = none)
     double x0_tol_dev = 0.0;    // the tolerance of the x0 gate the device currently holds (kkt[8 B]; written when a launch asks for another one)
@@ -110,9 +110,29 @@ struct slsqp_handle {
     double *lg_x, *lg_u, *lg_bx, *lg_bu, *lg_state, *lg_u0, *lg_pinf; int *lg_succ, *lg_it;
 };
 
-static RefArgs ref_args(slsqp_handle *h) { return RefArgs{h->ref_Y, h->ref_T, h->ref_stride}; }
-static BndArgs bnd_args(slsqp_handle *h, int step, const int *stepno) { return BndArgs{h->bnd_rows, h->bnd_T, h->bnd_stride, stepno, step}; }
-static PlantArgs plant_args(slsqp_handle *h) { return PlantArgs{h->pp_P, h->pp_stride, h->pp_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps}; }
+// The per-handle closed-loop options.  The persistent kernels' variant VAR is a set of these bits; the instantiated sets are
+// the five of with_loop_var: an option that needs the tracked cost's code path (parameters, bounds) carries the REF bit, and a handle without a
+// reference then passes one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference.
+constexpr int VAR_REF = 1, VAR_PP = 2, VAR_BND = 4;
+constexpr bool var_ref(int VAR) { return VAR & VAR_REF; }
+constexpr bool var_pp(int VAR) { return VAR & VAR_PP; }
+constexpr bool var_bnd(int VAR) { return VAR & VAR_BND; }
+// What a handle has set, asked by every launch site: ref / pp / bnd are the handle's own (the flags of the batch-wide kernels: REF and BND of k_lin_vec
+// and k_nom_eval, BND of k_tighten and k_rti_chain, pp for the plant step) and own_rf the handle's own reference, empty without one (what those two
+// kernels take); var, rf, pa are what the persistent kernels take (rf: own_rf, else the zero row where var has the REF bit, else empty; pa: empty
+// without parameters).
+struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; };
+static ClOptions cl_options(const slsqp_handle *h) {
+    ClOptions o{};
+    o.ref = h->ref_T > 0; o.pp = h->pp_P != nullptr; o.bnd = h->bnd_rows != nullptr;
+    o.var = ((o.ref || o.pp || o.bnd) ? VAR_REF : 0) | (o.pp ? VAR_PP : 0) | (o.bnd ? VAR_BND : 0);
+    if (o.ref) o.own_rf = RefArgs{h->ref_Y, h->ref_T, h->ref_stride};
+    o.rf = (o.var && !o.ref) ? RefArgs{h->zero_ref, 1, 0} : o.own_rf;
+    if (o.pp) o.pa = PlantArgs{h->pp_P, h->pp_stride, h->pp_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps};
+    return o;
+}
+// the bounds' table (empty without bounds) and the MPC step whose window a batch-wide launch reads, of the reference too: `step`, or stepno[b]
+static BndArgs bnd_args(const slsqp_handle *h, int step, const int *stepno) { return BndArgs{{h->bnd_rows, h->bnd_T, h->bnd_stride}, stepno, step}; }
 // A run-time choice among three as a template argument: f(std::integral_constant<int, i>) for i in 0..2, false for any other i.  f is a generic
 // lambda and names the constant as M() / V(); an instantiation that is missing stops the build.
 template <class F>
@@ -124,13 +144,24 @@ static bool dispatch3(int i, F &&f) {
     }
     return false;
 }
-// the same among five (the variants of the persistent kernels)
+// the same among the instantiated variants of the persistent kernels
 template <class F>
-static bool dispatch5(int i, F &&f) {
-    if (i == 3) { f(std::integral_constant<int, 3>{}); return true; }
-    if (i == 4) { f(std::integral_constant<int, 4>{}); return true; }
-    return dispatch3(i, f);
+static bool with_loop_var(int var, F &&f) {
+    switch (var) {
+    case 0: f(std::integral_constant<int, 0>{}); return true;
+    case VAR_REF: f(std::integral_constant<int, VAR_REF>{}); return true;
+    case VAR_REF | VAR_PP: f(std::integral_constant<int, VAR_REF | VAR_PP>{}); return true;
+    case VAR_REF | VAR_BND: f(std::integral_constant<int, VAR_REF | VAR_BND>{}); return true;
+    case VAR_REF | VAR_PP | VAR_BND: f(std::integral_constant<int, VAR_REF | VAR_PP | VAR_BND>{}); return true;
+    }
+    return false;
 }
+// a flag as a template argument: f(std::true_type / std::false_type), named B() in the generic lambda
+template <class F>
+static void with_flag(bool on, F &&f) { if (on) f(std::true_type{}); else f(std::false_type{}); }
+// the handle's own (REF, BND), for k_lin_vec and k_nom_eval
+template <class F>
+static void with_ref_bnd(const ClOptions &op, F &&f) { with_flag(op.ref, [&](auto REF) { with_flag(op.bnd, [&](auto BND) { f(REF, BND); }); }); }
 // the handle's plant model (0 pendulum, 1 quadrotor, 2 rocket): every launch of a kernel that is a template of the model goes through here
 template <class F>
 static int with_model(const slsqp_handle *h, F &&f) {
@@ -152,6 +183,30 @@ static int dalloc(std::vector<void *> &owned, T **p, size_t count) {
     return 0;
 }
 static void free_all(std::vector<void *> &owned) { for (void *p : owned) if (p) hipFree(p); owned.clear(); }
+// The device buffer of a per-handle closed-loop option (slsqp_cl_set_reference / _plant_params / _bounds), one path for all of them.
+// opt_install: a new buffer of `up` followed by n_zero zeros; only when it is complete the previous buffer is freed and *slot (and *keep, the host
+// copy a getter serves, where given) replaced -- on failure both stay as they were.  opt_clear: no buffer.  opt_fetch: the caller's array to the host.
+static int opt_install(const char *who, double **slot, std::vector<double> &up, size_t n_zero = 0, std::vector<double> *keep = nullptr) {
+    double *buf = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (up.size() + n_zero) + 64));
+    if ((n_zero && hipMemset(buf, 0, sizeof(double) * (up.size() + n_zero)) != hipSuccess) || hipMemcpy(buf, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(buf);
+        return fail(std::string(who) + ": upload failed");
+    }
+    if (*slot) hipFree(*slot);
+    *slot = buf;
+    if (keep) keep->swap(up);
+    return 0;
+}
+static void opt_clear(double **slot, std::vector<double> *keep = nullptr) {
+    if (*slot) hipFree(*slot);
+    *slot = nullptr;
+    if (keep) keep->clear();
+}
+static int opt_fetch(std::vector<double> &dst, const double *src, int loc) {
+    HIPCHK(hipMemcpy(dst.data(), src, sizeof(double) * dst.size(), loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost));
+    return 0;
+}
 
 // (nx, nu) pairs the QP / sweep kernels are instantiated for: the reference's three plants, plus whatever the build adds with
 //   -DSLSQP_EXTRA_DIMS="X(6,2) X(9,3)"      (limits of the single-wave kernels: nx <= 17, nu <= 4, nx + nu <= 21)
@@ -203,7 +258,7 @@ extern "C" slsqp_handle *slsqp_create(const slsqp_dims *d, int batch, int device
     rc |= dalloc(h->owned, &h->g, B * N * ni); rc |= dalloc(h->owned, &h->gN, B * nif); rc |= dalloc(h->owned, &h->c, B * N * nx); rc |= dalloc(h->owned, &h->q, B * h->n);
     rc |= dalloc(h->owned, &h->x0val, B * nx); rc |= dalloc(h->owned, &h->gf_raw, (size_t)nif); rc |= dalloc(h->owned, &h->g_raw, (size_t)ni);
     rc |= dalloc(h->owned, &h->Xn, B * (N + 1) * nx); rc |= dalloc(h->owned, &h->Un, B * N * nu); rc |= dalloc(h->owned, &h->xmeas, B * nx); rc |= dalloc(h->owned, &h->x0arg, B * nx);
-    rc |= dalloc(h->owned, &h->u0, B * nu); rc |= dalloc(h->owned, &h->wbuf, B * nx); rc |= dalloc(h->owned, &h->u_init, (size_t)nu); h->cl_steps = 0; rc |= dalloc(h->owned, &h->cst, (size_t)(3 * nx + 2 * nu) * 2);
+    rc |= dalloc(h->owned, &h->u0, B * nu); rc |= dalloc(h->owned, &h->wbuf, B * nx); rc |= dalloc(h->owned, &h->u_init, (size_t)nu); rc |= dalloc(h->owned, &h->zero_ref, (size_t)(nx + nu)); h->cl_steps = 0; rc |= dalloc(h->owned, &h->cst, (size_t)(3 * nx + 2 * nu) * 2);
     rc |= dalloc(h->owned, &h->ubg, B * h->mb); rc |= dalloc(h->owned, &h->lbg, B * h->mb);
     rc |= dalloc(h->owned, &h->primal, B * h->n); rc |= dalloc(h->owned, &h->dual, B * h->mb); rc |= dalloc(h->owned, &h->cost, B); rc |= dalloc(h->owned, &h->pin_dual, B * nx);
     rc |= dalloc(h->owned, &h->kkt, kkt_doubles(B)); rc |= dalloc(h->owned, &h->prev_primal, B * h->n); rc |= dalloc(h->owned, &h->Linv, B * N * nx * nx); rc |= dalloc(h->owned, &h->ws, B * qp_ws_doubles(h->n, N, nx)); rc |= dalloc(h->owned, &h->qpstate, B * 40);
@@ -285,9 +340,7 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     free_all(h->owned);
     if (h->stage) hipFree(h->stage);
     if (h->cl_W) hipFree(h->cl_W);
-    if (h->ref_Y) hipFree(h->ref_Y);
-    if (h->pp_P) hipFree(h->pp_P);
-    if (h->bnd_rows) hipFree(h->bnd_rows);
+    opt_clear(&h->ref_Y); opt_clear(&h->pp_P); opt_clear(&h->bnd_rows);
     if (h->qplog) hipFree(h->qplog);
     if (h->x0vlog) hipFree(h->x0vlog);
     if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
@@ -691,22 +744,14 @@ __device__ __forceinline__ int rti_chain_dev(const ChainArgs &c_, int b, int lan
         c.x0vlog[((size_t)b * c.log_steps + min(c.stepno[b], c.log_steps - 1)) * 2 + lane - 16] = c.q.qpstat[(size_t)b * 16 + (lane - 16) * 8 + 6] == -1 ? 0.0 : x0_record(c.q.kkt, c.q.B)[2 + (size_t)b * 2 + lane - 16];
     return 1;
 }
-template <int NX, int NU>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_rti_chain(ChainArgs c) {
+// BND: a handle with bounds (slsqp_cl_step at large batches, the rounds of slsqp_cl_run); without, bd is empty and never read
+template <int NX, int NU, bool BND>
+__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_rti_chain(ChainArgs c, BndArgs bd) {
     int b = blockIdx.x, lane = threadIdx.x;
     if (b >= c.q.B) return;
     if (c.runm && !c.runm[b]) return;
     extern __shared__ double sm[];
-    rti_chain_dev<NX, NU>(c, b, lane, sm);
-}
-// the same for a handle with bounds (slsqp_cl_step at large batches, the rounds of slsqp_cl_run)
-template <int NX, int NU>
-__global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_rti_chain_bnd(ChainArgs c, BndArgs bd) {
-    int b = blockIdx.x, lane = threadIdx.x;
-    if (b >= c.q.B) return;
-    if (c.runm && !c.runm[b]) return;
-    extern __shared__ double sm[];
-    rti_chain_dev<NX, NU, false, true>(c, b, lane, sm, &bd);
+    rti_chain_dev<NX, NU, false, BND>(c, b, lane, sm, &bd);
 }
 
 // ---- the whole closed loop as ONE persistent launch (slsqp_cl_run, opts.cl_persistent) ------------------------------------------------
@@ -800,7 +845,7 @@ struct ScpLoopArgs {
     LoopArgs L;
     int max_it, converge, rti_steps;
     int *nsolves;
-    BndArgs bd;      // slsqp_cl_set_bounds (variants 3 and 4 only; behind everything else, so no other field moves)
+    BndArgs bd;      // slsqp_cl_set_bounds (the variants with VAR_BND only; behind everything else, so no other field moves)
 };
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
@@ -868,16 +913,12 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
     CLSTAMP(10);
     return (s + 1 < L.steps) ? s + 1 : 0;
 }
-// The persistent closed loop, ONE body with five variants.  VAR 0: plain; 1: tracks a reference (slsqp_cl_set_reference: the linear cost of
-// cl_step_begin reads rf); 2: tracks a reference and steps the plant with the instance's own parameters (slsqp_cl_set_plant_params: cl_step_end reads
-// pa; without a reference rf is one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference); 3 and 4: variants 1 and 2
-// with the box bounds of slsqp_cl_set_bounds (the linearisation's g_k / g_N and the chain's terminal tightened row read blk->bd; a handle with bounds
-// but no reference passes the zero row, as variant 2 does).  A variant is passed empty rf / pa where it reads none.  The three calls that name VAR,
-// through the constants below, are all that depends on it.  The statements stand in the kernel, not in a function it
-// calls, and the next per-handle option is a further VAR value, not a further kernel.
-constexpr bool var_ref(int VAR) { return VAR > 0; }
-constexpr bool var_pp(int VAR) { return VAR == 2 || VAR == 4; }
-constexpr bool var_bnd(int VAR) { return VAR > 2; }
+// The persistent closed loop, ONE body with five variants, VAR a set of the bits VAR_REF / VAR_PP / VAR_BND (cl_options).  0: plain; REF: tracks a
+// reference (slsqp_cl_set_reference: the linear cost of cl_step_begin reads rf); PP: steps the plant with the instance's own parameters
+// (slsqp_cl_set_plant_params: cl_step_end reads pa); BND: the box bounds of slsqp_cl_set_bounds (the linearisation's g_k / g_N and the chain's terminal
+// tightened row read blk->bd).  PP and BND come with REF only (1, 3, 5, 7: a handle without a reference passes one row of zeros).  A variant is passed
+// empty rf / pa where it reads none.  The three calls that name VAR, through var_ref / var_pp / var_bnd, are all that depends on it.  The statements
+// stand in the kernel, not in a function it calls, and the next per-handle option is a further VAR bit, not a further kernel (DESIGN.md sections 14, 16).
 template <int MODEL, int VAR>
 __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
@@ -1489,11 +1530,14 @@ static int launch_chain_t(slsqp_handle *h, ChainArgs &c, const BndArgs *bd) {
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     h->ne_waves = 0;      // (slsqp_ne_solve's factors do not survive a QP solve)
-    if (bd) hipLaunchKernelGGL((k_rti_chain_bnd<NX, NU>), dim3(h->B), dim3(64), lds, h->st, c, *bd);
-    else hipLaunchKernelGGL((k_rti_chain<NX, NU>), dim3(h->B), dim3(64), lds, h->st, c);
+    with_flag(bd != nullptr, [&](auto BND) { hipLaunchKernelGGL((k_rti_chain<NX, NU, BND()>), dim3(h->B), dim3(64), lds, h->st, c, bd ? *bd : BndArgs{}); });
     if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
     HIPCHK(hipGetLastError());
     return 0;
+}
+// the tightening as a launch of its own: bd as for launch_chain_t
+static void launch_tighten(slsqp_handle *h, const TightenArgs &ta, const BndArgs *bd) {
+    with_flag(bd != nullptr, [&](auto BND) { hipLaunchKernelGGL((k_tighten<BND()>), dim3(h->B), dim3(128), 0, h->st, ta, bd ? *bd : BndArgs{}); });
 }
 static bool chain_allowed() { static const bool v = getenv("SLSQP_FUSE_RTI") ? atoi(getenv("SLSQP_FUSE_RTI")) != 0 : true; return v; }
 
@@ -1624,8 +1668,7 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
         if (launch_sweep(h, h->mask, h->eta, h->eta_f, o.eps_backoff, /* beta == eps for every column right after initialize_backoff */ i == 0)) return -1;
         tl_end(h, tl_s);
         TightenArgs ta{B, d.N, d.nx, d.nu, d.ni, d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, h->mask, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, 1, h->ct_part, h->cost_tube};
-        if (bd) hipLaunchKernelGGL(k_tighten_bnd, dim3(B), dim3(128), 0, h->st, ta, *bd);
-        else hipLaunchKernelGGL(k_tighten, dim3(B), dim3(128), 0, h->st, ta);
+        launch_tighten(h, ta, bd);
         if (rti) continue;      // RTI mode (every closed-loop script): nothing to decide on the host, the stream runs on
         int nmask = 0;
         HIPCHK(hipMemcpyAsync(&nmask, h->counter, sizeof(int), hipMemcpyDeviceToHost, h->st));
@@ -1705,25 +1748,20 @@ extern "C" int slsqp_cl_set_reference(slsqp_handle *h, const double *Xref, const
     if (loc != SLSQP_HOST && loc != SLSQP_DEVICE) return fail("slsqp_cl_set_reference: loc must be SLSQP_HOST or SLSQP_DEVICE");
     HIPCHK(hipStreamSynchronize(h->st));      // no launch may still read the buffer that is replaced
     if (T == 0) {
-        if (h->ref_Y) hipFree(h->ref_Y);
-        h->ref_Y = nullptr; h->ref_T = 0; h->ref_stride = 0;
+        opt_clear(&h->ref_Y);
+        h->ref_T = 0; h->ref_stride = 0;
         return 0;
     }
     const size_t nx = h->d.nx, nu = h->d.nu, nz = nx + nu, rows = (size_t)(per_instance ? h->B : 1) * T;
     std::vector<double> X(rows * nx), U(rows * nu, 0.0), Y(rows * nz);
-    const hipMemcpyKind kind = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
-    HIPCHK(hipMemcpy(X.data(), Xref, sizeof(double) * X.size(), kind));
-    if (Uref) HIPCHK(hipMemcpy(U.data(), Uref, sizeof(double) * U.size(), kind));
+    if (opt_fetch(X, Xref, loc) || (Uref && opt_fetch(U, Uref, loc))) return -1;
     for (size_t r = 0; r < rows; r++) {
         for (size_t i = 0; i < nx; i++) Y[r * nz + i] = X[r * nx + i];
         for (size_t i = 0; i < nu; i++) Y[r * nz + nx + i] = U[r * nu + i];
     }
     for (double v : Y) if (!std::isfinite(v)) return fail("slsqp_cl_set_reference: the reference holds a NaN or infinite entry");
-    double *dY = nullptr;
-    HIPCHK(hipMalloc((void **)&dY, sizeof(double) * Y.size() + 64));
-    if (hipMemcpy(dY, Y.data(), sizeof(double) * Y.size(), hipMemcpyHostToDevice) != hipSuccess) { hipFree(dY); return fail("slsqp_cl_set_reference: upload failed"); }
-    if (h->ref_Y) hipFree(h->ref_Y);
-    h->ref_Y = dY; h->ref_T = T; h->ref_stride = per_instance ? (size_t)T * nz : 0;
+    if (opt_install("slsqp_cl_set_reference", &h->ref_Y, Y)) return -1;
+    h->ref_T = T; h->ref_stride = per_instance ? (size_t)T * nz : 0;
     return 0;
 }
 
@@ -1748,25 +1786,28 @@ extern "C" int slsqp_cl_set_plant_params(slsqp_handle *h, const double *P, int n
     if (np > 0 && !P) return fail("slsqp_cl_set_plant_params: P is NULL with np > 0 (np = 0 clears the parameters)");
     HIPCHK(hipStreamSynchronize(h->st));      // no launch may still read the buffer that is replaced
     if (np == 0) {
-        if (h->pp_P) hipFree(h->pp_P);
-        h->pp_P = h->pp_merr = h->pp_zero_ref = nullptr; h->pp_np = 0; h->pp_stride = 0; h->pp_host.clear();
+        opt_clear(&h->pp_P, &h->pp_host);
+        h->pp_merr = nullptr; h->pp_np = 0; h->pp_stride = 0;
         return 0;
     }
     if (np != plant_params::count(h->model_id)) { std::string why; plant_params::check(h->model_id, nullptr, 0, np, &why); return fail("slsqp_cl_set_plant_params: " + why); }
-    const size_t rows = per_instance ? (size_t)h->B : 1, nP = rows * np, nE = (size_t)h->B * h->d.nx, nZ = (size_t)h->nz;
+    const size_t rows = per_instance ? (size_t)h->B : 1, nP = rows * np, nE = (size_t)h->B * h->d.nx;
     std::vector<double> host(nP);
-    HIPCHK(hipMemcpy(host.data(), P, sizeof(double) * nP, loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost));
+    if (opt_fetch(host, P, loc)) return -1;
     std::string why;
     if (!plant_params::check(h->model_id, host.data(), rows, np, &why)) return fail("slsqp_cl_set_plant_params: " + why);
-    double *buf = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (nP + nE + nZ) + 64));
-    if (hipMemset(buf, 0, sizeof(double) * (nP + nE + nZ)) != hipSuccess || hipMemcpy(buf, host.data(), sizeof(double) * nP, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(buf);
-        return fail("slsqp_cl_set_plant_params: upload failed");
-    }
-    if (h->pp_P) hipFree(h->pp_P);
-    h->pp_P = buf; h->pp_merr = buf + nP; h->pp_zero_ref = buf + nP + nE; h->pp_np = np; h->pp_stride = per_instance ? np : 0; h->pp_host.swap(host);
+    if (opt_install("slsqp_cl_set_plant_params", &h->pp_P, host, nE, &h->pp_host)) return -1;      // (model_err behind the rows, zeroed)
+    h->pp_merr = h->pp_P + nP; h->pp_np = np; h->pp_stride = per_instance ? np : 0;
     return 0;
+}
+// An option's rows as slsqp_get serves them, (B, T, w): elements [off, off + w) of the T rows of width W of `host` (the option's host copy: one set per
+// instance, or a shared one repeated), or `dflt` (w) for every row where the option is unset (host NULL)
+static std::vector<double> opt_rows(size_t B, const std::vector<double> *host, bool per_instance, size_t T, size_t W, size_t off, size_t w, const double *dflt) {
+    std::vector<double> v(B * T * w);
+    for (size_t b = 0; b < B; b++)
+        for (size_t t = 0; t < T; t++)
+            for (size_t i = 0; i < w; i++) v[(b * T + t) * w + i] = host ? (*host)[(per_instance ? b * T * W : 0) + t * W + off + i] : dflt[i];
+    return v;
 }
 // slsqp_get names that depend on the plant parameters: plant_params (B,np) (a shared row repeated; the defaults for a handle without parameters),
 // model_err (B,nx) (zeros without parameters).  Returns 1 when `name` was one of them and has been served, 0 when not, -1 on error.
@@ -1783,9 +1824,9 @@ static int get_plant_named(slsqp_handle *h, const char *name, void *out, int loc
         return 1;
     }
     const int np = plant_params::count(h->model_id);
-    std::vector<double> v((size_t)h->B * np);
-    for (size_t b = 0; b < (size_t)h->B; b++)
-        for (int i = 0; i < np; i++) v[b * np + i] = h->pp_P ? h->pp_host[(h->pp_stride ? b * np : 0) + i] : plant_params::default_value(h->model_id, i);
+    std::vector<double> dflt(np);
+    for (int i = 0; i < np; i++) dflt[i] = plant_params::default_value(h->model_id, i);
+    const std::vector<double> v = opt_rows(h->B, h->pp_P ? &h->pp_host : nullptr, h->pp_stride != 0, 1, np, 0, np, dflt.data());
     HIPCHK(hipMemcpy(out, v.data(), sizeof(double) * v.size(), kind));
     return 1;
 }
@@ -1801,27 +1842,17 @@ extern "C" int slsqp_cl_set_bounds(slsqp_handle *h, const double *g, const doubl
     if (!cl_bounds::check_call(g, T, per_instance, &why)) return fail("slsqp_cl_set_bounds: " + why);
     HIPCHK(hipStreamSynchronize(h->st));      // no launch may still read the buffer that is replaced
     if (T == 0) {
-        if (h->bnd_rows) hipFree(h->bnd_rows);
-        h->bnd_rows = h->bnd_zero_ref = nullptr; h->bnd_T = 0; h->bnd_stride = 0; h->bnd_host.clear();
+        opt_clear(&h->bnd_rows, &h->bnd_host);
+        h->bnd_T = 0; h->bnd_stride = 0;
         return 0;
     }
     if (!gf && !h->have_cons) return fail("slsqp_cl_set_bounds: gf = NULL repeats the model's gf: slsqp_set_constraints must be called first");
     const size_t ni = h->d.ni, nif = h->d.ni_f, sets = per_instance ? (size_t)h->B : 1, rows = sets * (size_t)T;
     std::vector<double> hg(rows * ni), hgf(gf ? rows * nif : 0), packed;
-    const hipMemcpyKind kind = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyDeviceToHost;
-    HIPCHK(hipMemcpy(hg.data(), g, sizeof(double) * hg.size(), kind));
-    if (gf) HIPCHK(hipMemcpy(hgf.data(), gf, sizeof(double) * hgf.size(), kind));
+    if (opt_fetch(hg, g, loc) || (gf && opt_fetch(hgf, gf, loc))) return -1;
     if (!cl_bounds::pack(hg.data(), gf ? hgf.data() : nullptr, h->gf_raw_host.data(), sets, T, (int)ni, (int)nif, &packed, &why)) return fail("slsqp_cl_set_bounds: " + why);
-    const size_t nR = packed.size(), nZ = (size_t)h->nz;
-    double *buf = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (nR + nZ) + 64));
-    if (hipMemset(buf, 0, sizeof(double) * (nR + nZ)) != hipSuccess || hipMemcpy(buf, packed.data(), sizeof(double) * nR, hipMemcpyHostToDevice) != hipSuccess) {
-        hipFree(buf);
-        return fail("slsqp_cl_set_bounds: upload failed");
-    }
-    if (h->bnd_rows) hipFree(h->bnd_rows);
-    h->bnd_rows = buf; h->bnd_zero_ref = buf + nR;
-    h->bnd_T = T; h->bnd_stride = per_instance ? (size_t)T * (ni + nif) : 0; h->bnd_host.swap(packed);
+    if (opt_install("slsqp_cl_set_bounds", &h->bnd_rows, packed, 0, &h->bnd_host)) return -1;
+    h->bnd_T = T; h->bnd_stride = per_instance ? (size_t)T * (ni + nif) : 0;
     return 0;
 }
 // slsqp_get names of the bounds: bounds_g (B, T, ni), bounds_gf (B, T, ni_f) (a shared set repeated; without bounds the model's box with T = 1).
@@ -1830,12 +1861,9 @@ static int get_bounds_named(slsqp_handle *h, const char *name, void *out, int lo
     const bool is_g = !strcmp(name, "bounds_g"), is_f = !strcmp(name, "bounds_gf");
     if (!is_g && !is_f) return 0;
     if (h->model_id < 0 || !h->have_cons) return fail(std::string(name) + ": slsqp_set_model and slsqp_set_constraints must be called first");
-    const size_t ni = h->d.ni, nif = h->d.ni_f, W = ni + nif, T = h->bnd_rows ? (size_t)h->bnd_T : 1, w = is_g ? ni : nif, off = is_g ? 0 : ni;
-    std::vector<double> v((size_t)h->B * T * w);
-    for (size_t b = 0; b < (size_t)h->B; b++)
-        for (size_t t = 0; t < T; t++)
-            for (size_t i = 0; i < w; i++)
-                v[(b * T + t) * w + i] = h->bnd_rows ? h->bnd_host[(h->bnd_stride ? b * T * W : 0) + t * W + off + i] : (is_g ? h->g_raw_host[i] : h->gf_raw_host[i]);
+    const size_t ni = h->d.ni, nif = h->d.ni_f;
+    const std::vector<double> v = opt_rows(h->B, h->bnd_rows ? &h->bnd_host : nullptr, h->bnd_stride != 0, h->bnd_rows ? (size_t)h->bnd_T : 1, ni + nif, is_g ? 0 : ni, is_g ? ni : nif,
+                                           is_g ? h->g_raw_host.data() : h->gf_raw_host.data());
     HIPCHK(hipMemcpy(out, v.data(), sizeof(double) * v.size(), loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice));
     return 1;
 }
@@ -1933,13 +1961,11 @@ static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int
     LinArgs a{h->B, d.N, dX, dU, h->g_raw, h->gf_raw, costs_of(h), h->A, h->Bm, h->c, h->g, h->gN, h->q, run, h->lin_stage, h->lin_tape};
     const int grid = 2048, blk = 128;
     const int gval = (int)((B * d.N + blk - 1) / blk);
+    const ClOptions op = cl_options(h);
     if (with_model(h, [&](auto M) {
             constexpr int NX = dyn::Dims<M()>::NX, NU = dyn::Dims<M()>::NU;
             hipLaunchKernelGGL((k_lin_val<M()>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<M()>), dim3(grid), dim3(blk), 0, h->st, a);
-            if (h->bnd_rows && h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_bnd<NX, NU, true>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), bnd_args(h, step, stepno));
-            else if (h->bnd_rows) hipLaunchKernelGGL((k_lin_vec_bnd<NX, NU, false>), dim3(grid), dim3(256), 0, h->st, a, RefArgs{}, bnd_args(h, step, stepno));
-            else if (h->ref_T > 0) hipLaunchKernelGGL((k_lin_vec_ref<NX, NU>), dim3(grid), dim3(256), 0, h->st, a, ref_args(h), step, stepno);
-            else hipLaunchKernelGGL((k_lin_vec<NX, NU>), dim3(grid), dim3(256), 0, h->st, a);
+            with_ref_bnd(op, [&](auto REF, auto BND) { hipLaunchKernelGGL((k_lin_vec<NX, NU, REF(), BND()>), dim3(grid), dim3(256), 0, h->st, a, op.own_rf, bnd_args(h, step, stepno)); });
         })) return -1;
     BoundsArgs ba{h->B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, run};
     hipLaunchKernelGGL(k_set_bounds, dim3(1024), dim3(256), 0, h->st, ba);
@@ -2004,14 +2030,11 @@ extern "C" int slsqp_nominal_solve(slsqp_handle *h, int max_qp, double tol, doub
     na.B = B; na.N = d.N; na.Xn = h->Xn; na.Un = h->Un; na.xmeas = h->xmeas; na.primal = h->primal; na.qp_status = h->status; na.g_raw = h->g_raw; na.gf_raw = h->gf_raw;
     na.cst = costs_of(h); na.st = h->nom_st; na.active = active; na.need_lin = h->nom_need_lin; na.status = h->nom_status; na.iters = h->nom_iters;
     na.n_active = h->counter + 2; na.rho = rho; na.tol = tol; na.w_max = 1e8;
-    const RefArgs rf = h->ref_T > 0 ? ref_args(h) : RefArgs{};      // the tracked objective, window of step 0
+    const ClOptions op = cl_options(h);      // the tracked objective and the box, window of step 0
     auto eval = [&](int mode) {
         na.mode = mode;
         return with_model(h, [&](auto M) {
-            if (h->bnd_rows && h->ref_T > 0) hipLaunchKernelGGL((k_nom_eval_bnd<M(), true>), dim3(B), dim3(128), 0, h->st, na, rf, bnd_args(h, 0, nullptr));      // the box, window of step 0
-            else if (h->bnd_rows) hipLaunchKernelGGL((k_nom_eval_bnd<M(), false>), dim3(B), dim3(128), 0, h->st, na, rf, bnd_args(h, 0, nullptr));
-            else if (h->ref_T > 0) hipLaunchKernelGGL((k_nom_eval<M(), true>), dim3(B), dim3(128), 0, h->st, na, rf);
-            else hipLaunchKernelGGL((k_nom_eval<M(), false>), dim3(B), dim3(128), 0, h->st, na, rf);
+            with_ref_bnd(op, [&](auto REF, auto BND) { hipLaunchKernelGGL((k_nom_eval<M(), REF(), BND()>), dim3(B), dim3(128), 0, h->st, na, op.own_rf, bnd_args(h, 0, nullptr)); });
         });
     };
     if (eval(0)) return -1;
@@ -2088,6 +2111,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     const double *dw = nullptr;
     if (w) { if (put(h, h->wbuf, w, sizeof(double) * (size_t)h->B * d.nx, loc)) return -1; dw = h->wbuf; }
     ClArgs a = cl_args(h, dw);
+    const ClOptions op = cl_options(h);
     if (h->cl_steps > 0) {
         if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 1, 0); })) return -1;
         if (slsqp_reset(h)) return -1;
@@ -2112,7 +2136,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     for (int ii = 0; ii < max_it; ii++) {
         hipLaunchKernelGGL(k_cl_x0arg, dim3(64), dim3(256), 0, h->st, a);
         const BndArgs bd = bnd_args(h, h->cl_steps, nullptr);      // (the tightening's terminal row: the window of this step)
-        if (solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->scp_active, /* no_sync */ true, h->bnd_rows ? &bd : nullptr)) return -1;
+        if (solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->scp_active, /* no_sync */ true, op.bnd ? &bd : nullptr)) return -1;
         HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
         ScpArgs sa{ii, converge ? 1 : 0, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
         hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, sa);
@@ -2138,7 +2162,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
         h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};      // (a slsqp_cl_run in between points the name at its own per-run buffer)
     }
     if (with_model(h, [&](auto M) {
-            if (h->pp_P) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, plant_args(h), h->cl_steps, nullptr, nullptr, nullptr);      // the plant has its own parameters
+            if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, op.pa, h->cl_steps, nullptr, nullptr, nullptr);      // the plant has its own parameters
             else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
         })) return -1;
     HIPCHK(hipGetLastError());
@@ -2168,15 +2192,11 @@ static int launch_loop_t(slsqp_handle *h, bool S) {
     const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
     if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
     hipEventRecord(h->ev[8], h->st);
-    // the kernels' variant: 2 plant parameters (which track a reference: without one, one row of zeros), 1 a reference, 0 neither (rf, pa empty, unread);
-    // with bounds 4 / 3 in place of 2 / 1 (3 also for a handle without a reference: the zero row).  The bounds themselves are in the block (make_loop_block)
-    const int var = h->bnd_rows ? (h->pp_P ? 4 : 3) : (h->pp_P ? 2 : (h->ref_T > 0 ? 1 : 0));
-    const RefArgs rf = h->ref_T > 0 ? ref_args(h) : (var >= 2 ? RefArgs{h->pp_P ? h->pp_zero_ref : h->bnd_zero_ref, 1, 0} : RefArgs{});
-    const PlantArgs pa = h->pp_P ? plant_args(h) : PlantArgs{};
-    dispatch5(var, [&](auto V) {
-        if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
-        else hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, rf, pa);
-    });
+    const ClOptions op = cl_options(h);      // (the bounds themselves are in the block: make_loop_block)
+    if (!with_loop_var(op.var, [&](auto V) {
+            if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
+            else hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);
+        })) return fail("no persistent closed-loop kernel for variant " + std::to_string(op.var));
     hipEventRecord(h->ev[9], h->st);
     if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
     HIPCHK(hipGetLastError());
@@ -2212,7 +2232,7 @@ static ScpLoopArgs make_loop_block(slsqp_handle *h, int steps, const double *dW,
     L.Q = ClQueue{h->clq_slots, h->clq_cap - 1u, (unsigned *)h->clq_ctl, (unsigned *)h->clq_ctl + 1, h->clq_ctl + 2, h->clq_ctl + 3};
     L.busy = h->cl_busy; L.t_begin = h->cl_tbegin;
     S.max_it = max_it; S.converge = scp_rti <= 0 ? 1 : 0; S.rti_steps = o.rti_steps; S.nsolves = h->qplog_nsolves;
-    if (h->bnd_rows) { S.bd.rows = h->bnd_rows; S.bd.T = h->bnd_T; S.bd.stride = h->bnd_stride; S.bd.stepno = h->cl_stepno; S.bd.step = 0; }      // (field by field: the padding stays zero; all zero bytes without bounds, and never read)
+    if (cl_options(h).bnd) { S.bd.rows = h->bnd_rows; S.bd.T = h->bnd_T; S.bd.stride = h->bnd_stride; S.bd.stepno = h->cl_stepno; S.bd.step = 0; }      // (field by field: the padding stays zero; all zero bytes without bounds, and never read)
     return S;
 }
 // the block goes to the handle's device buffer on the handle's stream, ahead of the launch that reads it (and behind the previous launch, which may
@@ -2348,6 +2368,7 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
     h->cl_budget = budget_ms > 0.0 ? (unsigned long long)(std::max(0.05, budget_ms) * 1e5) : (1ULL << 62);
     h->cl_total_steps = steps;
     ClArgs a = cl_args(h, nullptr);
+    const ClOptions op = cl_options(h);
     int rounds = 0;
     const int max_rounds = 40 * steps + 100;
     for (;; rounds++) {
@@ -2375,7 +2396,7 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         h->horizon_shifted = rounds > 0 ? 1 : 0;
         h->cl_round = true; h->cl_skip_begin = h->cl_skipb;
         const BndArgs bd = bnd_args(h, 0, h->cl_stepno);
-        const int rc = solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->cl_runm, /* no_sync */ true, h->bnd_rows ? &bd : nullptr);
+        const int rc = solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->cl_runm, /* no_sync */ true, op.bnd ? &bd : nullptr);
         h->cl_round = false; h->cl_skip_begin = nullptr;
         if (rc) return -1;
         // end of the step for the instances whose chain is done: nominal += delta, primal_infeasibility, log entry, plant + noise, step counter
@@ -2390,7 +2411,7 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
             hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, la);
         }
         if (with_model(h, [&](auto M) {
-                if (h->pp_P) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, plant_args(h), 0, h->cl_done, h->cl_stepno, dW);
+                if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, op.pa, 0, h->cl_done, h->cl_stepno, dW);
                 else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
             })) return -1;
         hipLaunchKernelGGL(k_cl_advance, dim3(gbi), dim3(256), 0, h->st, B, h->cl_done, h->cl_stepno, h->call_ids, h->cl_begin);
@@ -2520,7 +2541,7 @@ extern "C" int slsqp_sweep(slsqp_handle *h, const double *eta, const double *eta
     if (launch_sweep(h, nullptr, h->eta, h->eta_f, 1e-10)) return -1;
     HIPCHK(hipEventRecord(h->ev[1], h->st));
     TightenArgs ta{h->B, d.N, d.nx, d.nu, d.ni, d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, nullptr, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, 0, h->ct_part, h->cost_tube};
-    hipLaunchKernelGGL(k_tighten, dim3(h->B), dim3(128), 0, h->st, ta);
+    launch_tighten(h, ta, nullptr);
     HIPCHK(hipEventRecord(h->ev[2], h->st));
     HIPCHK(hipStreamSynchronize(h->st));
     h->t_sweep = ev_ms(h->ev[0], h->ev[1]); h->t_total = ev_ms(h->ev[0], h->ev[2]); h->t_qp = 0;

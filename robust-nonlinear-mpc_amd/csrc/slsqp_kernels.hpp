@@ -2170,17 +2170,22 @@ __global__ __launch_bounds__(64, 3) void k_sweep_prop(SweepSharedArgs aa) {
 // ------------------------------------------------------------------------------------------------
 // backoff sums + tightened bounds (fast_SLS_jit.py:173-186, 556-569) ; one workgroup per instance
 // ------------------------------------------------------------------------------------------------
-// Time-varying box bounds of the closed loops (slsqp_cl_set_bounds): rows [g(t); gf(t)] of absolute MPC time t, packed (T, NI + NIF) in the model's
-// own layout (g = [hi; -lo] over [x; u], gf = [hi; -lo] over x), shared by the batch (stride 0) or one block per instance (stride T (NI + NIF)).
-// Stage k < N of the horizon of MPC step s reads the g part of row min(s + k, T - 1), the terminal stage the gf part of row min(s + N, T - 1): the
-// last row is held.  The MPC step of instance b is stepno[b], or `step` where stepno is NULL.  Only the kernels launched for a handle WITH bounds
-// take this argument (the BND = true instantiations below); every other kernel keeps its arguments and its code.
-struct BndArgs { const double *rows; int T; size_t stride; const int *stepno; int step; };
-__device__ __forceinline__ int bnd_step(const BndArgs &r, int b) { return r.stepno ? r.stepno[b] : r.step; }
-// row of stage k of the window of MPC step s of instance b; W = NI + NIF
-__device__ __forceinline__ const double *bnd_row(const BndArgs &r, int b, int s, int k, int W) {
+// A table over MPC time, the form of every per-handle closed-loop option that varies with the step: rows of absolute MPC time t, packed (T, W),
+// shared by the batch (stride 0) or one block per instance (stride T W).  Stage k of the horizon of MPC step s reads row min(s + k, T - 1): the
+// last row is held.  An option that is off is passed an empty table, which the instantiation without its flag never reads.
+struct RowTab { const double *rows; int T; size_t stride; };
+// row of stage k of the window of MPC step s of instance b
+__device__ __forceinline__ const double *tab_row(const RowTab &r, int b, int s, int k, int W) {
     return r.rows + (size_t)b * r.stride + (size_t)min(s + k, r.T - 1) * W;
 }
+// Reference trajectory of the tracked cost (slsqp_cl_set_reference): rows y_ref(t) = [x_ref(t); u_ref(t)], W = NX + NU (the REF = true instantiations)
+using RefArgs = RowTab;
+// Time-varying box bounds of the closed loops (slsqp_cl_set_bounds): rows [g(t); gf(t)], W = NI + NIF, in the model's own layout (g = [hi; -lo] over
+// [x; u], gf = [hi; -lo] over x); stage k < N reads the g part of its row, the terminal stage the gf part (the BND = true instantiations).  Behind the
+// table, the MPC step whose window a batch-wide launch reads, for the reference too: stepno[b], or `step` where stepno is NULL.
+struct BndArgs : RowTab { const int *stepno; int step; };
+static_assert(sizeof(RefArgs) == 24 && sizeof(BndArgs) == 40, "ScpLoopArgs is compared as bytes and k_cl_loop takes rf by value: these layouts stay");
+__device__ __forceinline__ int bnd_step(const BndArgs &r, int b) { return r.stepno ? r.stepno[b] : r.step; }
 struct TightenArgs {
     int B, N, NX, NU, NI, NIF;   // NI, NIF: rows of G, Gf (2(nx+nu), 2nx for the box constraints of the reference's plants)
     const double *beta, *beta_f, *g, *gf_raw, *c;
@@ -2199,7 +2204,7 @@ __device__ __forceinline__ void tighten_dev(const TightenArgs &a, int b, int tid
     double *bx = a.backoff_x + (size_t)b * (N + 1) * NX, *bu = a.backoff_u + (size_t)b * N * NU;
     double *ub = a.ubg + (size_t)b * mb;
     const double *gfw = nullptr;
-    if constexpr (BND) { const BndArgs &bd = args_here<BLK>(bdp); gfw = bnd_row(bd, b, bnd_step(bd, b), N, NI + NIF) + NI; }
+    if constexpr (BND) { const BndArgs &bd = args_here<BLK>(bdp); gfw = tab_row(bd, b, bnd_step(bd, b), N, NI + NIF) + NI; }
     for (int o = tid; o < N * NI; o += nthr) {
         const int k = o / NI, i = o % NI;
         double acc = 0.0;
@@ -2225,16 +2230,12 @@ __device__ __forceinline__ void tighten_dev(const TightenArgs &a, int b, int tid
         a.cost_tube[b] = sqrt(acc);
     }
 }
-__global__ void k_tighten(TightenArgs a) {
+// BND: a handle with bounds (the separate launches of slsqp_cl_step); without, bd is empty and never read
+template <bool BND>
+__global__ void k_tighten(TightenArgs a, BndArgs bd) {
     const int b = blockIdx.x;
     if (a.run && !a.run[b]) return;
-    tighten_dev(a, b, threadIdx.x, blockDim.x);
-}
-// the same for a handle with bounds (the separate launches of slsqp_cl_step)
-__global__ void k_tighten_bnd(TightenArgs a, BndArgs bd) {
-    const int b = blockIdx.x;
-    if (a.run && !a.run[b]) return;
-    tighten_dev<true>(a, b, threadIdx.x, blockDim.x, &bd);
+    tighten_dev<BND>(a, b, threadIdx.x, blockDim.x, &bd);
 }
 
 // initialize_backoff (fast_SLS_jit.py:444-454)
@@ -2317,15 +2318,6 @@ __global__ __launch_bounds__(128) void k_lin_tan(LinArgs a) {
         lin_tan_item<MODEL>(a, b, k, dir);
     }
 }
-// Reference trajectory of the tracked cost (slsqp_cl_set_reference): rows y_ref(t) = [x_ref(t); u_ref(t)] of absolute MPC time t, packed (T, NX+NU),
-// shared by the batch (stride 0) or one block per instance (stride T (NX+NU)).  Stage k of the horizon of MPC step s reads row min(s + k, T - 1): the
-// last row is held.  Only the kernels launched for a handle WITH a reference take this argument (the REF = true instantiations below); every
-// other kernel keeps its arguments and its code.
-struct RefArgs { const double *Y; int T; size_t stride; };
-template <int NZ>
-__device__ __forceinline__ double ref_entry(const RefArgs &r, int b, int s, int k, int i) {
-    return r.Y[(size_t)b * r.stride + (size_t)min(s + k, r.T - 1) * NZ + i];
-}
 // g_k, g_N and q of element e of instance b.  REF: q = 2 H (y_nom - y_ref) with the window of MPC step s (formed as a difference first: a zero
 // reference gives the bits of 2 H y_nom).  BND: g_k = g_row - G [x_k; u_k] and g_N = gf_row - Gf x_N with the rows of the same window (bd already
 // read from wherever it lies)
@@ -2335,52 +2327,31 @@ __device__ __forceinline__ void lin_vec_item(const LinArgs &a, int b, int e, con
     const int n = NZ * a.N + NX, k = e / NZ, i = e % NZ;
     const double z = (i < NX) ? a.X[((size_t)b * (a.N + 1) + k) * NX + i] : a.U[((size_t)b * a.N + k) * NU + (i - NX)];
     double zq = z;
-    if constexpr (REF) zq = z - ref_entry<NZ>(*rf, b, s, k, i);
+    if constexpr (REF) zq = z - tab_row(*rf, b, s, k, NZ)[i];
     if (k < a.N) {
         double *g = a.g + ((size_t)b * a.N + k) * NI;
-        if constexpr (BND) { const double *r = bnd_row(*bd, b, s, k, NI + NIF); g[i] = r[i] - z; g[NZ + i] = r[NZ + i] + z; }
+        if constexpr (BND) { const double *r = tab_row(*bd, b, s, k, NI + NIF); g[i] = r[i] - z; g[NZ + i] = r[NZ + i] + z; }
         else { g[i] = a.g_raw[i] - z; g[NZ + i] = a.g_raw[NZ + i] + z; }
         a.q[(size_t)b * n + e] = 2.0 * (i < NX ? a.cst.Qd[i] : a.cst.Rd[i - NX]) * zq;
     } else {
         double *g = a.gN + (size_t)b * NIF;
-        if constexpr (BND) { const double *r = bnd_row(*bd, b, s, k, NI + NIF) + NI; g[i] = r[i] - z; g[NX + i] = r[NX + i] + z; }
+        if constexpr (BND) { const double *r = tab_row(*bd, b, s, k, NI + NIF) + NI; g[i] = r[i] - z; g[NX + i] = r[NX + i] + z; }
         else { g[i] = a.gf_raw[i] - z; g[NX + i] = a.gf_raw[NX + i] + z; }
         a.q[(size_t)b * n + e] = 2.0 * a.cst.Qfd[i] * zq;
     }
 }
-template <int NX, int NU>
-__global__ void k_lin_vec(LinArgs a) {
+// REF / BND: a handle with a reference / with bounds; a table that is off is empty and never read.  Every instance at bd's step (bnd_step), whichever
+// table is read
+template <int NX, int NU, bool REF, bool BND>
+__global__ void k_lin_vec(LinArgs a, RefArgs rf, BndArgs bd) {
     constexpr int NZ = NX + NU;
     const int n = NZ * a.N + NX;
     const size_t tot = (size_t)a.B * n;
     for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < tot; t += (size_t)gridDim.x * blockDim.x) {
         const int e = t % n, b = t / n;
         if (a.run && !a.run[b]) continue;
-        lin_vec_item<NX, NU>(a, b, e);
-    }
-}
-// the same for a handle with a reference: every instance at MPC step `step`, or at its own stepno[b] (the rounds of slsqp_cl_run)
-template <int NX, int NU>
-__global__ void k_lin_vec_ref(LinArgs a, RefArgs rf, int step, const int *stepno) {
-    constexpr int NZ = NX + NU;
-    const int n = NZ * a.N + NX;
-    const size_t tot = (size_t)a.B * n;
-    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < tot; t += (size_t)gridDim.x * blockDim.x) {
-        const int e = t % n, b = t / n;
-        if (a.run && !a.run[b]) continue;
-        lin_vec_item<NX, NU, true>(a, b, e, &rf, stepno ? stepno[b] : step);
-    }
-}
-// the same for a handle with bounds, with or without a reference (rf is empty and unread without one); every instance at bd's step
-template <int NX, int NU, bool REF>
-__global__ void k_lin_vec_bnd(LinArgs a, RefArgs rf, BndArgs bd) {
-    constexpr int NZ = NX + NU;
-    const int n = NZ * a.N + NX;
-    const size_t tot = (size_t)a.B * n;
-    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < tot; t += (size_t)gridDim.x * blockDim.x) {
-        const int e = t % n, b = t / n;
-        if (a.run && !a.run[b]) continue;
-        lin_vec_item<NX, NU, REF, true>(a, b, e, &rf, bnd_step(bd, b), &bd);
+        if constexpr (REF || BND) lin_vec_item<NX, NU, REF, BND>(a, b, e, &rf, bnd_step(bd, b), &bd);
+        else lin_vec_item<NX, NU>(a, b, e);
     }
 }
 // the whole linearisation of ONE instance by one wave (the persistent closed-loop kernel k_cl_loop): same items, same arithmetic
@@ -2691,20 +2662,88 @@ __device__ __forceinline__ double block_max128(double v, double *red) {
     return r;
 }
 // REF (a handle with a reference): the objective is the tracked cost sum hw (z - y_ref)^2 with the window of MPC step 0 (the initialiser runs before
-// the first step); without one it is sum hw z^2 and rf is empty and never read.  Everything else is the same for both.
-template <int MODEL, bool REF>
-__global__ __launch_bounds__(128) void k_nom_eval(NomArgs a, RefArgs rf) {
-    constexpr bool BND = false;
-    const BndArgs *bd = nullptr;
-#include "nom_eval_body.hpp"
-}
-// BND (a handle with bounds): the box whose violation the merit function counts is the window of MPC step 0 (slsqp_cl_set_bounds), per instance; the
-// QP's own rows follow through the linearisation (k_lin_vec_bnd -> k_nom_bounds), so the first nominal respects the bounds it will be held to
-template <int MODEL, bool REF>
-__global__ __launch_bounds__(128) void k_nom_eval_bnd(NomArgs a, RefArgs rf, BndArgs bda) {
-    constexpr bool BND = true;
-    const BndArgs *bd = &bda;
-#include "nom_eval_body.hpp"
+// the first step); without one it is sum hw z^2.  BND (a handle with bounds): the box whose violation the merit function counts is the window of MPC
+// step 0 (slsqp_cl_set_bounds), per instance; the QP's own rows follow through the linearisation (k_lin_vec -> k_nom_bounds), so the first nominal
+// respects the bounds it will be held to.  A table that is off is empty and never read.
+template <int MODEL, bool REF, bool BND>
+__global__ __launch_bounds__(128) void k_nom_eval(NomArgs a, RefArgs rf, BndArgs bd) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU, NZ = NX + NU;
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (!a.active[b]) return;
+    __shared__ double red[128];
+    __shared__ int dec_s;
+    const int N = a.N, n = NZ * N + NX;
+    double *X = a.Xn + (size_t)b * (N + 1) * NX, *U = a.Un + (size_t)b * N * NU;
+    const double *d = a.primal + (size_t)b * n;
+    double *S = a.st + (size_t)b * 12;
+    const bool trial = a.mode == 1;
+    double f = 0.0, v = 0.0, dm = 0.0, c = 0.0;
+    for (int e = t; e < n; e += 128) {
+        const int k = e / NZ, i = e % NZ;
+        const double z0 = (i < NX) ? X[k * NX + i] : U[k * NU + (i - NX)];
+        const double dv = trial ? d[e] : 0.0, z = z0 + dv;
+        const double hw = (k < N) ? (i < NX ? a.cst.Qd[i] : a.cst.Rd[i - NX]) : a.cst.Qfd[i];
+        double hi, lo;
+        if constexpr (BND) {      // the box of stage k in the window of MPC step 0
+            const double *r = tab_row(bd, b, 0, k, 2 * NZ + 2 * NX);
+            hi = (k < N) ? r[i] : r[2 * NZ + i]; lo = (k < N) ? -r[NZ + i] : -r[2 * NZ + NX + i];
+        } else { hi = (k < N) ? a.g_raw[i] : a.gf_raw[i]; lo = (k < N) ? -a.g_raw[NZ + i] : -a.gf_raw[NX + i]; }
+        const double zt = REF ? z - tab_row(rf, b, 0, k, NZ)[i] : z;
+        f += hw * zt * zt;
+        if (e >= NX) v += fmax(z - hi, 0.0) + fmax(lo - z, 0.0);   // x_0 is data (pinned to x_meas), its box is not the solver's to fix
+        dm = fmax(dm, fabs(dv));
+    }
+    for (int k = t; k < N; k += 128) {
+        double x[NX], u[NU], xp[NX];
+        for (int i = 0; i < NX; i++) x[i] = X[k * NX + i] + (trial ? d[k * NZ + i] : 0.0);
+        for (int i = 0; i < NU; i++) u[i] = U[k * NU + i] + (trial ? d[k * NZ + NX + i] : 0.0);
+        dyn::ddyn<MODEL, double>(x, u, xp);
+        for (int i = 0; i < NX; i++) c += fabs(xp[i] - (X[(k + 1) * NX + i] + (trial ? d[(k + 1) * NZ + i] : 0.0)));
+    }
+    if (t < NX) c += fabs(X[t] + (trial ? d[t] : 0.0) - a.xmeas[(size_t)b * NX + t]);
+    f = block_sum128(f, red); v = block_sum128(v, red); c = block_sum128(c, red); dm = block_max128(dm, red);
+    if (t == 0) {
+        int dec = 0;   // 0 retry the QP (same linearisation), 1 step accepted, 2 converged, 3 failed
+        double w = S[0], kap = S[1], kap0 = S[2];
+        const double f0 = S[3], c0 = S[4], v0 = S[5];
+        if (!trial) {
+            S[3] = f; S[4] = c; S[5] = v; S[1] = (v > 1e-7 || c > 1e-6) ? kap0 : 0.0;
+            dec = -1;
+        } else {
+            const int qs = a.qp_status[b];
+            const double phi0 = f0 + a.rho * (c0 + v0);
+            double r = 0.0;
+            if (!(qs == 0 || qs == 4)) {       // QP infeasible at this tau: ask for less
+                if (kap < 0.995) { kap = 1.0 - 0.3 * (1.0 - kap); dec = 0; } else dec = 3;
+            } else {
+                const double pred = phi0 - (f + a.rho * kap * (v0 + c0));     // linearised model: violation shrinks to kappa * (v0 + c0)
+                const double act = phi0 - (f + a.rho * (c + v));
+                r = pred > 0.0 ? act / pred : -1.0;
+                if (pred <= 1e-12 * fmax(1.0, fabs(phi0)) || dm < a.tol) dec = (v0 < 1e-7 && c0 < 1e-7)   /* l1 sums; the QP's own 1e-10 pads on every bound add up to ~1e-9 */ ? 2 : 1;
+                else if (r < 0.1) { w *= 4.0; kap = 1.0 - (1.0 - kap) / 3.0; dec = (w > a.w_max) ? 3 : 0; }
+                else { dec = 1; kap0 = kap; if (r > 0.7) { w = fmax(w / 3.0, 1e-6); kap0 = kap > 0.01 ? kap / 3.0 : 0.0; } }
+            }
+            S[6] = r; S[7] = dm;
+            if (dec == 1 || dec == 2) {
+                S[3] = f; S[4] = c; S[5] = v;
+                kap = (v > 1e-7 || c > 1e-6) ? kap0 : 0.0;
+                a.iters[b] += 1;
+            }
+            S[0] = w; S[1] = kap; S[2] = kap0;
+            a.need_lin[b] = (dec == 1) ? 1 : 0;
+            if (dec == 2) { a.status[b] = 0; a.active[b] = 0; }
+            else if (dec == 3) { a.status[b] = 2; a.active[b] = 0; }
+            else atomicAdd(a.n_active, 1);
+        }
+        dec_s = dec;
+    }
+    __syncthreads();
+    if (dec_s == 1 || dec_s == 2) {
+        for (int e = t; e < n; e += 128) {
+            const int k = e / NZ, i = e % NZ;
+            if (i < NX) X[k * NX + i] += d[e]; else U[k * NU + (i - NX)] += d[e];
+        }
+    }
 }
 // bounds of the initialiser's QP: dynamics rows -tau c (+-eps), box rows g_k + kappa max(-g_k, 0) (g_k = g - G y, so max(-g_k,0) is the
 // current violation); the box of x_0 is dropped (x_0 is pinned).

@@ -91,34 +91,36 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     B = len(mine)
     K = max(1, min(int(slices), B))
 
-    def ref_rows(a, b):      # the rows of a per-seed reference for the seeds [a, b) of this rank's shard
-        if reference is None or isinstance(reference, str):
-            return reference
-        Xr, Ur = reference if isinstance(reference, tuple) else (reference, None)
-        if np.ndim(Xr) != 3:
-            return reference
-        if len(Xr) != S:
-            raise ValueError(f"run_monte_carlo: a per-seed reference needs {S} leading rows, got {len(Xr)}")
-        return (np.asarray(Xr)[lo + a:lo + b], None if Ur is None else np.asarray(Ur)[lo + a:lo + b])
-    def param_rows(a, b):      # the same for per-seed plant parameters
-        def cut(v, what):
-            v = np.asarray(v, dtype=float)
-            if v.ndim == 0 or (what is None and v.ndim == 1):
-                return v
-            if len(v) != S:
-                raise ValueError(f"run_monte_carlo: per-seed plant parameters need {S} leading rows, got {len(v)}" + (f" ({what})" if what else ""))
-            return v[lo + a:lo + b]
-        if isinstance(plant_params, dict):
-            return {k: cut(v, k) for k, v in plant_params.items()}
-        return cut(plant_params, None)
-    def bound_rows(a, b):      # the same for per-seed bounds
-        gb, gfb = bounds if isinstance(bounds, (tuple, list)) and len(bounds) == 2 and np.ndim(bounds[0]) >= 2 else (bounds, None)
-        if np.ndim(gb) != 3:
-            return bounds
-        if len(gb) != S:
-            raise ValueError(f"run_monte_carlo: per-seed bounds need {S} leading rows, got {len(gb)}")
-        return (np.asarray(gb)[lo + a:lo + b], None if gfb is None else np.asarray(gfb)[lo + a:lo + b])
     cuts = [(B * k // K, B * (k + 1) // K) for k in range(K)]
+
+    def cut(k, v):
+        """Rows [lo + a, lo + b) of a per-seed array (leading axis of len(seeds)) for slice k, the seeds [a, b) of this rank's shard; None stays None."""
+        return None if v is None else np.asarray(v)[lo + cuts[k][0]:lo + cuts[k][1]]
+
+    def per_seed(v, what):      # the length check of an option's first per-seed array (the arrays that follow it are cut as it is)
+        if len(v) != S:
+            raise ValueError(f"run_monte_carlo: {what} {S} leading rows, got {len(v)}")
+        return v
+
+    def options(k):      # reference, plant_params and bounds of slice k: what is per seed cut with the seeds, everything else as given
+        kw = {}
+        if reference is not None:
+            Xr, Ur = reference if isinstance(reference, tuple) else (reference, None)
+            kw["reference"] = (cut(k, per_seed(Xr, "a per-seed reference needs")), cut(k, Ur)) if np.ndim(Xr) == 3 else reference
+        if isinstance(plant_params, dict):      # an entry is per seed from one axis on
+            kw["plant_params"] = {}
+            for name, v in plant_params.items():
+                v = np.asarray(v, dtype=float)
+                if v.ndim >= 1 and len(v) != S:
+                    raise ValueError(f"run_monte_carlo: per-seed plant parameters need {S} leading rows, got {len(v)} ({name})")
+                kw["plant_params"][name] = cut(k, v) if v.ndim >= 1 else v
+        elif plant_params is not None:          # a bare array from two
+            v = np.asarray(plant_params, dtype=float)
+            kw["plant_params"] = cut(k, per_seed(v, "per-seed plant parameters need")) if v.ndim >= 2 else v
+        if bounds is not None:
+            gb, gfb = bounds if isinstance(bounds, (tuple, list)) and len(bounds) == 2 and np.ndim(bounds[0]) >= 2 else (bounds, None)
+            kw["bounds"] = (cut(k, per_seed(gb, "per-seed bounds need")), cut(k, gfb)) if np.ndim(gb) == 3 else bounds
+        return kw
     parts, err = [None] * K, []
 
     def work(k):
@@ -128,12 +130,7 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["x0_box_tol"] = x0_box_tol
             if solve_waves != 1:
                 kw["solve_waves"] = solve_waves
-            if reference is not None:
-                kw["reference"] = ref_rows(*cuts[k])
-            if plant_params is not None:
-                kw["plant_params"] = param_rows(*cuts[k])
-            if bounds is not None:
-                kw["bounds"] = bound_rows(*cuts[k])
+            kw.update(options(k))
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:
             err.append(e)

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""What the bounds kernels cost: the persistent closed loop of a handle with bounds (variants 3 and 4 of k_cl_loop<M, VAR>: the window's rows in the
-linearisation and the terminal tightened row read from the bounds buffer; variant 3 also subtracts the one-row zero reference of a handle that has
+"""What the bounds kernels cost: the persistent closed loop of a handle with bounds (the variants with the BND bit of k_cl_loop<M, VAR>, VAR = 5 and 7: the window's rows in the
+linearisation and the terminal tightened row read from the bounds buffer; variant 5 also subtracts the one-row zero reference of a handle that has
 none) against the variant the same handle ran without them, on identical inputs in one process.  The bounds are the model's box repeated, so the
 work per QP is the same.
 
 Four configurations, after a warm-up on a disjoint seed batch run in turn `--repeats` times each:
   plain     nothing set (variant 0)
-  bnd       the model's box as T = steps + N + 1 per-instance rows (variant 3: reference + bounds, with the zero reference; the model's plant step)
-  v2        a one-row zero reference and plant parameters 1e-9 off the defaults (variant 2)
-  v2_bnd    the same with the bounds (variant 4: reference + plant parameters + bounds)
+  bnd       the model's box as T = steps + N + 1 per-instance rows (variant 5 = REF | BND: reference + bounds, with the zero reference; the model's plant step)
+  v2        a one-row zero reference and plant parameters 1e-9 off the defaults (variant 3 = REF | PP)
+  v2_bnd    the same with the bounds (variant 7 = REF | PP | BND: reference + plant parameters + bounds)
 Per run the duration of the persistent launch (HIP events around it, loop_stats.launch_ms).  One JSON line: medians and spreads (max - min), and
 whether bnd / v2_bnd give the bits of plain / v2.
 

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
-"""What the plant-parameter kernels cost: the persistent closed loop of a handle with plant parameters (k_cl_loop<M, 2>, variant 2 of the
+"""What the plant-parameter kernels cost: the persistent closed loop of a handle with plant parameters (k_cl_loop<M, 3>, the variant REF | PP of the
 kernel: per MPC step one more RK4 step on the plant lane) against the variant without them (k_cl_loop<M, 1>), on identical inputs in one process.
 
-All handles carry a one-row zero reference, so none takes variant 0.  Three configurations, after a warm-up on a disjoint seed batch run in turn
+All handles carry a one-row zero reference, so none takes the plain variant 0.  Three configurations, after a warm-up on a disjoint seed batch run in turn
 `--repeats` times each:
   ref       no parameters (k_cl_loop<M, 1>)
-  pp        the defaults set explicitly (k_cl_loop<M, 2>; a row equal to the model's constants takes the model's own step: model_error must be exactly zero; whether
+  pp        the defaults set explicitly (k_cl_loop<M, 3>; a row equal to the model's constants takes the model's own step: model_error must be exactly zero; whether
             the outputs equal ref's bit for bit is reported as outputs_equal / differing_keys)
-  pp_off    every parameter but the gimbal lengths off its default by a relative 1e-9 (k_cl_loop<M, 2> with BOTH RK4 steps on the plant lane: the cost of
+  pp_off    every parameter but the gimbal lengths off its default by a relative 1e-9 (k_cl_loop<M, 3> with BOTH RK4 steps on the plant lane: the cost of
             the feature; the closed loop is the same workload to nine digits)
 Per run the duration of the persistent launch (HIP events around it, loop_stats.launch_ms) and the wall time of the whole run.  One JSON line:
 medians and spreads (max - min).

@@ -4,7 +4,9 @@
 // made-up addresses: nothing dereferences them.
 //   1. the two QpArgs of a chain the old way -- two independent make_qp_args calls with (warm, stat_slot, snap_use) = (w, 0, 0) and (1, 1, 1) --
 //      against the new way, the common struct and qp_second_args, byte for byte, for w = 0 and w = 1 (and with ipm_restart off);
-//   2. the block the host stages for a launch against the LoopArgs that went to the kernel by value before, field by field.
+//   2. the block the host stages for a launch against the LoopArgs that went to the kernel by value before, field by field;
+//   3. the description of the handle's options (cl_options) in each of the 8 states (reference, parameters, bounds on or off): the persistent
+//      kernels' variant, reference and plant arguments, the batch-wide kernels' flags, and the bounds in the block against the struct they were before.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -40,7 +42,7 @@ static slsqp_handle *fake_handle(int B, int N) {
     FAKE(lg_it); FAKE(lg_pinf); FAKE(lg_state); FAKE(lg_succ); FAKE(lg_u); FAKE(lg_u0); FAKE(lg_x); FAKE(lin_stage); FAKE(lin_tape); FAKE(mask);
     FAKE(pending_reset); FAKE(pin_dual); FAKE(pinf); FAKE(prev_primal); FAKE(primal); FAKE(q); FAKE(qp_diag); FAKE(qplog); FAKE(qplog_nsolves); FAKE(qpstat);
     FAKE(qpstate); FAKE(scp_active); FAKE(scp_dmax); FAKE(scp_iters); FAKE(scp_success); FAKE(scp_upd); FAKE(stale); FAKE(status); FAKE(success); FAKE(u0);
-    FAKE(u_init); FAKE(ubg); FAKE(ws); FAKE(x0arg); FAKE(x0val); FAKE(x0vlog); FAKE(xmeas);
+    FAKE(u_init); FAKE(ubg); FAKE(ws); FAKE(x0arg); FAKE(x0val); FAKE(x0vlog); FAKE(xmeas); FAKE(zero_ref);
     return h;
 }
 
@@ -55,7 +57,51 @@ static OldArgs old_qp_pair(slsqp_handle *h, const slsqp_opts &o) {
     return r;
 }
 
+// the bounds' argument as it was declared before the table type: the block's bd keeps these bytes
+struct OldBndArgs { const double *rows; int T; size_t stride; const int *stepno; int step; };
+static_assert(sizeof(OldBndArgs) == sizeof(BndArgs) && sizeof(RefArgs) == 24, "the argument layouts stay");
+
+// ---- 3: states (ref, pp, bnd); the variant each ran as before the bit set was 0, 1, 2, 2, 3, 3, 4, 4 in the order of `want` below
+static void check_option_states() {
+    static const int want[8] = {/* 000 */ 0, /* 001 */ 5, /* 010 */ 3, /* 011 */ 7, /* 100 */ 1, /* 101 */ 5, /* 110 */ 3, /* 111 */ 7};
+    for (int st = 0; st < 8; st++) {
+        const bool ref = st & 4, pp = st & 2, bnd = st & 1;
+        slsqp_handle *h = fake_handle(5, 3);
+        if (ref) { FAKE(ref_Y); h->ref_T = 2; h->ref_stride = 2 * 5; }
+        if (pp) { FAKE(pp_P); FAKE(pp_merr); FAKE(lg_merr); h->pp_np = 3; h->pp_stride = 3; }
+        if (bnd) { FAKE(bnd_rows); h->bnd_T = 2; h->bnd_stride = 2 * 18; }
+        const ClOptions op = cl_options(h);
+        EXPECT(op.ref == ref && op.pp == pp && op.bnd == bnd && op.var == want[st]);
+        EXPECT(var_ref(op.var) == (st != 0) && var_pp(op.var) == pp && var_bnd(op.var) == bnd);
+        int seen = -1, calls = 0;
+        EXPECT(with_loop_var(op.var, [&](auto V) { seen = V(); calls++; }) && seen == want[st] && calls == 1);
+        with_ref_bnd(op, [&](auto REF, auto BND) { EXPECT(REF() == ref && BND() == bnd); calls++; });      // k_lin_vec, k_nom_eval: the handle's own, no zero row
+        EXPECT(calls == 2);
+        if (ref) EXPECT(op.own_rf.rows == h->ref_Y && op.own_rf.T == 2 && op.own_rf.stride == 10);      // k_lin_vec, k_nom_eval: the handle's own or none
+        else EXPECT(op.own_rf.rows == nullptr && op.own_rf.T == 0 && op.own_rf.stride == 0);
+        if (ref) EXPECT(op.rf.rows == h->ref_Y && op.rf.T == 2 && op.rf.stride == 10);
+        else if (st) EXPECT(op.rf.rows == h->zero_ref && op.rf.T == 1 && op.rf.stride == 0);
+        else EXPECT(op.rf.rows == nullptr && op.rf.T == 0 && op.rf.stride == 0);
+        if (pp) EXPECT(op.pa.P == h->pp_P && op.pa.stride == 3 && op.pa.model_err == h->pp_merr && op.pa.lg == h->lg_merr && op.pa.S == h->log_steps);
+        else EXPECT(op.pa.P == nullptr && op.pa.stride == 0 && op.pa.model_err == nullptr && op.pa.lg == nullptr && op.pa.S == 0);
+        const BndArgs bd = bnd_args(h, 4, h->cl_stepno);      // tighten / chain (BND = op.bnd) and the step of either table's window
+        EXPECT(bd.rows == h->bnd_rows && bd.T == h->bnd_T && bd.stride == h->bnd_stride && bd.stepno == h->cl_stepno && bd.step == 4);
+        // the block's bounds: the bytes of the struct as it was, filled field by field; all zero bytes without bounds
+        slsqp_opts o;
+        slsqp_default_opts(&o);
+        const ScpLoopArgs S = make_loop_block(h, 3, nullptr, o, false, 1);
+        OldBndArgs old;
+        std::memset(&old, 0, sizeof old);
+        if (bnd) { old.rows = h->bnd_rows; old.T = h->bnd_T; old.stride = h->bnd_stride; old.stepno = h->cl_stepno; old.step = 0; }
+        EXPECT(std::memcmp(&S.bd, &old, sizeof old) == 0);
+        EXPECT((const unsigned char *)&S.bd + sizeof S.bd == (const unsigned char *)&S + sizeof S);      // bd stays behind every other field
+        delete h;
+    }
+    for (int v : {-1, 2, 4, 6, 8}) EXPECT(!with_loop_var(v, [&](auto) { fails++; }));      // no instantiation, no fall-back
+}
+
 int main() {
+    check_option_states();
     for (int w = 0; w < 2; w++) for (int restart = 0; restart < 2; restart++) for (int scp = 0; scp < 2; scp++) {
         slsqp_handle *h = fake_handle(5 + w, 3 + 2 * restart);
         slsqp_opts o;

@@ -30,9 +30,9 @@ def setup(name, N=None, B=None, steps=None):
     return m, N, B, steps, x0, W, kw
 
 
-def make(m, N, B, tune=None, rti=1, rti_steps=1, reference=None, plant_params=None):
+def make(m, N, B, tune=None, rti=1, rti_steps=1, reference=None, plant_params=None, bounds=None):
     from robust_nonlinear_mpc_amd import ClosedLoopMPC
-    cl = ClosedLoopMPC(m, N, B, rti=rti, fast_sls_rti_steps=rti_steps, reference=reference, plant_params=plant_params)
+    cl = ClosedLoopMPC(m, N, B, rti=rti, fast_sls_rti_steps=rti_steps, reference=reference, plant_params=plant_params, bounds=bounds)
     if tune:
         tune(cl.f.opts)
     return cl
@@ -84,6 +84,55 @@ def assert_same(out, fin, ref, ref_fin, what=""):
         assert np.array_equal(out[k], ref[k], equal_nan=True), (what, k)
     for k in FIN_KEYS:
         assert np.array_equal(fin[k], ref_fin[k], equal_nan=True), (what, k)
+
+
+# ---- the per-handle options: every state (reference, plant parameters, bounds) on or off, tests/test_gpu_option_states.py and scripts/option_state_bits.py
+STATES = [(r, p, b) for r in (0, 1) for p in (0, 1) for b in (0, 1)]
+
+
+def option_state(m, B, state, T=2):
+    """make()'s keywords for one state: per-instance tables of T rows (shorter than steps + N: the held last row is in every window), the box with an
+    input limit of 0.22 and every side pulled in by up to 10 %, the reference up to 0.1 off the neutral point, the parameters up to 10 % off their
+    defaults; all differ per instance and row."""
+    from robust_nonlinear_mpc_amd._plant_cli import sample_plant_params
+    ref, pp, bnd = state
+    t, b = np.arange(T)[None, :, None], np.arange(B)[:, None, None]
+    kw = {}
+    if ref:
+        Xref = np.tile(np.asarray(m.x_ref, dtype=float), (B, T, 1))
+        Xref[:, :, :1] += 0.1 * np.sin(0.35 * t + 0.7 * b + 1.0)
+        kw["reference"] = (Xref, np.tile(np.asarray(m.u_ref, dtype=float), (B, T, 1)))
+    if pp:
+        kw["plant_params"] = sample_plant_params(m, 1000 + np.arange(B), 10.0)
+    if bnd:
+        def pull(base):
+            return np.asarray(base, dtype=float) * (1.0 - 0.1 * (0.5 + 0.5 * np.sin(0.35 * t + 0.7 * b + 0.3 * np.arange(len(base))[None, None, :])))
+        g = np.array(m.g, dtype=float)
+        g[m.nx:m.nz] = g[m.nz + m.nx:] = 0.22      # (the pendulum's first inputs are -0.24 without it: the rows are active)
+        kw["bounds"] = (pull(g), pull(m.gf))
+    return kw
+
+
+def _tune(**fields):
+    def tune(o):
+        for k, v in fields.items():
+            setattr(o, k, v)
+    return tune
+
+
+def option_state_runs(state, name="pendulum"):
+    """Every closed-loop route of one state at the plant's smallest shape: {route: (out, fin)}.  step0 / step2: one slsqp_cl_step per step through the
+    separate launches / the fused chain; persistent, rounds: slsqp_cl_run; scp_step, scp: rti = 2 with two fast-SLS steps, step by step and
+    slsqp_cl_run_scp.  Every run starts with slsqp_nominal_solve."""
+    m, N, B, steps, x0, W, kw = setup(name)
+    mk = option_state(m, B, state)
+    scp = dict(rti=2, rti_steps=2, **mk)
+    return {"step0": stepwise(make(m, N, B, _tune(fuse_rti=0), **mk), steps, x0, W, **kw),
+            "step2": stepwise(make(m, N, B, _tune(fuse_rti=2), **mk), steps, x0, W, **kw),
+            "persistent": decoupled(make(m, N, B, **mk), steps, x0, W, **kw),
+            "rounds": decoupled(make(m, N, B, _tune(cl_persistent=0), **mk), steps, x0, W, **kw),
+            "scp_step": stepwise(make(m, N, B, **scp), steps, x0, W, **kw),
+            "scp": decoupled(make(m, N, B, **scp), steps, x0, W, **kw)}
 
 
 def main(path):

@@ -106,7 +106,7 @@ def test_blocks_are_per_handle():
 # ---- 4: the other loop kernels ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["ref", "pp", "scp"])
 def test_the_other_loop_kernels_are_bitwise_the_step_by_step_loop(kind):
-    """k_cl_loop<M, 1> (a reference), k_cl_loop<M, 2> (plant parameters) and k_cl_loop_scp<M, 0> (slsqp_cl_run_scp with rti = 2) at the pendulum shape."""
+    """k_cl_loop<M, 1> (a reference), k_cl_loop<M, 3> (plant parameters: VAR = REF | PP) and k_cl_loop_scp<M, 0> (slsqp_cl_run_scp with rti = 2) at the pendulum shape."""
     from robust_nonlinear_mpc_amd import plant_param_defaults
     m, N, B, steps, x0, W, kw = R.setup("pendulum")
     mk = dict(rti=2) if kind == "scp" else {}

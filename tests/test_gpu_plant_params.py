@@ -184,8 +184,8 @@ def _tune_converge(o):
 def test_persistent_loops_are_bitwise_the_step_by_step_loop_with_plant_params(model, N, B, steps, waves, rti, rti_steps, tune, with_reference):
     """As test_persistent_loops_are_bitwise_the_step_by_step_loop_with_a_reference (tests/test_gpu_reference.py): with 7 waves for 96 or 50 instances
     the instances are at different steps at the same time and change hands, so every plant step must read its own instance's row.  Rocket: rti 1 /
-    one fast-SLS step (k_cl_loop<M, 2>), also through the round-based loop; pendulum: the script setting and SCP converge mode (k_cl_loop_scp<M, 2>).
-    Without a reference variant 2 of the kernels gets the one-row zero reference."""
+    one fast-SLS step (k_cl_loop<M, 3>, VAR = REF | PP), also through the round-based loop; pendulum: the script setting and SCP converge mode (k_cl_loop_scp<M, 3>).
+    Without a reference that variant of the kernels gets the one-row zero reference."""
     from robust_nonlinear_mpc_amd import get_model
     m = get_model(model)
     P = H.spread_params(m, B, 15.0, seed=9)

@@ -9,7 +9,8 @@ from conftest import ROOT
 def test_one_qp_args_per_chain_and_the_staged_block_under_sanitizers():
     """The two QpArgs of a chain filled independently (warm, stat_slot, snap_use) = (w, 0, 0) and (1, 1, 1) against the common struct and
     qp_second_args, memcmp, for w = 0 and 1; the block the host stages for a launch against what went to the kernels by value, field by field; a
-    second launch of the same handle with other steps and options."""
+    second launch of the same handle with other steps and options; the description of the handle's options (cl_options) in each of the 8 states of
+    (reference, plant parameters, bounds): the kernels' variant and arguments, and the bounds in the block against the struct they were before."""
     exe = os.path.join(ROOT, "tests", "_build", "loop_args_check")
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     # (host pass only: no device code is generated, so this is the host compiler's time; the sanitizer runtimes are linked into the program)
