@@ -167,12 +167,6 @@ template <class F>
 static int with_model(const slsqp_handle *h, F &&f) {
     return dispatch3(h->model_id, f) ? 0 : fail("no kernels for model id " + std::to_string(h->model_id) + " (0 pendulum, 1 quadrotor, 2 rocket)");
 }
-static Costs costs_of(slsqp_handle *h) {
-    const int nx = h->d.nx, nu = h->d.nu;
-    Costs c;
-    c.Qd = h->cst; c.Rd = c.Qd + nx; c.Qfd = c.Rd + nu; c.Qregd = c.Qfd + nx; c.Rregd = c.Qregd + nx; c.Qregfd = c.Rregd + nu; c.prox = 0.0;
-    return c;
-}
 
 template <typename T>
 static int dalloc(std::vector<void *> &owned, T **p, size_t count) {
@@ -228,6 +222,17 @@ static std::string dims_list() {
 #undef X
     return r;
 }
+// the (nx, nu) pair as template arguments, as with_model gives the plant: every launch of a kernel that is a template of the pair goes through here.
+// f(std::integral_constant<int, NX>, std::integral_constant<int, NU>), NX() / NU() in the generic lambda, returns an int; no such pair in the build is an error that says so
+template <class F>
+static int with_dims(int nx, int nu, F &&f) {
+#define X(NX_, NU_) if (nx == NX_ && nu == NU_) return f(std::integral_constant<int, NX_>{}, std::integral_constant<int, NU_>{});
+    SLSQP_DIM_LIST
+#undef X
+    return fail("no kernels for (nx, nu) = (" + std::to_string(nx) + "," + std::to_string(nu) + "); built for" + dims_list());
+}
+template <class F>
+static int with_dims(const slsqp_handle *h, F &&f) { return with_dims(h->d.nx, h->d.nu, f); }
 
 extern "C" int slsqp_qp_nnz(const slsqp_dims *d, int *n, int *m, int *nnzP, int *nnzA) {
     const int nz = d->nx + d->nu;
@@ -441,6 +446,7 @@ extern "C" int slsqp_set_constraints(slsqp_handle *h, const double *G, const dou
     return 0;
 }
 
+static BoundsArgs bounds_args(slsqp_handle *h, const int *run);      // (with the other argument builders, below)
 extern "C" int slsqp_update_dynamics(slsqp_handle *h, const double *A, const double *Bm, const double *E, const double *g, const double *g_N,
                                      const double *c, int loc) {
     hipSetDevice(h->dev);
@@ -453,8 +459,7 @@ extern "C" int slsqp_update_dynamics(slsqp_handle *h, const double *A, const dou
     if (put(h, h->g, g, sizeof(double) * B * d.N * d.ni, loc)) return -1;
     if (put(h, h->gN, g_N, sizeof(double) * B * d.ni_f, loc)) return -1;
     if (put(h, h->c, c, sizeof(double) * B * d.N * d.nx, loc)) return -1;
-    BoundsArgs a{h->B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, nullptr};
-    hipLaunchKernelGGL(k_set_bounds, dim3(1024), dim3(256), 0, h->st, a);
+    hipLaunchKernelGGL(k_set_bounds, dim3(1024), dim3(256), 0, h->st, bounds_args(h, nullptr));
     HIPCHK(hipGetLastError());
     h->have_dyn = true;
     return 0;
@@ -1250,6 +1255,72 @@ __global__ void k_join_y(int B, int mb, int nx, const double *dual, const double
     }
 }
 
+// ---- kernel argument builders ---------------------------------------------------------
+// One builder per argument struct: the handle and, by name, what varies between the launch sites.  Every site calls it; no HIP call in any of them.
+static Costs costs_of(slsqp_handle *h) {
+    const int nx = h->d.nx, nu = h->d.nu;
+    Costs c;
+    c.Qd = h->cst; c.Rd = c.Qd + nx; c.Qfd = c.Rd + nu; c.Qregd = c.Qfd + nx; c.Rregd = c.Qregd + nx; c.Qregfd = c.Rregd + nu; c.prox = 0.0;
+    return c;
+}
+static ClArgs cl_args(slsqp_handle *h, const double *w) {
+    ClArgs a;
+    a.B = h->B; a.N = h->d.N; a.NX = h->d.nx; a.NU = h->d.nu; a.Xn = h->Xn; a.Un = h->Un; a.xmeas = h->xmeas; a.primal = h->primal;
+    a.success = h->success; a.x0arg = h->x0arg; a.E = h->E; a.w = w; a.u0 = h->u0; a.u_init = h->u_init;
+    return a;
+}
+// run: the instances that are tightened (NULL = all); write_ubg: the tightened rows go into the QP's bounds (a solve) or only into the back-offs (slsqp_sweep)
+static TightenArgs tighten_args(slsqp_handle *h, const int *run, int write_ubg) {
+    return TightenArgs{h->B, h->d.N, h->d.nx, h->d.nu, h->d.ni, h->d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, run, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, write_ubg, h->ct_part, h->cost_tube};
+}
+static SweepArgs sweep_args(slsqp_handle *h, const int *run, const double *eta, const double *eta_f, double eps) {
+    return SweepArgs{h->B, h->d.N, h->d.nw, h->A, h->Bm, h->E, 0, eta, eta_f, run, costs_of(h), h->K, h->beta, h->beta_f, h->ct_part, eps};
+}
+// rti: RTI mode (no count of the instances that go on); first: first iteration of the solve (the beta repair); shared_cols: beta = eps in every
+// column, evaluate_dual_eta writes column 0 only
+static AfterQpArgs after_qp_args(slsqp_handle *h, const slsqp_opts &o, const int *active, int rti, int first, int shared_cols) {
+    const EtaArgs ea{h->B, h->d.N, h->d.nx, h->d.ni, h->d.ni_f, h->dual, h->beta, h->beta_f, h->alive, h->eta, h->eta_f, o.eps_backoff, h->stale, shared_cols};
+    const ConvArgs ca{h->B, h->n, h->primal, h->prev_primal, h->has_prev, h->alive, h->conv, o.conv_tol};
+    return AfterQpArgs{h->B, rti, first, h->status, active, h->alive, h->infeas, h->mask, h->success, h->itnum, h->counter, h->stale, h->conv, ea, ca, h->beta, h->beta_f};
+}
+// run: the instances whose back-offs are reset (NULL = all); fill_beta: beta = eps too (the handle's first solve)
+static InitBackoffArgs init_backoff_args(slsqp_handle *h, const slsqp_opts &o, const int *run, int fill_beta) {
+    return InitBackoffArgs{h->B, h->d.N, h->d.nx, h->d.nu, o.eps_backoff, run, h->beta, h->beta_f, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, fill_beta};
+}
+// x0: the device array the pin value is taken from, or NULL when it has been written already; skip_begin: instances in the middle of a solve (slsqp_cl_run's rounds)
+static SolveBeginArgs solve_begin_args(slsqp_handle *h, const slsqp_opts &o, const double *x0, const int *active, const int *skip_begin) {
+    return SolveBeginArgs{h->B, h->d.nx, x0, h->x0val, active, h->alive, h->infeas, h->success, h->pending_reset, h->itnum, h->stale,
+                          h->eta, h->eta_f, (size_t)h->d.N * h->d.N * h->d.ni, (size_t)(h->d.N + 1) * h->d.ni_f, init_backoff_args(h, o, active, 0), skip_begin};
+}
+// X, U: the device trajectory that is linearised; run: the instances it is done for (NULL = all)
+static LinArgs lin_args(slsqp_handle *h, const double *X, const double *U, const int *run) {
+    return LinArgs{h->B, h->d.N, X, U, h->g_raw, h->gf_raw, costs_of(h), h->A, h->Bm, h->c, h->g, h->gN, h->q, run, h->lin_stage, h->lin_tape};
+}
+static BoundsArgs bounds_args(slsqp_handle *h, const int *run) {
+    return BoundsArgs{h->B, h->d.N, h->d.nx, h->d.ni, h->d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, run};
+}
+// the log entry: stepno[b] for the instances of mask (NULL = all), or `step` for everybody with stepno = NULL
+static ClLogArgs cl_log_args(slsqp_handle *h, const int *stepno, const int *mask, int step) {
+    return ClLogArgs{stepno, mask, h->B, h->d.N, h->d.nx, h->d.nu, h->log_steps, step, h->Xn, h->Un, h->backoff_x, h->backoff_u, h->scp_success, h->scp_iters,
+                     h->pinf, h->lg_x, h->lg_u, h->lg_bx, h->lg_bu, h->lg_state, h->lg_u0, h->lg_pinf, h->lg_succ, h->lg_it};
+}
+static ScpArgs scp_args(slsqp_handle *h, const slsqp_opts &o, int it, int converge) {
+    return ScpArgs{it, converge, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
+}
+// dynamic LDS of a wave that runs a whole chain (k_rti_chain, the persistent loops): the largest of its parts' work areas
+template <int NX, int NU>
+static size_t chain_lds_bytes(const slsqp_handle *h) {
+    return sizeof(double) * std::max({(size_t)qp_lds_doubles<NX, NU>(h->d.N), (size_t)(2 * h->n + 8), (size_t)sweep_lds_doubles<NX, NU>(), (size_t)sweep_prop_lds_doubles<NX, NU>()});
+}
+// a launch between a pair of kev events, when opts.time_kernels asks for it and there is room (harvest_kernel_events reads them)
+template <class F>
+static void timed_launch(slsqp_handle *h, F &&launch) {
+    const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
+    if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
+    launch();
+    if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
+}
+
 // ---- kernel dispatch ---------------------------------------------------------------------------------------
 // ticks a QP solve may take: 1 (start) + 2 per interior-point iteration + (1 + n_refine) per polish round, after at most warm_rounds + as_rounds
 // active-set rounds of the attempts that precede the interior point
@@ -1261,11 +1332,7 @@ static int launch_qp_t(slsqp_handle *h, const QpArgs &a, int max_iter, bool mx) 
     const dim3 grid(h->B), blk(64);
     const int max_ticks = qp_max_ticks(a, max_iter);
     // one launch per QP solve: every wave runs its instance to completion (k_qp_solve)
-    const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
-    if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
-    if (mx) hipLaunchKernelGGL((k_qp_solve<NX, NU, true>), grid, blk, lds, h->st, a, max_ticks);
-    else hipLaunchKernelGGL((k_qp_solve<NX, NU, false>), grid, blk, lds, h->st, a, max_ticks);
-    if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
+    timed_launch(h, [&] { with_flag(mx, [&](auto MX) { hipLaunchKernelGGL((k_qp_solve<NX, NU, MX()>), grid, blk, lds, h->st, a, max_ticks); }); });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1333,21 +1400,30 @@ static void set_x0_tol(slsqp_handle *h, double tol) {
     h->x0_tol_dev = tol;
 }
 
-static QpArgs make_qp_args(slsqp_handle *h, const int *run, const slsqp_opts *o, int warm, const double *prox = nullptr, int stat_slot = 0, int snap_take = 0, int snap_use = 0,
-                           int warm_shift = 0) {
+// What one QP of a call asks for: warm start, the nominal initialiser's proximal weights (B, 12) or NULL, the statistics slot, whether the interior point's iterate
+// is copied (snap_take) and may be restarted from (snap_use), whether the warm set moves one stage on with the horizon
+struct QpCall { int warm = 0; const double *prox = nullptr; int stat_slot = 0, snap_take = 0, snap_use = 0, warm_shift = 0; };
+// the first and the last QP of a fast-SLS call
+static QpCall qp_first_call(int warm, int warm_shift) { QpCall c; c.warm = warm; c.snap_take = 1; c.warm_shift = warm_shift; return c; }
+static QpCall qp_last_call(int warm_shift) { QpCall c; c.warm = 1; c.stat_slot = 1; c.snap_take = 1; c.snap_use = 1; c.warm_shift = warm_shift; return c; }
+// what the last QP of a call changes in the first one's arguments (make_qp_args with qp_last_call: warm, statistics slot 1, restart from the first QP's iterate copy)
+static Qp2Ints qp_second_ints(const slsqp_opts &o) { const QpCall l = qp_last_call(0); return Qp2Ints{l.warm, l.stat_slot, (l.snap_use && o.ipm_restart) ? 1 : 0}; }
+// the tolerance of the x0 gate a launch with these arguments asks for (set_x0_tol): the nominal initialiser's QPs (prox) stay strict
+static double qp_x0_tol(const slsqp_handle *h, const QpCall &c) { return c.prox ? 0.0 : h->x0_box_tol; }
+
+static QpArgs make_qp_args(slsqp_handle *h, const int *run, const slsqp_opts *o, const QpCall &c) {
     QpArgs a;
     memset(&a, 0, sizeof a);      // (padding too: the closed-loop kernels' argument block is compared and copied as bytes)
-    a.qpstat = h->qpstat; a.stat_slot = stat_slot; a.diag = h->qp_diag;
-    set_x0_tol(h, prox ? 0.0 : h->x0_box_tol);      // (prox: the nominal initialiser's QPs stay strict)
+    a.qpstat = h->qpstat; a.stat_slot = c.stat_slot; a.diag = h->qp_diag;
     static const double snap_mu = getenv("SLSQP_SNAP_MU") ? atof(getenv("SLSQP_SNAP_MU")) : 1e-3;
-    a.snap_take = snap_take; a.snap_use = snap_use && o->ipm_restart; a.snap_mu = snap_mu; a.call_id = h->call_id; a.call_ids = h->cl_round ? h->call_ids : nullptr; a.as_first = o->as_first; a.as_rounds = o->as_rounds; a.as_max_viol = o->as_max_viol; a.as_warm_max_set = o->as_warm_max_set; a.as_warm_last = o->as_warm_last;
+    a.snap_take = c.snap_take; a.snap_use = c.snap_use && o->ipm_restart; a.snap_mu = snap_mu; a.call_id = h->call_id; a.call_ids = h->cl_round ? h->call_ids : nullptr; a.as_first = o->as_first; a.as_rounds = o->as_rounds; a.as_max_viol = o->as_max_viol; a.as_warm_max_set = o->as_warm_max_set; a.as_warm_last = o->as_warm_last;
     { static const double pe = getenv("SLSQP_PINF_EPS") ? atof(getenv("SLSQP_PINF_EPS")) : 1e-4; a.pinf_eps = pe; }
-    { static const int ws = getenv("SLSQP_WARM_SHIFT") ? atoi(getenv("SLSQP_WARM_SHIFT")) : 1; a.warm_shift = ws ? warm_shift : 0; a.shift_stepno = nullptr; }
-    a.prox = prox; a.prox_stride = 12; a.inst_launches = h->inst_launches;
+    { static const int ws = getenv("SLSQP_WARM_SHIFT") ? atoi(getenv("SLSQP_WARM_SHIFT")) : 1; a.warm_shift = ws ? c.warm_shift : 0; a.shift_stepno = nullptr; }
+    a.prox = c.prox; a.prox_stride = 12; a.inst_launches = h->inst_launches;
     a.B = h->B; a.N = h->d.N; a.A = h->A; a.Bm = h->Bm; a.q = h->q; a.ubg = h->ubg; a.lbg = h->lbg; a.x0val = h->x0val; a.run = run;
     a.cst = costs_of(h); a.Linv = h->Linv; a.ws = h->ws; a.primal = h->primal; a.dual = h->dual; a.cost = h->cost; a.pin_dual = h->pin_dual; a.kkt = h->kkt;
     a.status = h->status; a.iters = h->iters; a.max_iter = o->qp_max_iter; a.eps = o->qp_eps;
-    a.state = h->qpstate; a.warm = warm; a.warm_rounds = o->warm_rounds;
+    a.state = h->qpstate; a.warm = c.warm; a.warm_rounds = o->warm_rounds;
     a.init_s = getenv("SLSQP_INIT_S") ? atof(getenv("SLSQP_INIT_S")) : 1.0; a.init_lam = getenv("SLSQP_INIT_LAM") ? atof(getenv("SLSQP_INIT_LAM")) : 0.0;
     const bool mx = o->precision == 1;
     a.n_refine = mx ? 3 : 1;   // fp64: one refinement solve; its forward sweep measures the dynamics residual of the first solve (certificate)
@@ -1385,10 +1461,7 @@ static int launch_qp_mw_t(slsqp_handle *h, const QpArgs &a, int max_iter) {
     const size_t lds = mw_lds_bytes<NX, NU>(h, W);
     if (lds > 160 * 1024) return fail("solve_waves: the work areas of that many waves do not fit the LDS for this horizon");
     const int max_ticks = qp_max_ticks(a, max_iter);
-    const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
-    if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
-    hipLaunchKernelGGL((k_qp_solve_mw<NX, NU>), dim3(h->B), dim3(64 * W), lds, h->st, a, max_ticks, h->cr, W);
-    if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
+    timed_launch(h, [&] { hipLaunchKernelGGL((k_qp_solve_mw<NX, NU>), dim3(h->B), dim3(64 * W), lds, h->st, a, max_ticks, h->cr, W); });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1408,35 +1481,20 @@ static int mw_refuse(const slsqp_handle *h, const slsqp_opts &o) {
     return 0;
 }
 
-static int launch_qp(slsqp_handle *h, const int *run, const slsqp_opts *o, int warm, const double *prox = nullptr, int stat_slot = 0, int snap_take = 0, int snap_use = 0,
-                     int warm_shift = 0) {
+// one QP solve of the instances of `run` (NULL = all), on the multi-wave or the single-wave kernel
+static int launch_qp(slsqp_handle *h, const int *run, const slsqp_opts *o, const QpCall &c) {
     h->ne_waves = 0;      // (this launch overwrites the factor buffers: slsqp_ne_solve(factor = 0) may not substitute with them)
-    if (h->solve_waves > 1) {
-        if (mw_refuse(h, *o)) return -1;
-        flag_nonfinite(h, run);
-        const QpArgs a = make_qp_args(h, h->runq, o, warm, prox, stat_slot, snap_take, snap_use, warm_shift);
-        h->time_kernels = o->time_kernels != 0;
-        h->mx_retry = 0;
-        int rc = -1;
-#define X(NX_, NU_) if (h->d.nx == NX_ && h->d.nu == NU_) rc = launch_qp_mw_t<NX_, NU_>(h, a, o->qp_max_iter);
-        SLSQP_DIM_LIST
-#undef X
-        if (rc) return -1;
-        apply_nonfinite(h, run, stat_slot);
-        return 0;
-    }
+    if (mw_refuse(h, *o)) return -1;
     flag_nonfinite(h, run);
-    const QpArgs a = make_qp_args(h, h->runq, o, warm, prox, stat_slot, snap_take, snap_use, warm_shift);
-    const bool mx = o->precision == 1;
+    set_x0_tol(h, qp_x0_tol(h, c));
+    const QpArgs a = make_qp_args(h, h->runq, o, c);
     h->time_kernels = o->time_kernels != 0;
+    h->mx_retry = 0;
+    const bool mw = h->solve_waves > 1, mx = o->precision == 1;      // (never both: mw_refuse)
     auto go = [&](const QpArgs &q, bool m) {
-#define X(NX_, NU_) if (h->d.nx == NX_ && h->d.nu == NU_) return launch_qp_t<NX_, NU_>(h, q, o->qp_max_iter, m);
-        SLSQP_DIM_LIST
-#undef X
-        return -1;
+        return with_dims(h, [&](auto NX, auto NU) { return mw ? launch_qp_mw_t<NX(), NU()>(h, q, o->qp_max_iter) : launch_qp_t<NX(), NU()>(h, q, o->qp_max_iter, m); });
     };
     if (go(a, mx)) return -1;
-    h->mx_retry = 0;
     if (mx) {
         HIPCHK(hipMemsetAsync(h->counter + 3, 0, sizeof(int), h->st));
         hipLaunchKernelGGL(k_mark_retry, dim3((h->B + 255) / 256), dim3(256), 0, h->st, h->B, a.run, h->status, h->retry, h->counter + 3);
@@ -1450,10 +1508,17 @@ static int launch_qp(slsqp_handle *h, const int *run, const slsqp_opts *o, int w
             if (go(r, false)) return -1;
         }
     }
-    apply_nonfinite(h, run, stat_slot);
+    apply_nonfinite(h, run, c.stat_slot);
     return 0;
 }
 
+template <int NX, int NU>
+static int launch_sweep_gen_t(slsqp_handle *h, const SweepArgs &a) {
+    const size_t lds = sizeof(double) * sweep_gen_lds_doubles<NX, NU>();
+    hipLaunchKernelGGL((k_sweep_gen<NX, NU>), dim3(h->B * (h->d.N + 1)), dim3(64), lds, h->st, (SweepGenArgs{a, h->Gd, h->Gfd, h->d.ni, h->d.ni_f}));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 template <int NX, int NU>
 static int launch_sweep_t(slsqp_handle *h, const SweepArgs &a) {
     const size_t lds = sizeof(double) * sweep_lds_doubles<NX, NU>();
@@ -1473,65 +1538,35 @@ static int launch_sweep_shared_t(slsqp_handle *h, const SweepArgs &a) {
 static bool sweep_shared_allowed() { static const bool v = getenv("SLSQP_SWEEP_SHARED") ? atoi(getenv("SLSQP_SWEEP_SHARED")) != 0 : true; return v; }
 // shared_cols: every column's eta is the same (first fast-SLS iteration after initialize_backoff): one Riccati recursion per instance
 static int launch_sweep(slsqp_handle *h, const int *run, const double *eta, const double *eta_f, double eps, bool shared_cols = false) {
-    SweepArgs a;
-    a.B = h->B; a.N = h->d.N; a.NW = h->d.nw; a.A = h->A; a.Bm = h->Bm; a.E = h->E; a.E_per_instance = 0; a.eta = eta; a.eta_f = eta_f;
-    a.run = run; a.cst = costs_of(h); a.K = h->K; a.beta = h->beta; a.beta_f = h->beta_f; a.ct_part = h->ct_part; a.eps = eps;
-    if (h->general_G) {
-        SweepGenArgs ga{a, h->Gd, h->Gfd, h->d.ni, h->d.ni_f};
-        const dim3 grid(h->B * (h->d.N + 1)), blk(64);
-#define X(NX_, NU_) if (h->d.nx == NX_ && h->d.nu == NU_) { const size_t lds = sizeof(double) * sweep_gen_lds_doubles<NX_, NU_>(); hipLaunchKernelGGL((k_sweep_gen<NX_, NU_>), grid, blk, lds, h->st, ga); }
-        SLSQP_DIM_LIST
-#undef X
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (shared_cols && sweep_shared_allowed()) {
-#define X(NX_, NU_) if (h->d.nx == NX_ && h->d.nu == NU_) return launch_sweep_shared_t<NX_, NU_>(h, a);
-        SLSQP_DIM_LIST
-#undef X
-        return -1;
-    }
-#define X(NX_, NU_) if (h->d.nx == NX_ && h->d.nu == NU_) return launch_sweep_t<NX_, NU_>(h, a);
-    SLSQP_DIM_LIST
-#undef X
-    return -1;
+    const SweepArgs a = sweep_args(h, run, eta, eta_f, eps);
+    return with_dims(h, [&](auto NX, auto NU) {
+        if (h->general_G) return launch_sweep_gen_t<NX(), NU()>(h, a);
+        if (shared_cols && sweep_shared_allowed()) return launch_sweep_shared_t<NX(), NU()>(h, a);
+        return launch_sweep_t<NX(), NU()>(h, a);
+    });
 }
 
-// what the last QP of a call changes in the first one's arguments: warm, statistics slot 1, restart from the first QP's iterate copy (make_qp_args
-// with warm = 1, stat_slot = 1, snap_use = 1 and everything else as for the first)
-static Qp2Ints qp_second_ints(const slsqp_opts &o) { return Qp2Ints{1, 1, o.ipm_restart ? 1 : 0}; }
-// arguments of one RTI chain (k_rti_chain / k_cl_loop): QP #1, what follows it, the sweep, the tightening, QP #2
-static int qp_max_ticks(const QpArgs &a, int max_iter);
+// arguments of one RTI chain (k_rti_chain / k_cl_loop): QP #1, what follows it, the sweep, the tightening, QP #2 (memset first: part of the persistent kernels' block)
 static ChainArgs make_chain_args(slsqp_handle *h, const slsqp_opts &o, const int *active, int wshift) {
-    const slsqp_dims &d = h->d;
-    const int B = h->B;
     ChainArgs c;
     memset(&c, 0, sizeof c);
-    c.q = make_qp_args(h, h->alive, &o, o.warm_start ? 1 : 0, nullptr, 0, 1, 0, wshift);
+    c.q = make_qp_args(h, h->alive, &o, qp_first_call(o.warm_start ? 1 : 0, wshift));
     c.q2 = qp_second_ints(o);
-    EtaArgs ea{B, d.N, d.nx, d.ni, d.ni_f, h->dual, h->beta, h->beta_f, h->alive, h->eta, h->eta_f, o.eps_backoff, h->stale, 1};
-    ConvArgs ca{B, h->n, h->primal, h->prev_primal, h->has_prev, h->alive, h->conv, o.conv_tol};
-    c.aq = AfterQpArgs{B, 1, 1, h->status, active, h->alive, h->infeas, h->mask, h->success, h->itnum, h->counter, h->stale, h->conv, ea, ca, h->beta, h->beta_f};
-    SweepArgs sa;
-    sa.B = h->B; sa.N = d.N; sa.NW = d.nw; sa.A = h->A; sa.Bm = h->Bm; sa.E = h->E; sa.E_per_instance = 0; sa.eta = h->eta; sa.eta_f = h->eta_f;
-    sa.run = h->mask; sa.cst = costs_of(h); sa.K = h->K; sa.beta = h->beta; sa.beta_f = h->beta_f; sa.ct_part = h->ct_part; sa.eps = o.eps_backoff;
-    c.sw = SweepSharedArgs{sa, h->Kc, h->Aclc, h->stale};
-    c.ta = TightenArgs{B, d.N, d.nx, d.nu, d.ni, d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, h->mask, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, 1, h->ct_part, h->cost_tube};
+    c.aq = after_qp_args(h, o, active, /* rti */ 1, /* first */ 1, /* shared_cols */ 1);
+    c.sw = SweepSharedArgs{sweep_args(h, h->mask, h->eta, h->eta_f, o.eps_backoff), h->Kc, h->Aclc, h->stale};
+    c.ta = tighten_args(h, h->mask, 1);
     c.active = active; c.success = h->success; c.infeas = h->infeas; c.times = h->chain_times;
     c.max_ticks = qp_max_ticks(c.q, o.qp_max_iter);
-    c.lag = nullptr; c.runm = nullptr; c.done = nullptr; c.t0word = nullptr; c.budget = 0; c.qplog = nullptr; c.x0vlog = nullptr; c.stepno = nullptr; c.log_steps = 0; c.fin_count = nullptr; c.cut_count = 0xFFFFFFFFu;
+    c.cut_count = 0xFFFFFFFFu;      // (lag, runm, done, t0word, budget, fin_count, the per-step log: NULL / 0, slsqp_cl_run's callers set them)
     return c;
 }
 
 // the fused RTI chain (k_rti_chain): one launch for QP #1 -> eta -> shared Riccati + propagation -> tightened bounds -> QP #2
 template <int NX, int NU>
 static int launch_chain_t(slsqp_handle *h, ChainArgs &c, const BndArgs *bd) {
-    const size_t lds = sizeof(double) * std::max({(size_t)qp_lds_doubles<NX, NU>(h->d.N), (size_t)(2 * h->n + 8), (size_t)sweep_lds_doubles<NX, NU>(), (size_t)sweep_prop_lds_doubles<NX, NU>()});
-    const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
-    if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
+    const size_t lds = chain_lds_bytes<NX, NU>(h);
     h->ne_waves = 0;      // (slsqp_ne_solve's factors do not survive a QP solve)
-    with_flag(bd != nullptr, [&](auto BND) { hipLaunchKernelGGL((k_rti_chain<NX, NU, BND()>), dim3(h->B), dim3(64), lds, h->st, c, bd ? *bd : BndArgs{}); });
-    if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
+    timed_launch(h, [&] { with_flag(bd != nullptr, [&](auto BND) { hipLaunchKernelGGL((k_rti_chain<NX, NU, BND()>), dim3(h->B), dim3(64), lds, h->st, c, bd ? *bd : BndArgs{}); }); });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1571,8 +1606,15 @@ static void tl_take(slsqp_handle *h) {     // accumulators -> the handle's timin
     }
     h->tl_acc[0] = h->tl_acc[1] = h->tl_acc[2] = h->tl_acc[3] = h->tl_acc[4] = 0;
 }
+// the tail of an entry point whose work is enqueued: return (no_sync: the caller synchronises the stream later and then calls tl_take), or wait and take the timeline
+static int finish_enqueued(slsqp_handle *h, bool no_sync) {
+    if (no_sync) return 0;
+    HIPCHK(hipStreamSynchronize(h->st));
+    tl_take(h);
+    return 0;
+}
 
-// no_sync: return with the launches queued (the caller synchronises the stream later and then calls tl_take)
+// no_sync: finish_enqueued
 // bd: the bounds whose window gives the tightening's terminal row (the closed-loop entry points of a handle with bounds), or NULL: the model's gf
 // (slsqp_solve brings its own g and always passes NULL)
 static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_opts *opts, const int *active, bool no_sync = false, const BndArgs *bd = nullptr) {
@@ -1600,30 +1642,22 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
     const int wshift = h->horizon_shifted; h->horizon_shifted = 0;
     const int tl_tot = tl_begin(h, 2);
     if (h->beta_inited) {     // every solve but the handle's first: the whole preamble in one launch
-        SolveBeginArgs sb{B, d.nx, loc == SLSQP_HOST ? nullptr : x0, h->x0val, active, h->alive, h->infeas, h->success, h->pending_reset, h->itnum, h->stale,
-                          h->eta, h->eta_f, (size_t)d.N * d.N * d.ni, (size_t)(d.N + 1) * d.ni_f,
-                          InitBackoffArgs{B, d.N, d.nx, d.nu, o.eps_backoff, active, h->beta, h->beta_f, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, 0}, h->cl_skip_begin};
-        hipLaunchKernelGGL(k_solve_begin, dim3(B), dim3(256), 0, h->st, sb);
+        hipLaunchKernelGGL(k_solve_begin, dim3(B), dim3(256), 0, h->st, solve_begin_args(h, o, loc == SLSQP_HOST ? nullptr : x0, active, h->cl_skip_begin));
     } else {
-    if (active) hipLaunchKernelGGL(k_copy_int, dim3(gb), dim3(256), 0, h->st, active, h->alive, B);
-    else hipLaunchKernelGGL(k_fill_int, dim3(gb), dim3(256), 0, h->st, h->alive, 1, B);
-    hipLaunchKernelGGL(k_apply_pending_reset, dim3(B), dim3(256), 0, h->st, B, h->pending_reset, active, h->itnum, h->eta, (size_t)d.N * d.N * d.ni, h->eta_f,
-                       (size_t)(d.N + 1) * d.ni_f, h->stale);
-    hipLaunchKernelGGL(k_fill_int, dim3(gb), dim3(256), 0, h->st, h->infeas, 0, B);
-    hipLaunchKernelGGL(k_fill_int, dim3(gb), dim3(256), 0, h->st, h->success, 0, B);
-    {   // initialize_backoff at the top of every solve (fast_SLS_jit.py:281,299)
-        // the first solve of a handle fills beta for every instance (also the ones outside `active`: later calls rely on it)
-        InitBackoffArgs ia{B, d.N, d.nx, d.nu, o.eps_backoff, h->beta_inited ? active : nullptr, h->beta, h->beta_f, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->beta_inited ? 0 : 1};
-        if (!h->beta_inited && active) {   // ... but their back-off arrays must stay untouched: two launches then
-            InitBackoffArgs ib = ia; ib.run = nullptr;
-            InitBackoffArgs ic = ia; ic.run = active; ic.fill_beta = 0;
+        if (active) hipLaunchKernelGGL(k_copy_int, dim3(gb), dim3(256), 0, h->st, active, h->alive, B);
+        else hipLaunchKernelGGL(k_fill_int, dim3(gb), dim3(256), 0, h->st, h->alive, 1, B);
+        hipLaunchKernelGGL(k_apply_pending_reset, dim3(B), dim3(256), 0, h->st, B, h->pending_reset, active, h->itnum, h->eta, (size_t)d.N * d.N * d.ni, h->eta_f,
+                           (size_t)(d.N + 1) * d.ni_f, h->stale);
+        hipLaunchKernelGGL(k_fill_int, dim3(gb), dim3(256), 0, h->st, h->infeas, 0, B);
+        hipLaunchKernelGGL(k_fill_int, dim3(gb), dim3(256), 0, h->st, h->success, 0, B);
+        // initialize_backoff at the top of every solve (fast_SLS_jit.py:281,299).  The first solve of a handle fills beta for every instance (also the
+        // ones outside `active`: later calls rely on it), but their back-off arrays must stay untouched: the fill is launches of its own then
+        if (active) {
             hipLaunchKernelGGL(k_fill_doubles, dim3(1024), dim3(256), 0, h->st, h->beta, o.eps_backoff, (size_t)B * d.N * d.N * d.ni);
             hipLaunchKernelGGL(k_fill_doubles, dim3(1024), dim3(256), 0, h->st, h->beta_f, o.eps_backoff, (size_t)B * (d.N + 1) * d.ni_f);
-            (void)ib;
-            hipLaunchKernelGGL(k_init_backoff, dim3(B), dim3(256), 0, h->st, ic);
-        } else hipLaunchKernelGGL(k_init_backoff, dim3(B), dim3(256), 0, h->st, ia);
+            hipLaunchKernelGGL(k_init_backoff, dim3(B), dim3(256), 0, h->st, init_backoff_args(h, o, active, 0));
+        } else hipLaunchKernelGGL(k_init_backoff, dim3(B), dim3(256), 0, h->st, init_backoff_args(h, o, nullptr, 1));
         h->beta_inited = true;
-    }
     }
     // (small batches keep the separate launches: there the SLS propagation of an instance runs as N + 1 waves side by side, which is what a B = 1 caller
     // waits for -- 1.1 against 1.6 ms per rocket RTI step -- while from ~150 instances on the columns of one instance would only compete with other
@@ -1632,6 +1666,7 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
     if (rti && steps == 1 && o.precision == 0 && fuse_here && h->solve_waves == 1 && chain_allowed() && sweep_shared_allowed() && !h->general_G) {
         // fast_SLS.solve with rti_steps = 1 (the rocket script's setting) as ONE launch: every wave takes its instance through the whole chain
         h->time_kernels = o.time_kernels != 0;
+        set_x0_tol(h, h->x0_box_tol);
         ChainArgs c = make_chain_args(h, o, active, wshift);
         if (h->cl_round) {      // a round of slsqp_cl_run: suspended solves resume, unfinished ones suspend at the deadline
             c.lag = h->cl_lag; c.runm = h->cl_runm; c.done = h->cl_done; c.t0word = h->t0word; c.budget = h->cl_budget;
@@ -1640,35 +1675,26 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
             HIPCHK(hipMemsetAsync(h->t0word, 0, 2 * sizeof(unsigned long long), h->st));
         } else flag_nonfinite(h, active, h->alive, h->infeas);      // (slsqp_cl_run's rounds and k_cl_loop linearise their own data; the NaN-keeping certificate guards them)
         const int tl_c = tl_begin(h, 4);
-        int rc = -1;
-#define X(NX_, NU_) if (d.nx == NX_ && d.nu == NU_) rc = launch_chain_t<NX_, NU_>(h, c, bd);
-        SLSQP_DIM_LIST
-#undef X
-        if (rc) return -1;
+        if (with_dims(h, [&](auto NX, auto NU) { return launch_chain_t<NX(), NU()>(h, c, bd); })) return -1;
         if (!h->cl_round) apply_nonfinite(h, active, 0);      // (an instance flagged at QP #1 never reaches QP #2)
         tl_end(h, tl_c);
         if (h->chain_times_host) HIPCHK(hipMemcpyAsync(h->chain_times_host, h->chain_times, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
         tl_end(h, tl_tot);
-        if (no_sync) return 0;
-        HIPCHK(hipStreamSynchronize(h->st));
-        tl_take(h);
-        return 0;
+        return finish_enqueued(h, no_sync);
     }
     for (int i = 0; i < steps; i++) {
         const int tl_q = tl_begin(h, 0);
-        if (launch_qp(h, h->alive, &o, (i > 0 || o.warm_start) ? 1 : 0, nullptr, 0, 1, i > 0 ? 1 : 0, i == 0 ? wshift : 0)) return -1;
+        QpCall qc = qp_first_call((i > 0 || o.warm_start) ? 1 : 0, i == 0 ? wshift : 0);
+        qc.snap_use = i > 0 ? 1 : 0;
+        if (launch_qp(h, h->alive, &o, qc)) return -1;
         tl_end(h, tl_q);
         // flags after the QP, evaluate_dual_eta, check_convergence_socp, masks and (first iteration) the beta repair: one launch
-        EtaArgs ea{B, d.N, d.nx, d.ni, d.ni_f, h->dual, h->beta, h->beta_f, h->alive, h->eta, h->eta_f, o.eps_backoff, h->stale, (i == 0 && sweep_shared_allowed()) ? 1 : 0};
-        ConvArgs ca{B, h->n, h->primal, h->prev_primal, h->has_prev, h->alive, h->conv, o.conv_tol};
         if (!rti) HIPCHK(hipMemsetAsync(h->counter, 0, sizeof(int), h->st));      // (the count of instances that go on is only read in converge mode)
-        AfterQpArgs aq{B, rti ? 1 : 0, i == 0 ? 1 : 0, h->status, active, h->alive, h->infeas, h->mask, h->success, h->itnum, h->counter, h->stale, h->conv, ea, ca, h->beta, h->beta_f};
-        hipLaunchKernelGGL(k_after_qp, dim3(B), dim3(256), 0, h->st, aq);
+        hipLaunchKernelGGL(k_after_qp, dim3(B), dim3(256), 0, h->st, after_qp_args(h, o, active, rti ? 1 : 0, i == 0 ? 1 : 0, (i == 0 && sweep_shared_allowed()) ? 1 : 0));
         const int tl_s = tl_begin(h, 1);
         if (launch_sweep(h, h->mask, h->eta, h->eta_f, o.eps_backoff, /* beta == eps for every column right after initialize_backoff */ i == 0)) return -1;
         tl_end(h, tl_s);
-        TightenArgs ta{B, d.N, d.nx, d.nu, d.ni, d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, h->mask, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, 1, h->ct_part, h->cost_tube};
-        launch_tighten(h, ta, bd);
+        launch_tighten(h, tighten_args(h, h->mask, 1), bd);
         if (rti) continue;      // RTI mode (every closed-loop script): nothing to decide on the host, the stream runs on
         int nmask = 0;
         HIPCHK(hipMemcpyAsync(&nmask, h->counter, sizeof(int), hipMemcpyDeviceToHost, h->st));
@@ -1677,14 +1703,11 @@ static int solve_impl(slsqp_handle *h, const double *x0, int loc, const slsqp_op
     }
     // final QP: RTI always (fast_SLS_jit.py:293); converge mode only for instances that hit MAX_ITER (:311)
     const int tl_q2 = tl_begin(h, 0);
-    if (launch_qp(h, h->alive, &o, 1, nullptr, 1, 1, 1, wshift)) return -1;
+    if (launch_qp(h, h->alive, &o, qp_last_call(wshift))) return -1;
     tl_end(h, tl_q2);
     hipLaunchKernelGGL(k_finish, dim3(gb), dim3(256), 0, h->st, B, rti ? 1 : 0, h->alive, h->infeas, h->success, active, h->pending_reset);
     tl_end(h, tl_tot);
-    if (no_sync) return 0;
-    HIPCHK(hipStreamSynchronize(h->st));
-    tl_take(h);
-    return 0;
+    return finish_enqueued(h, no_sync);
 }
 
 extern "C" int slsqp_solve(slsqp_handle *h, const double *x0, int loc, const slsqp_opts *opts) { return solve_impl(h, x0, loc, opts, nullptr); }
@@ -1912,7 +1935,6 @@ extern "C" int slsqp_reset(slsqp_handle *h) {
     hipSetDevice(h->dev);
     // reset_solver_to_zeros (fast_SLS_jit.py:424-442): eta/eta_f/iteration_number to zero, bounds and linear cost dropped.
     // `_prev_primal_vec` is NOT cleared by the reference (quirk q5) and is not cleared here.
-    const slsqp_dims &d = h->d;
     const size_t B = h->B;
     // eta, eta_f and K (1.5 GB at rocket B = 4096) are not cleared here: every entry the device reads is rewritten first (evaluate_dual_eta before the
     // sweep, the sweep before anything reads K), so they are only marked stale and zeroed on demand when slsqp_get asks for them
@@ -1920,11 +1942,9 @@ extern "C" int slsqp_reset(slsqp_handle *h) {
     HIPCHK(hipMemsetAsync(h->itnum, 0, sizeof(int) * B, h->st));
     HIPCHK(hipMemsetAsync(h->pending_reset, 0, sizeof(int) * B, h->st));
     HIPCHK(hipMemsetAsync(h->q, 0, sizeof(double) * B * h->n, h->st));
-    (void)d;
     h->have_dyn = false;
     return 0;
 }
-
 
 // ---- linearisation step in front of the path (SCP_SLS.update_jacobian) ----------------------------------------------
 extern "C" int slsqp_set_model(slsqp_handle *h, int model_id, const double *g_raw) {
@@ -1958,7 +1978,7 @@ static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int
         HIPCHK(hipMemcpyAsync(tmp + nX, U, sizeof(double) * nU, hipMemcpyHostToDevice, h->st));
         dX = tmp; dU = tmp + nX;
     }
-    LinArgs a{h->B, d.N, dX, dU, h->g_raw, h->gf_raw, costs_of(h), h->A, h->Bm, h->c, h->g, h->gN, h->q, run, h->lin_stage, h->lin_tape};
+    const LinArgs a = lin_args(h, dX, dU, run);
     const int grid = 2048, blk = 128;
     const int gval = (int)((B * d.N + blk - 1) / blk);
     const ClOptions op = cl_options(h);
@@ -1967,8 +1987,7 @@ static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int
             hipLaunchKernelGGL((k_lin_val<M()>), dim3(gval), dim3(blk), 0, h->st, a); hipLaunchKernelGGL((k_lin_tan<M()>), dim3(grid), dim3(blk), 0, h->st, a);
             with_ref_bnd(op, [&](auto REF, auto BND) { hipLaunchKernelGGL((k_lin_vec<NX, NU, REF(), BND()>), dim3(grid), dim3(256), 0, h->st, a, op.own_rf, bnd_args(h, step, stepno)); });
         })) return -1;
-    BoundsArgs ba{h->B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, run};
-    hipLaunchKernelGGL(k_set_bounds, dim3(1024), dim3(256), 0, h->st, ba);
+    hipLaunchKernelGGL(k_set_bounds, dim3(1024), dim3(256), 0, h->st, bounds_args(h, run));
     HIPCHK(hipGetLastError());
     if (loc == SLSQP_HOST) HIPCHK(hipStreamSynchronize(h->st));   // the caller's buffers may be reused on return; device callers stay asynchronous on the handle's stream
     h->have_dyn = true;
@@ -1976,15 +1995,7 @@ static int linearize_impl(slsqp_handle *h, const double *X, const double *U, int
 }
 extern "C" int slsqp_linearize(slsqp_handle *h, const double *X, const double *U, int loc) { return linearize_impl(h, X, U, loc, nullptr, h->cl_steps); }
 
-
 // ---- closed-loop driver around the path (SCP_SLS.solve + reset_warm_start + plant) -------------------------
-static ClArgs cl_args(slsqp_handle *h, const double *w) {
-    ClArgs a;
-    a.B = h->B; a.N = h->d.N; a.NX = h->d.nx; a.NU = h->d.nu; a.Xn = h->Xn; a.Un = h->Un; a.xmeas = h->xmeas; a.primal = h->primal;
-    a.success = h->success; a.x0arg = h->x0arg; a.E = h->E; a.w = w; a.u0 = h->u0; a.u_init = h->u_init;
-    return a;
-}
-
 extern "C" int slsqp_cl_init(slsqp_handle *h, const double *x_meas, const double *X_nom, const double *U_nom, const double *u_init, int loc) {
     hipSetDevice(h->dev);
     if (h->model_id < 0) return fail("slsqp_set_model must be called first");
@@ -2025,7 +2036,6 @@ extern "C" int slsqp_nominal_solve(slsqp_handle *h, int max_qp, double tol, doub
     if (!(rho > 0.0)) rho = 1e3;
     int *active = h->scp_active;
     hipLaunchKernelGGL(k_nom_init, dim3(gbi), dim3(256), 0, h->st, B, h->nom_st, active, h->nom_need_lin, h->nom_status, h->nom_iters, 1.0, 0.5);
-    ClArgs ca = cl_args(h, nullptr);
     NomArgs na;
     na.B = B; na.N = d.N; na.Xn = h->Xn; na.Un = h->Un; na.xmeas = h->xmeas; na.primal = h->primal; na.qp_status = h->status; na.g_raw = h->g_raw; na.gf_raw = h->gf_raw;
     na.cst = costs_of(h); na.st = h->nom_st; na.active = active; na.need_lin = h->nom_need_lin; na.status = h->nom_status; na.iters = h->nom_iters;
@@ -2045,7 +2055,9 @@ extern "C" int slsqp_nominal_solve(slsqp_handle *h, int max_qp, double tol, doub
         hipLaunchKernelGGL(k_nom_bounds, dim3(1024), dim3(256), 0, h->st, ba);
         hipLaunchKernelGGL(k_nom_x0, dim3((B * d.nx + 255) / 256), dim3(256), 0, h->st, B, d.N, d.nx, h->Xn, h->xmeas, h->nom_st, h->x0val);
         HIPCHK(hipEventRecord(h->ev[6], h->st));
-        if (launch_qp(h, active, &o, it > 0 ? 1 : 0, h->nom_st /* S[0] = w: stride 12 */)) return -1;
+        QpCall qc;
+        qc.warm = it > 0 ? 1 : 0; qc.prox = h->nom_st;      // (S[0] = w: stride 12)
+        if (launch_qp(h, active, &o, qc)) return -1;
         HIPCHK(hipEventRecord(h->ev[7], h->st));
         HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
         if (eval(1)) return -1;
@@ -2138,8 +2150,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
         const BndArgs bd = bnd_args(h, h->cl_steps, nullptr);      // (the tightening's terminal row: the window of this step)
         if (solve_impl(h, h->x0arg, SLSQP_DEVICE, &o, h->scp_active, /* no_sync */ true, op.bnd ? &bd : nullptr)) return -1;
         HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
-        ScpArgs sa{ii, converge ? 1 : 0, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
-        hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, sa);
+        hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, scp_args(h, o, ii, converge ? 1 : 0));
         if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_infeas<M()>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf); })) return -1;
         if (ii + 1 == max_it) break;
         if (converge) {     // the host decides whether anyone is still iterating; RTI mode runs its rti iterations without looking (the instances that
@@ -2155,9 +2166,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
         tl_end(h, tl_j);
     }
     if (h->log_steps > 0 && h->cl_steps < h->log_steps) {
-        ClLogArgs la{nullptr, nullptr, h->B, d.N, d.nx, d.nu, h->log_steps, h->cl_steps, h->Xn, h->Un, h->backoff_x, h->backoff_u, h->scp_success, h->scp_iters,
-                     h->pinf, h->lg_x, h->lg_u, h->lg_bx, h->lg_bu, h->lg_state, h->lg_u0, h->lg_pinf, h->lg_succ, h->lg_it};
-        hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, la);
+        hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, cl_log_args(h, nullptr, nullptr, h->cl_steps));
         hipLaunchKernelGGL(k_cl_log_x0v, dim3((2 * h->B + 255) / 256), dim3(256), 0, h->st, h->B, h->log_steps, h->cl_steps, h->x0viol, h->qpstat, h->lg_x0v);
         h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};      // (a slsqp_cl_run in between points the name at its own per-run buffer)
     }
@@ -2166,8 +2175,7 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
             else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
         })) return -1;
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->st));
-    tl_take(h);
+    if (finish_enqueued(h, false)) return -1;
     h->cl_steps++;
     return 0;
 }
@@ -2181,7 +2189,7 @@ __global__ void k_cl_begin_flags(int B, const int *begin, int *scp_success, int 
 template <int MODEL>
 static int launch_loop_t(slsqp_handle *h, bool S) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    const size_t lds = sizeof(double) * std::max({(size_t)qp_lds_doubles<NX, NU>(h->d.N), (size_t)(2 * h->n + 8), (size_t)sweep_lds_doubles<NX, NU>(), (size_t)sweep_prop_lds_doubles<NX, NU>()});
+    const size_t lds = chain_lds_bytes<NX, NU>(h);
     int cu = 0;
     if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, h->dev) != hipSuccess || cu <= 0) cu = 256;
     const int env_waves = getenv("SLSQP_LOOP_WAVES") ? atoi(getenv("SLSQP_LOOP_WAVES")) : 0;      // (tests / experiments: fewer waves than the GPU holds)
@@ -2189,24 +2197,24 @@ static int launch_loop_t(slsqp_handle *h, bool S) {
     const int grid = std::max(1, std::min(h->B, slots));
     h->cl_loop_waves = grid;
     const ScpLoopArgs *blk = (const ScpLoopArgs *)h->loop_blk;
-    const bool timed = h->time_kernels && h->n_kev + 2 <= (int)h->kev.size();
-    if (timed) hipEventRecord(h->kev[h->n_kev], h->st);
-    hipEventRecord(h->ev[8], h->st);
     const ClOptions op = cl_options(h);      // (the bounds themselves are in the block: make_loop_block)
-    if (!with_loop_var(op.var, [&](auto V) {
-            if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of the maximum above)
+    bool found = false;
+    timed_launch(h, [&] {
+        hipEventRecord(h->ev[8], h->st);
+        found = with_loop_var(op.var, [&](auto V) {
+            if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of chain_lds_bytes)
             else hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);
-        })) return fail("no persistent closed-loop kernel for variant " + std::to_string(op.var));
-    hipEventRecord(h->ev[9], h->st);
-    if (timed) { hipEventRecord(h->kev[h->n_kev + 1], h->st); h->n_kev += 2; }
+        });
+        hipEventRecord(h->ev[9], h->st);
+    });
+    if (!found) return fail("no persistent closed-loop kernel for variant " + std::to_string(op.var));
     HIPCHK(hipGetLastError());
     return 0;
 }
-// the argument block of one persistent launch (every byte defined: the block is copied and compared as bytes); no HIP call in here
+// the argument block of one persistent launch, composed of the builders' results (memset first: the block is copied and compared as bytes); no HIP call in
+// here -- the x0 tolerance its QPs ask for is cl_run_persistent's to write
 static ScpLoopArgs make_loop_block(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, bool scp, int scp_rti) {
     const int max_it = !scp ? 1 : (scp_rti > 0 ? scp_rti : o.max_scp_iter);
-    const slsqp_dims &d = h->d;
-    const int B = h->B;
     ScpLoopArgs S;
     memset(&S, 0, sizeof S);
     LoopArgs &L = S.L;
@@ -2216,14 +2224,11 @@ static ScpLoopArgs make_loop_block(slsqp_handle *h, int steps, const double *dW,
     L.c.q.shift_stepno = h->cl_stepno;      // the horizon has moved for the instances past their first step
     L.c.qplog = h->qplog; L.c.x0vlog = h->x0vlog; L.c.stepno = h->cl_stepno; L.c.log_steps = h->qplog_steps;
     L.cl = cl_args(h, nullptr);
-    L.lin = LinArgs{B, d.N, h->Xn, h->Un, h->g_raw, h->gf_raw, costs_of(h), h->A, h->Bm, h->c, h->g, h->gN, h->q, nullptr, h->lin_stage, h->lin_tape};
-    L.ba = BoundsArgs{B, d.N, d.nx, d.ni, d.ni_f, h->g, h->gN, h->c, h->ubg, h->lbg, 1e-10, nullptr};
-    L.sb = SolveBeginArgs{B, d.nx, h->x0arg, h->x0val, active, h->alive, h->infeas, h->success, h->pending_reset, h->itnum, h->stale,
-                          h->eta, h->eta_f, (size_t)d.N * d.N * d.ni, (size_t)(d.N + 1) * d.ni_f,
-                          InitBackoffArgs{B, d.N, d.nx, d.nu, o.eps_backoff, active, h->beta, h->beta_f, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, 0}, nullptr};
-    L.lg = ClLogArgs{h->cl_stepno, nullptr, B, d.N, d.nx, d.nu, h->log_steps, 0, h->Xn, h->Un, h->backoff_x, h->backoff_u, h->scp_success, h->scp_iters,
-                     h->pinf, h->lg_x, h->lg_u, h->lg_bx, h->lg_bu, h->lg_state, h->lg_u0, h->lg_pinf, h->lg_succ, h->lg_it};
-    L.sa = ScpArgs{0, 0, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
+    L.lin = lin_args(h, h->Xn, h->Un, nullptr);
+    L.ba = bounds_args(h, nullptr);
+    L.sb = solve_begin_args(h, o, h->x0arg, active, nullptr);
+    L.lg = cl_log_args(h, h->cl_stepno, nullptr, 0);
+    L.sa = scp_args(h, o, 0, 0);
     L.steps = steps; L.n = h->n; L.have_log = h->log_steps > 0 ? 1 : 0;
     L.keep_laggards = getenv("SLSQP_LOOP_KEEP") ? atoi(getenv("SLSQP_LOOP_KEEP")) : 1;
     L.fence = getenv("SLSQP_LOOP_FENCE") ? atoi(getenv("SLSQP_LOOP_FENCE")) : 3;      // (experiments only: 0 drops the hand-over fences)
@@ -2259,6 +2264,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
         h->beta_inited = true;
     }
     h->time_kernels = o.time_kernels != 0;
+    set_x0_tol(h, h->x0_box_tol);
     const ScpLoopArgs S = make_loop_block(h, steps, dW, o, scp, scp_rti);
     const LoopArgs &L = S.L;
     if (write_loop_block(h, S)) return -1;
@@ -2280,8 +2286,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
         if (scp) memset(h->chain_times_host, 0, 4 * sizeof(unsigned long long));      // (no per-part clock in the general step: the launch counts as QP time)
         else HIPCHK(hipMemcpyAsync(h->chain_times_host, h->chain_times, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
     }
-    HIPCHK(hipStreamSynchronize(h->st));
-    tl_take(h);
+    if (finish_enqueued(h, false)) return -1;
     h->cl_loop_ms = ev_ms(h->ev[8], h->ev[9]);
     h->have_dyn = true;
     int unfinished = 0;
@@ -2360,7 +2365,6 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
     h->ne_waves = 0;      // (slsqp_ne_solve's factors do not survive a QP solve)
     if (!(o.rti_steps == 1 && o.precision == 0 && o.fuse_rti && chain_allowed() && sweep_shared_allowed()) || h->general_G)
         return fail("slsqp_cl_run needs the fused RTI chain: rti_steps = 1, fp64, fuse_rti = 1, box constraints (use slsqp_cl_step otherwise)");
-    const slsqp_dims &d = h->d;
     const int B = h->B, gbi = (B + 255) / 256, gb = (B + 63) / 64;
     const double *dW = nullptr;
     if (cl_run_prepare(h, steps, W, loc, &dW)) return -1;
@@ -2402,14 +2406,9 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         // end of the step for the instances whose chain is done: nominal += delta, primal_infeasibility, log entry, plant + noise, step counter
         hipLaunchKernelGGL(k_copy_int, dim3(gbi), dim3(256), 0, h->st, h->cl_done, h->scp_active, B);
         HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
-        ScpArgs sa{0, 0, o.scp_eps, h->scp_active, h->scp_success, h->scp_iters, h->counter + 2, h->scp_dmax, h->scp_upd};
-        hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, sa);
+        hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, scp_args(h, o, 0, 0));
         if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_infeas<M()>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf); })) return -1;
-        if (h->log_steps > 0) {
-            ClLogArgs la{h->cl_stepno, h->cl_done, h->B, d.N, d.nx, d.nu, h->log_steps, 0, h->Xn, h->Un, h->backoff_x, h->backoff_u, h->scp_success, h->scp_iters,
-                         h->pinf, h->lg_x, h->lg_u, h->lg_bx, h->lg_bu, h->lg_state, h->lg_u0, h->lg_pinf, h->lg_succ, h->lg_it};
-            hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, la);
-        }
+        if (h->log_steps > 0) hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, cl_log_args(h, h->cl_stepno, h->cl_done, 0));
         if (with_model(h, [&](auto M) {
                 if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, op.pa, 0, h->cl_done, h->cl_stepno, dW);
                 else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
@@ -2508,7 +2507,9 @@ extern "C" int slsqp_qp_solve(slsqp_handle *h, double *x, double *y, int *status
     if (opts) o = *opts; else slsqp_default_opts(&o);
     if (mw_refuse(h, o)) return -1;
     HIPCHK(hipEventRecord(h->ev[0], h->st));
-    if (launch_qp(h, nullptr, &o, o.warm_start ? 1 : 0)) return -1;
+    QpCall qc;
+    qc.warm = o.warm_start ? 1 : 0;
+    if (launch_qp(h, nullptr, &o, qc)) return -1;
     HIPCHK(hipEventRecord(h->ev[1], h->st));
     HIPCHK(hipStreamSynchronize(h->st));
     harvest_kernel_events(h);
@@ -2540,8 +2541,7 @@ extern "C" int slsqp_sweep(slsqp_handle *h, const double *eta, const double *eta
     HIPCHK(hipEventRecord(h->ev[0], h->st));
     if (launch_sweep(h, nullptr, h->eta, h->eta_f, 1e-10)) return -1;
     HIPCHK(hipEventRecord(h->ev[1], h->st));
-    TightenArgs ta{h->B, d.N, d.nx, d.nu, d.ni, d.ni_f, h->beta, h->beta_f, h->g, h->gf_raw, h->c, nullptr, h->backoff, h->backoff_f, h->backoff_x, h->backoff_u, h->ubg, 0, h->ct_part, h->cost_tube};
-    launch_tighten(h, ta, nullptr);
+    launch_tighten(h, tighten_args(h, nullptr, 0), nullptr);
     HIPCHK(hipEventRecord(h->ev[2], h->st));
     HIPCHK(hipStreamSynchronize(h->st));
     h->t_sweep = ev_ms(h->ev[0], h->ev[1]); h->t_total = ev_ms(h->ev[0], h->ev[2]); h->t_qp = 0;
@@ -2557,7 +2557,6 @@ extern "C" int slsqp_sweep(slsqp_handle *h, const double *eta, const double *eta
     HIPCHK(hipStreamSynchronize(h->st));
     return 0;
 }
-
 
 // ---- self-test of the wave-level building blocks (wave_la.hpp) ---------------------------------------------------
 // One wave runs one primitive on operands the caller supplies; tests/test_gpu_parity.py compares with numpy.  `in` / `out` are packed
@@ -2643,10 +2642,7 @@ extern "C" int slsqp_ne_solve(slsqp_handle *h, int waves, int factor, const doub
     if (!rc) {
         // the QP solves' own stored factors live in the same scratch: they are gone after this call
         forget_factors(h);
-        rc = -2;
-#define X(NX_, NU_) if (h->d.nx == NX_ && h->d.nu == NU_) rc = launch_ne_solve_t<NX_, NU_>(h, waves, factor, delta, dPI, dV, dW, dG, dUF, dout);
-        SLSQP_DIM_LIST
-#undef X
+        if (with_dims(h, [&](auto NX, auto NU) { return launch_ne_solve_t<NX(), NU()>(h, waves, factor, delta, dPI, dV, dW, dG, dUF, dout); })) rc = -2;      // (-2: the message is already there)
     }
     if (!rc && hipMemcpyAsync(W, dW, sizeof(double) * B * nw, kout, h->st) != hipSuccess) rc = -1;
     if (!rc && hipMemcpyAsync(G, dG, sizeof(double) * B * n, kout, h->st) != hipSuccess) rc = -1;
