@@ -241,13 +241,16 @@ __device__ __forceinline__ int ne_forward(double *sm, const NeG<NX, NU> g, bool 
     int fail = 0;
     // software pipeline: stage k+1's blocks are fetched HBM/L2 -> registers while stage k is being processed
     IO io;
-    double rPi = 0.0, rV = 0.0, rE = 0.0;
+    // Nothing in the prefetch is consumed before the next stage's start: vector loads return in order, so one value used
+    // at once would land the whole prefetch with it.  The bound pair therefore travels as loaded, on every path (with eflag == 0 it is not
+    // used), and e_k is formed where it is read.
+    double rPi = 0.0, rV = 0.0, rEu = 0.0, rEl = 0.0;
     auto prefetch = [&](int k) {
+        const int ls = min(lane, NZ + NX - 1), lx = min(lane, NX - 1);
+        rEu = g.ub[k * SR + lx]; rEl = g.lb[k * SR + lx];
         io.load_AB(g.A + (size_t)k * MM, g.Bm + (size_t)k * NX * NU, lane);
         if (!(factor_all && k >= k0)) io.load_L(g.Linv + (size_t)k * IO::DSTR, lane);
-        const int ls = min(lane, NZ + NX - 1), lx = min(lane, NX - 1);
         rPi = g.PI[k * NZ + ls]; rV = g.V[k * NZ + ls];
-        if (eflag != 0.0) rE = 0.5 * (g.ub[k * SR + lx] + g.lb[k * SR + lx]);
     };
     if (ks > 0) {
         io.load_L(g.Linv + (size_t)(ks - 1) * IO::DSTR, lane);
@@ -260,7 +263,8 @@ __device__ __forceinline__ int ne_forward(double *sm, const NeG<NX, NU> g, bool 
         io.store_AB(sA, sB, lane);
         if (!factor) io.store_L(Lcur, lane);
         if (lane < NZ + NX) { sPiS[lane] = rPi; sVS[lane] = rV; }
-        const double ek = rE;
+        double ek = (eflag != 0.0) ? 0.5 * (rEu + rEl) : 0.0;
+        asm volatile("" : "+v"(ek));      // formed here: sunk to its use behind the prefetch it would keep the old pair live across the new one's load, and the copy at the back edge lands it
         wla::wsync();
         if (k + 1 < g.N) prefetch(k + 1);
         if (factor) {
@@ -324,12 +328,14 @@ __device__ __forceinline__ void ne_backward(double *sm, const NeG<NX, NU> g, int
         const int lx = min(lane, NX - 1);
         r.Pi = g.PI[(k + 1) * NZ + lx]; r.W = g.UF[k * NX + lx];
     };
-    auto stage = [&](int k, StageRegs &r) {
+    // Every stage of the loop reloads its set, the last two with stage 0 again (a valid stage, never used): with a load on every path the
+    // number of loads behind a set's own is the same wherever a stage starts, and the wait for the set leaves the other one in flight
+    auto stage = [&](int k, StageRegs &r, bool reload) {
         r.io.store_AB(sA, sB, lane);
         r.io.store_L(sLa, lane);
         if (lane < NX) { sPiS[lane] = r.Pi; sWp[lane] = r.W; }
         wla::wsync();
-        if (k >= 2) load(k - 2, r);
+        if (reload) load(max(k - 2, 0), r);
         if (lane < NX) sT1[lane] = sPiS[lane] * sT3[lane];
         wla::wsync();
         // nu_k = u_k - Dinv_k O_{k+1}' nu_{k+1} = u_k + Dinv_k (pi_x,k+1 .* A_{k+1}' nu_{k+1})
@@ -349,11 +355,13 @@ __device__ __forceinline__ void ne_backward(double *sm, const NeG<NX, NU> g, int
         wla::wsync();
     };
     load(g.N - 1, r0);
-    if (g.N >= 2) load(g.N - 2, r1);
-    for (int k = g.N - 1; k >= 0; k -= 2) {
-        stage(k, r0);
-        if (k >= 1) stage(k - 1, r1);
+    load(max(g.N - 2, 0), r1);
+    int k = g.N - 1;
+    for (; k >= 1; k -= 2) {
+        stage(k, r0, true);
+        stage(k - 1, r1, true);
     }
+    if (k == 0) stage(0, r0, false);      // odd N: the last stage, nothing left to load
     if (lane < NX) g.G[lane] = sT3[lane];
 }
 
@@ -1941,17 +1949,19 @@ __device__ __forceinline__ void sweep_ric1_dev(const SweepSharedArgs &aa, int b,
     }
     wla::wsync();
     constexpr int RA = (NX * NX + 63) / 64, RB = (NX * NU + 63) / 64;
-    double rA[RA], rB[RB], rC = 0.0;
+    // the eta pair travels as loaded, ahead of the blocks, and is summed where the stage reads it: summed inside the fetch it would land the
+    // blocks of the same fetch with it
+    double rA[RA], rB[RB], rCu = 0.0, rCl = 0.0;
     const int lz = min(lane, NZ - 1);
     const double regd = (lz < NX) ? a.cst.Qregd[lz] : a.cst.Rregd[lz - NX];
     auto fetch = [&](int k) {
         const double *Ak = gA + (size_t)k * NX * NX, *Bk = gB + (size_t)k * NX * NU;
+        const double *e = eta + ((size_t)k * N + j) * NI;
+        rCu = e[lz]; rCl = e[NZ + lz];
 #pragma unroll
         for (int r = 0; r < RA; r++) rA[r] = Ak[min(r * 64 + lane, NX * NX - 1)];
 #pragma unroll
         for (int r = 0; r < RB; r++) rB[r] = Bk[min(r * 64 + lane, NX * NU - 1)];
-        const double *e = eta + ((size_t)k * N + j) * NI;
-        rC = e[lz] + e[NZ + lz] + regd;
     };
     if (lane == 0 && aa.stale) aa.stale[b] = (aa.stale[b] & ~2) | 32;
     fetch(N - 1);
@@ -1960,7 +1970,7 @@ __device__ __forceinline__ void sweep_ric1_dev(const SweepSharedArgs &aa, int b,
         for (int r = 0; r < RA; r++) { const int o = r * 64 + lane; if (o < NX * NX) sA[o] = rA[r]; }
 #pragma unroll
         for (int r = 0; r < RB; r++) { const int o = r * 64 + lane; if (o < NX * NU) sB[o] = rB[r]; }
-        if (lane < NZ) sC[lane] = rC;
+        if (lane < NZ) sC[lane] = rCu + rCl + regd;
         wla::wsync();
         if (k - 1 >= 0) fetch(k - 1);
 #if SWEEP_MFMA
@@ -2082,6 +2092,10 @@ __device__ __forceinline__ void sweep_prop_dev(const SweepSharedArgs &aa, int b,
 #pragma unroll
         for (int r = 0; r < RB; r++) rK[r] = Kk[min(r * 64 + lane, NX * NU - 1)];
     };
+    // the row weights of the tube cost are batch constants: read once, ahead of the stage loop (a load inside it that is used at once would
+    // land the next stage's fetch2 with it)
+    const int lz = min(lane, NZ - 1);
+    const double wreg = (lz < NX) ? a.cst.Qregd[lz] : a.cst.Rregd[lz - NX];
     // row norms of [Phi_x; Phi_u] of column j at stage k -> beta, tube cost
     auto norms = [&](const double *Pc, const double *sPu, int k, int j, double &ctube) {
         const int g3 = lane / NZ, rw = lane - g3 * NZ;
@@ -2093,7 +2107,7 @@ __device__ __forceinline__ void sweep_prop_dev(const SweepSharedArgs &aa, int b,
         }
         s = s + __shfl(s, lane + NZ) + __shfl(s, lane + 2 * NZ);
         if (lane < NZ) {
-            const double wr = (lane < NX) ? a.cst.Qregd[lane] : a.cst.Rregd[lane - NX];
+            const double wr = wreg;
             ctube = fma(wr * wr, s, ctube);
             s = fmax(s, a.eps);
             double *bo = beta + ((size_t)k * N + j) * NI;
