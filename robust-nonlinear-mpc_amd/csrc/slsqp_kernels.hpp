@@ -9,6 +9,7 @@
 //   k_qp_solve                the QP of QP.solve            solver/qp_jit.py:362-402 (data layout :77-192)
 //   k_sweep_ric1 / _prop      _backward_solve_numba / _propagate / _backoff_from_phi (beta part), first fast-SLS iteration   fast_SLS_jit.py:43-158
 //   k_sweep / k_sweep_gen     the same for later iterations / a general constraint matrix G
+//                             (one statement of each step for all of them: ric_recursion / ric_stage, tube_norms, tube_terminal, sweep_gemm, SweepBlock, SweepLds)
 //   k_tighten                 _backoff_from_phi (sums) + update_tightening tail             :160-188, :556-569
 //   k_set_bounds              QP.update_dynamics + offset_constraints  solver/qp_jit.py:268-273, 595-610
 //   k_lin_val / _tan / _vec   SCP_SLS.update_jacobian       solver/SCP_SLS_jit.py:251-366
@@ -1518,12 +1519,31 @@ struct SweepArgs {
     double eps;
 };
 
+// LDS layout of one sweep wave (offsets in doubles): A_k | S_{k+1} | y = A'S, then B_k, x = B'S, F = x A, K_k, Phi_u, H and the cost diagonal C.
+// Aliases: A + B K replaces A_k in place (oAcl = oA: every use of A_k precedes it); y (A + B K) lands where S_{k+1} was (oSn = oS: dead once B'S and
+// A'S are formed) and is symmetrised in place; the Riccati buffers are dead in the propagate phase, which keeps Phi_k / Phi_{k+1} in oPhi = oS and
+// oPhi2 = oYm (NW == NX).  GEN: k_sweep_gen's layout, the full cost blocks C_xx (oCx, behind y) and C_uu (oC) in place of the diagonal.
+template <int NX, int NU, bool GEN = false>
+struct SweepLds {
+    static constexpr int MM = NX * NX, NB = NX * NU;
+    static constexpr int oA = 0, oS = MM, oYm = 2 * MM, oCx = 3 * MM, oB = GEN ? 4 * MM : 3 * MM, oX = oB + NB, oF = oX + NB, oK = oF + NB, oPu = oK + NB,
+                         oH = oPu + NB, oC = oH + NU * NU, TOTAL = oC + (GEN ? NU * NU : NX + NU) + 8;
+    static constexpr int oAcl = oA, oSn = oS, oPhi = oS, oPhi2 = oYm;
+    static_assert(TOTAL == (GEN ? 4 * MM + 5 * NB + 2 * NU * NU + 8 : 3 * MM + 5 * NB + NU * NU + (NX + NU) + 8), "the totals the host has always sized the launches with");
+};
+// ... of one propagate-only wave (sweep_prop_dev): A_k + B_k K_k, Phi_k / Phi_{k+1} of its two columns, K_k, Phi_u of the two columns
 template <int NX, int NU>
-__host__ __device__ constexpr int sweep_lds_doubles() {
-    // sA sS sYm (3 NX^2: A + B K is formed in place in sA, y (A + B K) in sS, the propagate phase reuses sS / sYm for Phi, NW == NX)
-    // + sB sX sF sK sPu (5 NX NU) + sH (NU^2) + sC (NX+NU)
-    return 3 * NX * NX + 5 * NX * NU + NU * NU + (NX + NU) + 8;
-}
+struct SweepPropLds {
+    static constexpr int MM = NX * NX, NB = NX * NU;
+    static constexpr int oAcl = 0, oPcA = MM, oPnA = 2 * MM, oPcB = 3 * MM, oPnB = 4 * MM, oK = 5 * MM, oPuA = oK + NB, oPuB = oPuA + NB, TOTAL = oPuB + NB + 8;
+    static_assert(TOTAL == 5 * MM + 3 * NB + 8, "the total the host has always sized the launches with");
+};
+template <int NX, int NU>
+__host__ __device__ constexpr int sweep_lds_doubles() { return SweepLds<NX, NU>::TOTAL; }
+template <int NX, int NU>
+__host__ __device__ constexpr int sweep_gen_lds_doubles() { return SweepLds<NX, NU, true>::TOTAL; }
+template <int NX, int NU>
+__host__ __device__ constexpr int sweep_prop_lds_doubles() { return SweepPropLds<NX, NU>::TOTAL; }
 
 // SWEEP_MFMA (default 1): the dense products of the sweep (A'S, y Acl, Acl Phi, B'S, x A, K Phi, A + B K) run on the fp64 matrix core for
 // NX >= 13 (wla::gemm_mfma: one 16x16 tile, the 17th row / column / k on the vector ALU beside it); 0 = vector-ALU GEMMs only.
@@ -1533,24 +1553,127 @@ __host__ __device__ constexpr int sweep_lds_doubles() {
 #ifndef SWEEP_WAVES_PER_SIMD
 #define SWEEP_WAVES_PER_SIMD 3
 #endif
-// disturbance column j of instance b by one wave (k_sweep: one wave per column; k_cl_loop_scp: one wave walks the columns of its instance)
+template <int NX>
+constexpr bool sweep_mfma = (SWEEP_MFMA != 0) && NX >= 13;
+
+// ---- the steps of the sweep, each stated once; k_sweep, k_sweep_ric1 + k_sweep_prop and the loop kernels are built from these ----
+// C (M x N) = op(A) B: the matrix core or the vector ALU, there with 1 x 2 outputs per lane for the NU-row products and 3 x 2 for the NX-row ones
+template <int NX, int NU, int M, int N, int K, bool TA = false>
+__device__ __forceinline__ void sweep_gemm(const double *A, int lda, const double *B, int ldb, double *C, int ldc, int lane) {
+    if constexpr (sweep_mfma<NX>) wla::gemm_mfma<M, N, K, TA, false>(A, lda, B, ldb, C, ldc, lane);
+    else wla::gemm_blk<M, N, K, TA, false, (M == NU ? 1 : 3), 2, false>(A, lda, B, ldb, C, ldc, 1.0, lane);
+}
+// Acl = A + B K on the vector ALU (Acl may be A: entry o reads A[o] only).  The pass loop is left to the compiler: unrolled by pragma it costs
+// k_sweep_gen<13,4> six VGPRs and a wave per SIMD.
 template <int NX, int NU>
-__device__ __forceinline__ void sweep_col_dev(const SweepArgs &a, int b, int j, int lane, double *sm) {
+__device__ __forceinline__ void acl_form(const double *sA, const double *sB, const double *sK, double *sAcl, int lane) {
+    for (int o = lane; o < NX * NX; o += 64) {
+        const int i = o / NX, jj = o % NX;
+        double s = sA[o];
+#pragma unroll
+        for (int u = 0; u < NU; u++) s = fma(sB[i * NU + u], sK[u * NX + jj], s);
+        sAcl[o] = s;
+    }
+}
+// ... where sweep_gemm would put it
+template <int NX, int NU>
+__device__ __forceinline__ void sweep_acl(const double *sA, const double *sB, const double *sK, double *sAcl, int lane) {
+    if constexpr (sweep_mfma<NX>) wla::gemm_mfma<NX, NX, NU, false, false, true>(sB, NU, sK, NX, sAcl, NX, lane, sA, NX);
+    else acl_form<NX, NU>(sA, sB, sK, sAcl, lane);
+}
+// K = -H^{-1} F, one column per lane
+template <int NX, int NU>
+__device__ __forceinline__ void k_solve(const double *sH, const double *sF, double *sK, int lane) {
+    if (lane < NX) {
+        double f[NU];
+#pragma unroll
+        for (int u = 0; u < NU; u++) f[u] = sF[u * NX + lane];
+        wla::spd_solve_small<NU>(sH, NU, f);
+#pragma unroll
+        for (int u = 0; u < NU; u++) sK[u * NX + lane] = -f[u];
+    }
+}
+// A stage block of LEN doubles in flight between global memory and LDS: next stage's blocks are fetched into registers while the current stage is processed
+template <int LEN>
+struct SweepBlock {
+    static constexpr int R = (LEN + 63) / 64;
+    double v[R];
+    __device__ __forceinline__ void load(const double *M, int lane) {
+#pragma unroll
+        for (int r = 0; r < R; r++) v[r] = M[min(r * 64 + lane, LEN - 1)];
+    }
+    __device__ __forceinline__ void store(double *lds, int lane) const {
+#pragma unroll
+        for (int r = 0; r < R; r++) { const int o = r * 64 + lane; if (o < LEN) lds[o] = v[r]; }
+    }
+};
+// weight of row min(lane, NZ - 1) of [Phi_x; Phi_u] in the tube cost, also the regulariser's share of that entry of the stage cost diagonal (batch constants)
+template <int NX, int NU>
+__device__ __forceinline__ double row_weight(const Costs &cst, int lane) {
+    const int lz = min(lane, NX + NU - 1);
+    return (lz < NX) ? cst.Qregd[lz] : cst.Rregd[lz - NX];
+}
+
+// One Riccati stage: on entry A_k, B_k, S_{k+1} and the cost diagonal are in LDS; on exit K_k (also written to Kg), A_k + B_k K_k in A_k's place (ACL_OUT:
+// also written to Ag) and S_k in S_{k+1}'s.
+template <int NX, int NU, bool ACL_OUT>
+__device__ __forceinline__ void ric_stage(double *sm, double *Kg, double *Ag, int lane) {
+    using W = SweepLds<NX, NU>;
+    double *sA = sm + W::oA, *sS = sm + W::oS, *sYm = sm + W::oYm, *sAcl = sm + W::oAcl, *sSn = sm + W::oSn;
+    double *sB = sm + W::oB, *sX = sm + W::oX, *sF = sm + W::oF, *sK = sm + W::oK, *sH = sm + W::oH, *sC = sm + W::oC;
+    sweep_gemm<NX, NU, NU, NX, NX, true>(sB, NU, sS, NX, sX, NX, lane);    // x = B' S   (NU x NX)
+    sweep_gemm<NX, NU, NX, NX, NX, true>(sA, NX, sS, NX, sYm, NX, lane);   // y = A' S   (NX x NX)
+    wla::wsync();
+    {   // H = x B (NU x NU), the sum over k split over three lane groups (lane = entry + NU^2 g)
+        constexpr int NH = NU * NU;
+        const int g3 = lane / NH, o = lane - g3 * NH, hi = o / NU, hj = o % NU;
+        double hs = 0.0;
+        if (g3 < 3) {
+#pragma unroll
+            for (int q = 0; q < (NX + 2) / 3; q++) { const int kk = 3 * q + g3; if (kk < NX) hs = fma(sX[hi * NX + kk], sB[kk * NU + hj], hs); }
+        }
+        hs = hs + __shfl(hs, lane + NH) + __shfl(hs, lane + 2 * NH);
+        if (lane < NH) sH[lane] = hs;
+    }
+    sweep_gemm<NX, NU, NU, NX, NX>(sX, NX, sA, NX, sF, NX, lane);          // F = x A
+    wla::wsync();
+    if (lane < NU) sH[lane * NU + lane] += sC[NX + lane];
+    wla::wsync();
+    k_solve<NX, NU>(sH, sF, sK, lane);
+    wla::wsync();
+#pragma unroll
+    for (int o = lane; o < NU * NX; o += 64) Kg[o] = sK[o];
+    sweep_acl<NX, NU>(sA, sB, sK, sAcl, lane);
+    wla::wsync();
+    if constexpr (ACL_OUT) {
+#pragma unroll
+        for (int o = lane; o < NX * NX; o += 64) Ag[o] = sAcl[o];
+    }
+    sweep_gemm<NX, NU, NX, NX, NX>(sYm, NX, sAcl, NX, sSn, NX, lane);      // y (A + B K)
+    wla::wsync();
+#pragma unroll
+    for (int o = lane; o < NX * NX; o += 64) {   // S = (Sn + Sn')/2 + diag, in place: the lane of (i,j), i >= j, writes both (i,j) and (j,i)
+        const int i = o / NX, jj = o % NX;
+        if (i >= jj) {
+            const double v = 0.5 * (sSn[o] + sSn[jj * NX + i]) + ((i == jj) ? sC[i] : 0.0);
+            sS[o] = v; sS[jj * NX + i] = v;
+        }
+    }
+    wla::wsync();
+}
+// The Riccati recursion of disturbance column j of instance b, stages N - 1 .. j, by one wave: K_k goes to Kd + k kstride, with ACL_OUT
+// A_k + B_k K_k to Ad + k NX^2.  Software pipeline: the next stage's eta pair, A_k and B_k are fetched into registers while the current stage is
+// processed.  The eta pair travels as loaded, ahead of the blocks, and is summed where the stage reads it: summed inside the fetch it would land
+// the blocks of the same fetch with it.
+template <int NX, int NU, bool ACL_OUT>
+__device__ __forceinline__ void ric_recursion(const SweepArgs &a, int b, int j, double *Kd, size_t kstride, double *Ad, int lane, double *sm) {
     using L = Lay<NX, NU>;
-    constexpr int NZ = L::NZ, NI = L::NI, NIF = L::NIF, NW = NX;
+    using W = SweepLds<NX, NU>;
+    constexpr int NZ = L::NZ, NI = L::NI, NIF = L::NIF;
     const int N = a.N;
-    double *p = sm;
-    double *sA = p; p += NX * NX; double *sS = p; p += NX * NX; double *sYm = p; p += NX * NX;
-    double *sAcl = sA;                     // A + B K replaces A_k in place (every use of A_k precedes it)
-    double *sSn = sS;                      // y (A + B K) lands where S_{k+1} was (dead once B'S and A'S are formed), symmetrised in place
-    double *sPhi = sS, *sPhi2 = sYm;       // the Riccati buffers are dead in the propagate phase
-    double *sB = p; p += NX * NU; double *sX = p; p += NX * NU; double *sF = p; p += NX * NU; double *sK = p; p += NX * NU;
-    double *sPu = p; p += NU * NW; double *sH = p; p += NU * NU; double *sC = p; p += NZ;
+    double *sA = sm + W::oA, *sS = sm + W::oS, *sB = sm + W::oB, *sC = sm + W::oC;
     const double *gA = a.A + (size_t)b * N * NX * NX, *gB = a.Bm + (size_t)b * N * NX * NU;
     const double *eta = a.eta + (size_t)b * N * N * NI, *eta_f = a.eta_f + (size_t)b * (N + 1) * NIF;
-    double *gK = a.K + (size_t)b * N * (N + 1) * NU * NX;
-    double *beta = a.beta + (size_t)b * N * N * NI, *beta_f = a.beta_f + (size_t)b * (N + 1) * NIF;
-
     // terminal: S[N,j] = Gf' diag(eta_f[j]) Gf + Q_reg_f   (Gf = [I;-I], Q_reg_f diagonal)
 #pragma unroll
     for (int o = lane; o < NX * NX; o += 64) {
@@ -1558,102 +1681,93 @@ __device__ __forceinline__ void sweep_col_dev(const SweepArgs &a, int b, int j, 
         sS[o] = (i == jj) ? eta_f[j * NIF + i] + eta_f[j * NIF + NX + i] + a.cst.Qregfd[i] : 0.0;
     }
     wla::wsync();
-    // software pipeline: next stage's A_k, B_k, eta are fetched into registers while the current stage is processed
-    constexpr int RA = (NX * NX + 63) / 64, RB = (NX * NU + 63) / 64;
-    double rA[RA], rB[RB], rC = 0.0;
+    SweepBlock<NX * NX> rA;
+    SweepBlock<NX * NU> rB;
+    double rCu = 0.0, rCl = 0.0;
     const int lz = min(lane, NZ - 1);
-    const double regd = (lz < NX) ? a.cst.Qregd[lz] : a.cst.Rregd[lz - NX];
+    const double regd = row_weight<NX, NU>(a.cst, lane);
     auto fetch = [&](int k) {
-        const double *Ak = gA + (size_t)k * NX * NX, *Bk = gB + (size_t)k * NX * NU;
-#pragma unroll
-        for (int r = 0; r < RA; r++) rA[r] = Ak[min(r * 64 + lane, NX * NX - 1)];
-#pragma unroll
-        for (int r = 0; r < RB; r++) rB[r] = Bk[min(r * 64 + lane, NX * NU - 1)];
         const double *e = eta + ((size_t)k * N + j) * NI;
-        rC = e[lz] + e[NZ + lz] + regd;
+        rCu = e[lz]; rCl = e[NZ + lz];
+        rA.load(gA + (size_t)k * NX * NX, lane);
+        rB.load(gB + (size_t)k * NX * NU, lane);
     };
     if (N - 1 >= j) fetch(N - 1);
     for (int k = N - 1; k >= j; k--) {
-#pragma unroll
-        for (int r = 0; r < RA; r++) { const int o = r * 64 + lane; if (o < NX * NX) sA[o] = rA[r]; }
-#pragma unroll
-        for (int r = 0; r < RB; r++) { const int o = r * 64 + lane; if (o < NX * NU) sB[o] = rB[r]; }
-        if (lane < NZ) sC[lane] = rC;
+        rA.store(sA, lane);
+        rB.store(sB, lane);
+        if (lane < NZ) sC[lane] = rCu + rCl + regd;
         wla::wsync();
         if (k - 1 >= j) fetch(k - 1);
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NU, NX, NX, true, false>(sB, NU, sS, NX, sX, NX, lane);
-        else
-#endif
-        wla::gemm_blk<NU, NX, NX, true, false, 1, 2, false>(sB, NU, sS, NX, sX, NX, 1.0, lane);   // x = B' S   (NU x NX)
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NX, NX, NX, true, false>(sA, NX, sS, NX, sYm, NX, lane);   // y = A' S on the fp64 matrix core
-        else
-#endif
-        wla::gemm_blk<NX, NX, NX, true, false, 3, 2, false>(sA, NX, sS, NX, sYm, NX, 1.0, lane);  // y = A' S   (NX x NX)
-        wla::wsync();
-        {   // H = x B (NU x NU), the sum over k split over three lane groups (lane = entry + NU^2 g)
-            constexpr int NH = NU * NU;
-            const int g3 = lane / NH, o = lane - g3 * NH, hi = o / NU, hj = o % NU;
-            double hs = 0.0;
-            if (g3 < 3) {
-#pragma unroll
-                for (int q = 0; q < (NX + 2) / 3; q++) { const int kk = 3 * q + g3; if (kk < NX) hs = fma(sX[hi * NX + kk], sB[kk * NU + hj], hs); }
-            }
-            hs = hs + __shfl(hs, lane + NH) + __shfl(hs, lane + 2 * NH);
-            if (lane < NH) sH[lane] = hs;
-        }
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NU, NX, NX, false, false>(sX, NX, sA, NX, sF, NX, lane);
-        else
-#endif
-        wla::gemm_blk<NU, NX, NX, false, false, 1, 2, false>(sX, NX, sA, NX, sF, NX, 1.0, lane);  // F = x A
-        wla::wsync();
-        if (lane < NU) sH[lane * NU + lane] += sC[NX + lane];
-        wla::wsync();
-        // K = -H^{-1} F, one column per lane
-        if (lane < NX) {
-            double f[NU];
-#pragma unroll
-            for (int u = 0; u < NU; u++) f[u] = sF[u * NX + lane];
-            wla::spd_solve_small<NU>(sH, NU, f);
-#pragma unroll
-            for (int u = 0; u < NU; u++) sK[u * NX + lane] = -f[u];
-        }
-        wla::wsync();
-        double *Kg = gK + ((size_t)k * (N + 1) + j) * NU * NX;
-#pragma unroll
-        for (int o = lane; o < NU * NX; o += 64) Kg[o] = sK[o];
-        // Acl = A + B K
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NX, NX, NU, false, false, true>(sB, NU, sK, NX, sAcl, NX, lane, sA, NX);
-        else
-#endif
-#pragma unroll
-        for (int o = lane; o < NX * NX; o += 64) {
-            const int i = o / NX, jj = o % NX;
-            double s = sA[o];
-#pragma unroll
-            for (int u = 0; u < NU; u++) s = fma(sB[i * NU + u], sK[u * NX + jj], s);
-            sAcl[o] = s;
-        }
-        wla::wsync();
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NX, NX, NX, false, false>(sYm, NX, sAcl, NX, sSn, NX, lane);
-        else
-#endif
-        wla::gemm_blk<NX, NX, NX, false, false, 3, 2, false>(sYm, NX, sAcl, NX, sSn, NX, 1.0, lane);  // y (A + B K)
-        wla::wsync();
-#pragma unroll
-        for (int o = lane; o < NX * NX; o += 64) {   // S = (Sn + Sn')/2 + diag, in place: the lane of (i,j), i >= j, writes both (i,j) and (j,i)
-            const int i = o / NX, jj = o % NX;
-            if (i >= jj) {
-                const double v = 0.5 * (sSn[o] + sSn[jj * NX + i]) + ((i == jj) ? sC[i] : 0.0);
-                sS[o] = v; sS[jj * NX + i] = v;
-            }
-        }
-        wla::wsync();
+        ric_stage<NX, NU, ACL_OUT>(sm, Kd + k * kstride, ACL_OUT ? Ad + (size_t)k * NX * NX : nullptr, lane);
     }
+}
+// Row norms of [Phi_x; Phi_u] of one column at one stage -> beta (bo: its NI entries; rows i and NZ + i of G = [I;-I] coincide) and the column's
+// share of cost_tube^2.  The sum over w is split over three lane groups (lane = row + NZ g); wreg = row_weight.
+template <int NX, int NU>
+__device__ __forceinline__ void tube_norms(const double *Pc, const double *sPu, double wreg, double eps, double *bo, double &ctube, int lane) {
+    constexpr int NZ = NX + NU, NW = NX;
+    const int g3 = lane / NZ, rw = lane - g3 * NZ;
+    const double *row = (rw < NX) ? Pc + rw * NW : sPu + (rw - NX) * NW;
+    double s = 0.0;
+    if (g3 < 3) {
+#pragma unroll
+        for (int q = 0; q < (NW + 2) / 3; q++) { const int w = 3 * q + g3; if (w < NW) s = fma(row[w], row[w], s); }
+    }
+    s = s + __shfl(s, lane + NZ) + __shfl(s, lane + 2 * NZ);
+    if (lane < NZ) {
+        ctube = fma(wreg * wreg, s, ctube);       // weighted row norms: this column's share of cost_tube^2
+        s = fmax(s, eps);
+        bo[lane] = s; bo[NZ + lane] = s;
+    }
+}
+// || row ||^2 by one lane
+template <int NW>
+__device__ __forceinline__ double row_norm2(const double *row) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; w++) s = fma(row[w], row[w], s);
+    return s;
+}
+// The terminal stage of column j: beta_f from the rows of Phi_N, their share of the tube cost, and the column's cost_tube^2 part written out
+template <int NX, int NU>
+__device__ __forceinline__ void tube_terminal(const SweepArgs &a, int b, int j, const double *Pc, double ctube, int lane) {
+    constexpr int NIF = 2 * NX, NW = NX;
+    if (lane < NX) {
+        double s = row_norm2<NW>(Pc + lane * NW);
+        ctube = fma(a.cst.Qregfd[lane] * a.cst.Qregfd[lane], s, ctube);
+        s = fmax(s, a.eps);
+        double *bf = a.beta_f + ((size_t)b * (a.N + 1) + j) * NIF;
+        bf[lane] = s; bf[NX + lane] = s;
+    }
+    ctube = wla::wave_sum(ctube);
+    if (lane == 0 && a.ct_part) a.ct_part[(size_t)b * (a.N + 1) + j] = ctube;
+}
+// XCD-aware block -> (instance b, item j of its `per` items): blocks i and i+8 share an XCD; all items of an instance stay on one XCD, so that its
+// stage blocks stay in that XCD's L2 (speed only; any mapping is correct)
+__device__ __forceinline__ void xcd_block_map(int bid, int B, int per, int *b, int *j) {
+    const int Bfull = (B / 8) * 8;
+    if (bid < Bfull * per) {
+        const int xcd = bid % 8, slot = bid / 8;
+        *b = (slot / per) * 8 + xcd; *j = slot % per;
+    } else {
+        const int r = bid - Bfull * per;
+        *b = Bfull + r / per; *j = r % per;
+    }
+}
+
+// disturbance column j of instance b by one wave (k_sweep: one wave per column; k_cl_loop_scp: one wave walks the columns of its instance)
+template <int NX, int NU>
+__device__ __forceinline__ void sweep_col_dev(const SweepArgs &a, int b, int j, int lane, double *sm) {
+    using W = SweepLds<NX, NU>;
+    constexpr int NI = Lay<NX, NU>::NI, NW = NX;
+    const int N = a.N;
+    double *sA = sm + W::oA, *sAcl = sm + W::oAcl, *sPhi = sm + W::oPhi, *sPhi2 = sm + W::oPhi2, *sB = sm + W::oB, *sK = sm + W::oK, *sPu = sm + W::oPu;
+    const double *gA = a.A + (size_t)b * N * NX * NX, *gB = a.Bm + (size_t)b * N * NX * NU;
+    double *gK = a.K + ((size_t)b * N * (N + 1) + j) * NU * NX;      // K[k,j] at gK + k kstride
+    const size_t kstride = (size_t)(N + 1) * NU * NX;
+    double *beta = a.beta + (size_t)b * N * N * NI;
+    ric_recursion<NX, NU, false>(a, b, j, gK, kstride, nullptr, lane, sm);
     wla::wsync_mem();   // K written above is re-read below by other lanes of this wave
     // propagate column j and accumulate row norms
     const double *Eg = a.E + (a.E_per_instance ? (size_t)b * (N + 1) * NX * NW : 0) + (size_t)j * NX * NW;
@@ -1661,102 +1775,40 @@ __device__ __forceinline__ void sweep_col_dev(const SweepArgs &a, int b, int j, 
     for (int o = lane; o < NX * NW; o += 64) sPhi[o] = Eg[o];
     wla::wsync();
     double *Pc = sPhi, *Pn = sPhi2;
-    double rK[RB];
+    SweepBlock<NX * NX> rA;
+    SweepBlock<NX * NU> rB, rK;
     double ctube = 0.0;
     auto fetch2 = [&](int k) {
-        const double *Ak = gA + (size_t)k * NX * NX, *Bk = gB + (size_t)k * NX * NU;
-        const double *Kg = gK + ((size_t)k * (N + 1) + j) * NU * NX;
-#pragma unroll
-        for (int r = 0; r < RA; r++) rA[r] = Ak[min(r * 64 + lane, NX * NX - 1)];
-#pragma unroll
-        for (int r = 0; r < RB; r++) { const int o = min(r * 64 + lane, NX * NU - 1); rB[r] = Bk[o]; rK[r] = Kg[o]; }
+        rA.load(gA + (size_t)k * NX * NX, lane);
+        rB.load(gB + (size_t)k * NX * NU, lane);
+        rK.load(gK + k * kstride, lane);
     };
+    const double wreg = row_weight<NX, NU>(a.cst, lane);      // read once, ahead of the stage loop
     if (j < N) fetch2(j);
     for (int k = j; k < N; k++) {
-#pragma unroll
-        for (int r = 0; r < RA; r++) { const int o = r * 64 + lane; if (o < NX * NX) sA[o] = rA[r]; }
-#pragma unroll
-        for (int r = 0; r < RB; r++) { const int o = r * 64 + lane; if (o < NX * NU) { sB[o] = rB[r]; sK[o] = rK[r]; } }
+        rA.store(sA, lane);
+        rB.store(sB, lane);
+        rK.store(sK, lane);
         wla::wsync();
         if (k + 1 < N) fetch2(k + 1);
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NU, NW, NX, false, false>(sK, NX, Pc, NW, sPu, NW, lane);
-        else
-#endif
-        wla::gemm_blk<NU, NW, NX, false, false, 1, 2, false>(sK, NX, Pc, NW, sPu, NW, 1.0, lane);  // Phi_u = K Phi_x
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NX, NX, NU, false, false, true>(sB, NU, sK, NX, sAcl, NX, lane, sA, NX);
-        else
-#endif
-#pragma unroll
-        for (int o = lane; o < NX * NX; o += 64) {
-            const int i = o / NX, jj = o % NX;
-            double s = sA[o];
-#pragma unroll
-            for (int u = 0; u < NU; u++) s = fma(sB[i * NU + u], sK[u * NX + jj], s);
-            sAcl[o] = s;
-        }
+        sweep_gemm<NX, NU, NU, NW, NX>(sK, NX, Pc, NW, sPu, NW, lane);       // Phi_u = K Phi_x
+        sweep_acl<NX, NU>(sA, sB, sK, sAcl, lane);
         wla::wsync();
-        // beta[k,j,i] = max(|| row i of [Phi_x;Phi_u] ||^2, eps), rows i and NZ+i of G=[I;-I] coincide
-        {   // row norms, the sum over w split over three lane groups (lane = row + NZ g)
-            const int g3 = lane / NZ, rw = lane - g3 * NZ;
-            const double *row = (rw < NX) ? Pc + rw * NW : sPu + (rw - NX) * NW;
-            double s = 0.0;
-            if (g3 < 3) {
-#pragma unroll
-                for (int q = 0; q < (NW + 2) / 3; q++) { const int w = 3 * q + g3; if (w < NW) s = fma(row[w], row[w], s); }
-            }
-            s = s + __shfl(s, lane + NZ) + __shfl(s, lane + 2 * NZ);
-            if (lane < NZ) {
-                const double wr = (lane < NX) ? a.cst.Qregd[lane] : a.cst.Rregd[lane - NX];
-                ctube = fma(wr * wr, s, ctube);       // weighted row norms: this column's share of cost_tube^2
-                s = fmax(s, a.eps);
-                double *bo = beta + ((size_t)k * N + j) * NI;
-                bo[lane] = s; bo[NZ + lane] = s;
-            }
-        }
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NX, NW, NX, false, false>(sAcl, NX, Pc, NW, Pn, NW, lane);        // Phi_{k+1} = Acl Phi_k
-        else
-#endif
-        wla::gemm_blk<NX, NW, NX, false, false, 3, 2, false>(sAcl, NX, Pc, NW, Pn, NW, 1.0, lane);
+        tube_norms<NX, NU>(Pc, sPu, wreg, a.eps, beta + ((size_t)k * N + j) * NI, ctube, lane);      // beta[k,j,i] = max(|| row i of [Phi_x;Phi_u] ||^2, eps)
+        sweep_gemm<NX, NU, NX, NW, NX>(sAcl, NX, Pc, NW, Pn, NW, lane);      // Phi_{k+1} = Acl Phi_k
         wla::wsync();
         double *t = Pc; Pc = Pn; Pn = t;
     }
-    if (lane < NX) {
-        const double *row = Pc + lane * NW;
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; w++) s = fma(row[w], row[w], s);
-        ctube = fma(a.cst.Qregfd[lane] * a.cst.Qregfd[lane], s, ctube);
-        s = fmax(s, a.eps);
-        beta_f[j * NIF + lane] = s; beta_f[j * NIF + NX + lane] = s;
-    }
-    ctube = wla::wave_sum(ctube);
-    if (lane == 0 && a.ct_part) a.ct_part[(size_t)b * (N + 1) + j] = ctube;
+    tube_terminal<NX, NU>(a, b, j, Pc, ctube, lane);
 }
 template <int NX, int NU>
 __global__ __launch_bounds__(64, SWEEP_WAVES_PER_SIMD) void k_sweep(SweepArgs a) {
-    const int N = a.N, lane = threadIdx.x;
-    // XCD-aware mapping: blocks i and i+8 share an XCD; keep all columns of an instance on one XCD so its
-    // A_k/B_k stay in that XCD's L2 (speed only; any mapping is correct).
-    const int ncol = N + 1;
     int b, j;
-    {
-        const int bid = blockIdx.x;
-        const int Bfull = (a.B / 8) * 8;
-        if (bid < Bfull * ncol) {
-            const int xcd = bid % 8, slot = bid / 8;
-            b = (slot / ncol) * 8 + xcd; j = slot % ncol;
-        } else {
-            const int r = bid - Bfull * ncol;
-            b = Bfull + r / ncol; j = r % ncol;
-        }
-    }
+    xcd_block_map(blockIdx.x, a.B, a.N + 1, &b, &j);
     if (b >= a.B) return;
     if (a.run && !a.run[b]) return;
     extern __shared__ double sm[];
-    sweep_col_dev<NX, NU>(a, b, j, lane, sm);
+    sweep_col_dev<NX, NU>(a, b, j, threadIdx.x, sm);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1768,8 +1820,6 @@ __global__ __launch_bounds__(64, SWEEP_WAVES_PER_SIMD) void k_sweep(SweepArgs a)
 // ------------------------------------------------------------------------------------------------
 struct SweepGenArgs { SweepArgs s; const double *G, *Gf; int NI, NIF; };
 template <int NX, int NU>
-__host__ __device__ constexpr int sweep_gen_lds_doubles() { return 4 * NX * NX + 5 * NX * NU + 2 * NU * NU + 8; }
-template <int NX, int NU>
 __global__ __launch_bounds__(64) void k_sweep_gen(SweepGenArgs ga) {
     const SweepArgs &a = ga.s;
     constexpr int NZ = NX + NU, NW = NX;
@@ -1777,11 +1827,11 @@ __global__ __launch_bounds__(64) void k_sweep_gen(SweepGenArgs ga) {
     const int ncol = N + 1, b = blockIdx.x / ncol, j = blockIdx.x % ncol;
     if (b >= a.B || (a.run && !a.run[b])) return;
     extern __shared__ double sm[];
-    double *p = sm;
-    double *sA = p; p += NX * NX; double *sS = p; p += NX * NX; double *sYm = p; p += NX * NX; double *sCx = p; p += NX * NX;
-    double *sAcl = sA, *sSn = sS, *sPhi = sS, *sPhi2 = sYm;
-    double *sB = p; p += NX * NU; double *sX = p; p += NX * NU; double *sF = p; p += NX * NU; double *sK = p; p += NX * NU;
-    double *sPu = p; p += NU * NW; double *sH = p; p += NU * NU; double *sCu = p; p += NU * NU;
+    using W = SweepLds<NX, NU, true>;
+    double *sA = sm + W::oA, *sS = sm + W::oS, *sYm = sm + W::oYm, *sCx = sm + W::oCx, *sAcl = sm + W::oAcl, *sSn = sm + W::oSn, *sPhi = sm + W::oPhi, *sPhi2 = sm + W::oPhi2;
+    double *sB = sm + W::oB, *sX = sm + W::oX, *sF = sm + W::oF, *sK = sm + W::oK, *sPu = sm + W::oPu, *sH = sm + W::oH, *sCu = sm + W::oC;
+    SweepBlock<NX * NX> rA;
+    SweepBlock<NX * NU> rB;
     const double *gA = a.A + (size_t)b * N * NX * NX, *gB = a.Bm + (size_t)b * N * NX * NU;
     const double *eta = a.eta + (size_t)b * N * N * NI, *eta_f = a.eta_f + (size_t)b * (N + 1) * NIF;
     double *gK = a.K + (size_t)b * N * (N + 1) * NU * NX;
@@ -1796,15 +1846,15 @@ __global__ __launch_bounds__(64) void k_sweep_gen(SweepGenArgs ga) {
     }
     wla::wsync();
     for (int k = N - 1; k >= j; k--) {
-        const double *Ak = gA + (size_t)k * NX * NX, *Bk = gB + (size_t)k * NX * NU, *e = eta + ((size_t)k * N + j) * NI;
+        const double *e = eta + ((size_t)k * N + j) * NI;
+        rA.load(gA + (size_t)k * NX * NX, lane); rA.store(sA, lane);
+        rB.load(gB + (size_t)k * NX * NU, lane); rB.store(sB, lane);
         for (int o = lane; o < NX * NX; o += 64) {
             const int i = o / NX, jj = o % NX;
-            sA[o] = Ak[o];
             double s = (i == jj) ? a.cst.Qregd[i] : 0.0;                                   // C_xx + Q_reg
             for (int r = 0; r < NI; r++) s = fma(G[r * NZ + i] * e[r], G[r * NZ + jj], s);
             sCx[o] = s;
         }
-        for (int o = lane; o < NX * NU; o += 64) sB[o] = Bk[o];
         for (int o = lane; o < NU * NU; o += 64) {
             const int i = o / NU, jj = o % NU;
             double s = (i == jj) ? a.cst.Rregd[i] : 0.0;                                   // C_uu + R_reg
@@ -1823,24 +1873,11 @@ __global__ __launch_bounds__(64) void k_sweep_gen(SweepGenArgs ga) {
         }
         wla::gemm_blk<NU, NX, NX, false, false, 1, 2, false>(sX, NX, sA, NX, sF, NX, 1.0, lane);  // F = x A
         wla::wsync();
-        if (lane < NX) {   // K = -H^{-1} F, one column per lane (H symmetric positive definite: C_uu is a Gram matrix, R_reg > 0, x B = B' S B)
-            double f[NU];
-#pragma unroll
-            for (int u = 0; u < NU; u++) f[u] = sF[u * NX + lane];
-            wla::spd_solve_small<NU>(sH, NU, f);
-#pragma unroll
-            for (int u = 0; u < NU; u++) sK[u * NX + lane] = -f[u];
-        }
+        k_solve<NX, NU>(sH, sF, sK, lane);      // (H symmetric positive definite: C_uu is a Gram matrix, R_reg > 0, x B = B' S B)
         wla::wsync();
         double *Kg = gK + ((size_t)k * (N + 1) + j) * NU * NX;
         for (int o = lane; o < NU * NX; o += 64) Kg[o] = sK[o];
-        for (int o = lane; o < NX * NX; o += 64) {                                                // Acl = A + B K
-            const int i = o / NX, jj = o % NX;
-            double s = sA[o];
-#pragma unroll
-            for (int u = 0; u < NU; u++) s = fma(sB[i * NU + u], sK[u * NX + jj], s);
-            sAcl[o] = s;
-        }
+        acl_form<NX, NU>(sA, sB, sK, sAcl, lane);
         wla::wsync();
         wla::gemm_blk<NX, NX, NX, false, false, 3, 2, false>(sYm, NX, sAcl, NX, sSn, NX, 1.0, lane);  // y (A + B K)
         wla::wsync();
@@ -1861,18 +1898,12 @@ __global__ __launch_bounds__(64) void k_sweep_gen(SweepGenArgs ga) {
     double *Pc = sPhi, *Pn = sPhi2;
     double ctube = 0.0;
     for (int k = j; k < N; k++) {
-        const double *Ak = gA + (size_t)k * NX * NX, *Bk = gB + (size_t)k * NX * NU, *Kg = gK + ((size_t)k * (N + 1) + j) * NU * NX;
-        for (int o = lane; o < NX * NX; o += 64) sA[o] = Ak[o];
-        for (int o = lane; o < NX * NU; o += 64) { sB[o] = Bk[o]; sK[o] = Kg[o]; }
+        rA.load(gA + (size_t)k * NX * NX, lane); rA.store(sA, lane);
+        rB.load(gB + (size_t)k * NX * NU, lane); rB.store(sB, lane);
+        rB.load(gK + ((size_t)k * (N + 1) + j) * NU * NX, lane); rB.store(sK, lane);
         wla::wsync();
         wla::gemm_blk<NU, NW, NX, false, false, 1, 2, false>(sK, NX, Pc, NW, sPu, NW, 1.0, lane);  // Phi_u = K Phi_x
-        for (int o = lane; o < NX * NX; o += 64) {
-            const int i = o / NX, jj = o % NX;
-            double s = sA[o];
-#pragma unroll
-            for (int u = 0; u < NU; u++) s = fma(sB[i * NU + u], sK[u * NX + jj], s);
-            sAcl[o] = s;
-        }
+        acl_form<NX, NU>(sA, sB, sK, sAcl, lane);
         wla::wsync();
         for (int r = lane; r < NI; r += 64) {
             double s = 0.0;
@@ -1885,11 +1916,8 @@ __global__ __launch_bounds__(64) void k_sweep_gen(SweepGenArgs ga) {
             beta[((size_t)k * N + j) * NI + r] = fmax(s, a.eps);
         }
         if (lane < NZ) {   // this column's share of cost_tube^2 (weighted row norms of [Phi_x; Phi_u])
-            const double *row = (lane < NX) ? Pc + lane * NW : sPu + (lane - NX) * NW;
-            double s = 0.0;
-            for (int w = 0; w < NW; w++) s = fma(row[w], row[w], s);
-            const double wr = (lane < NX) ? a.cst.Qregd[lane] : a.cst.Rregd[lane - NX];
-            ctube = fma(wr * wr, s, ctube);
+            const double wr = row_weight<NX, NU>(a.cst, lane);
+            ctube = fma(wr * wr, row_norm2<NW>((lane < NX) ? Pc + lane * NW : sPu + (lane - NX) * NW), ctube);
         }
         wla::gemm_blk<NX, NW, NX, false, false, 3, 2, false>(sAcl, NX, Pc, NW, Pn, NW, 1.0, lane);    // Phi_{k+1} = Acl Phi_k
         wla::wsync();
@@ -1904,12 +1932,7 @@ __global__ __launch_bounds__(64) void k_sweep_gen(SweepGenArgs ga) {
         }
         beta_f[j * NIF + r] = fmax(s, a.eps);
     }
-    if (lane < NX) {
-        const double *row = Pc + lane * NW;
-        double s = 0.0;
-        for (int w = 0; w < NW; w++) s = fma(row[w], row[w], s);
-        ctube = fma(a.cst.Qregfd[lane] * a.cst.Qregfd[lane], s, ctube);
-    }
+    if (lane < NX) ctube = fma(a.cst.Qregfd[lane] * a.cst.Qregfd[lane], row_norm2<NW>(Pc + lane * NW), ctube);
     ctube = wla::wave_sum(ctube);
     if (lane == 0 && a.ct_part) a.ct_part[(size_t)b * (N + 1) + j] = ctube;
 }
@@ -1919,8 +1942,9 @@ __global__ __launch_bounds__(64) void k_sweep_gen(SweepGenArgs ga) {
 // evaluate_dual_eta (:475-487) gives eta[k,j] = mu_k / (2 sqrt(eps)) for every column j <= k and eta_f[j] = mu_f / (2 sqrt(eps)) for every j: the
 // cost blocks of the N+1 Riccati recursions of _backward_solve_numba (:65-84) are the same, hence S[k,j] = S[k], K[k,j] = K[k] and
 // A_k + B_k K_k for all j <= k.  One wave per instance runs that recursion once (k_sweep_ric1: 20 stages instead of 210) and leaves K_k and
-// A_k + B_k K_k in a compact scratch; one wave per (instance, column) then only propagates Phi and takes the row norms (k_sweep_prop).  Same
-// arithmetic in the same order as k_sweep, which remains for the later iterations of a solve (beta, hence eta, then differ from column to column).
+// A_k + B_k K_k in a compact scratch; one wave per (instance, column) then only propagates Phi and takes the row norms (k_sweep_prop).  The
+// recursion, the row norms and the terminal column are the functions k_sweep calls (ric_recursion, tube_norms, tube_terminal): the same arithmetic in
+// the same order as k_sweep, which remains for the later iterations of a solve (beta, hence eta, then differ from column to column).
 // In the rocket script's setting (one fast-SLS step per MPC step) every sweep is a first one.
 // ------------------------------------------------------------------------------------------------
 struct SweepSharedArgs {
@@ -1930,123 +1954,9 @@ struct SweepSharedArgs {
 };
 template <int NX, int NU>
 __device__ __forceinline__ void sweep_ric1_dev(const SweepSharedArgs &aa, int b, int lane, double *sm) {
-    const SweepArgs &a = aa.s;
-    using L = Lay<NX, NU>;
-    constexpr int NZ = L::NZ, NI = L::NI, NIF = L::NIF;
-    const int N = a.N, j = 0;
-    double *p = sm;
-    double *sA = p; p += NX * NX; double *sS = p; p += NX * NX; double *sYm = p; p += NX * NX;
-    double *sAcl = sA, *sSn = sS;
-    double *sB = p; p += NX * NU; double *sX = p; p += NX * NU; double *sF = p; p += NX * NU; double *sK = p; p += NX * NU;
-    p += NU * NX; double *sH = p; p += NU * NU; double *sC = p; p += NZ;
-    const double *gA = a.A + (size_t)b * N * NX * NX, *gB = a.Bm + (size_t)b * N * NX * NU;
-    const double *eta = a.eta + (size_t)b * N * N * NI, *eta_f = a.eta_f + (size_t)b * (N + 1) * NIF;
-    double *gKc = aa.Kc + (size_t)b * N * NU * NX, *gAc = aa.Aclc + (size_t)b * N * NX * NX;
-#pragma unroll
-    for (int o = lane; o < NX * NX; o += 64) {
-        const int i = o / NX, jj = o % NX;
-        sS[o] = (i == jj) ? eta_f[j * NIF + i] + eta_f[j * NIF + NX + i] + a.cst.Qregfd[i] : 0.0;
-    }
-    wla::wsync();
-    constexpr int RA = (NX * NX + 63) / 64, RB = (NX * NU + 63) / 64;
-    // the eta pair travels as loaded, ahead of the blocks, and is summed where the stage reads it: summed inside the fetch it would land the
-    // blocks of the same fetch with it
-    double rA[RA], rB[RB], rCu = 0.0, rCl = 0.0;
-    const int lz = min(lane, NZ - 1);
-    const double regd = (lz < NX) ? a.cst.Qregd[lz] : a.cst.Rregd[lz - NX];
-    auto fetch = [&](int k) {
-        const double *Ak = gA + (size_t)k * NX * NX, *Bk = gB + (size_t)k * NX * NU;
-        const double *e = eta + ((size_t)k * N + j) * NI;
-        rCu = e[lz]; rCl = e[NZ + lz];
-#pragma unroll
-        for (int r = 0; r < RA; r++) rA[r] = Ak[min(r * 64 + lane, NX * NX - 1)];
-#pragma unroll
-        for (int r = 0; r < RB; r++) rB[r] = Bk[min(r * 64 + lane, NX * NU - 1)];
-    };
+    const int N = aa.s.N;
     if (lane == 0 && aa.stale) aa.stale[b] = (aa.stale[b] & ~2) | 32;
-    fetch(N - 1);
-    for (int k = N - 1; k >= 0; k--) {
-#pragma unroll
-        for (int r = 0; r < RA; r++) { const int o = r * 64 + lane; if (o < NX * NX) sA[o] = rA[r]; }
-#pragma unroll
-        for (int r = 0; r < RB; r++) { const int o = r * 64 + lane; if (o < NX * NU) sB[o] = rB[r]; }
-        if (lane < NZ) sC[lane] = rCu + rCl + regd;
-        wla::wsync();
-        if (k - 1 >= 0) fetch(k - 1);
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NU, NX, NX, true, false>(sB, NU, sS, NX, sX, NX, lane);
-        else
-#endif
-        wla::gemm_blk<NU, NX, NX, true, false, 1, 2, false>(sB, NU, sS, NX, sX, NX, 1.0, lane);   // x = B' S   (NU x NX)
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NX, NX, NX, true, false>(sA, NX, sS, NX, sYm, NX, lane);
-        else
-#endif
-        wla::gemm_blk<NX, NX, NX, true, false, 3, 2, false>(sA, NX, sS, NX, sYm, NX, 1.0, lane);  // y = A' S   (NX x NX)
-        wla::wsync();
-        {
-            constexpr int NH = NU * NU;
-            const int g3 = lane / NH, o = lane - g3 * NH, hi = o / NU, hj = o % NU;
-            double hs = 0.0;
-            if (g3 < 3) {
-#pragma unroll
-                for (int q = 0; q < (NX + 2) / 3; q++) { const int kk = 3 * q + g3; if (kk < NX) hs = fma(sX[hi * NX + kk], sB[kk * NU + hj], hs); }
-            }
-            hs = hs + __shfl(hs, lane + NH) + __shfl(hs, lane + 2 * NH);
-            if (lane < NH) sH[lane] = hs;
-        }
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NU, NX, NX, false, false>(sX, NX, sA, NX, sF, NX, lane);
-        else
-#endif
-        wla::gemm_blk<NU, NX, NX, false, false, 1, 2, false>(sX, NX, sA, NX, sF, NX, 1.0, lane);  // F = x A
-        wla::wsync();
-        if (lane < NU) sH[lane * NU + lane] += sC[NX + lane];
-        wla::wsync();
-        if (lane < NX) {
-            double f[NU];
-#pragma unroll
-            for (int u = 0; u < NU; u++) f[u] = sF[u * NX + lane];
-            wla::spd_solve_small<NU>(sH, NU, f);
-#pragma unroll
-            for (int u = 0; u < NU; u++) sK[u * NX + lane] = -f[u];
-        }
-        wla::wsync();
-        double *Kg = gKc + (size_t)k * NU * NX;
-#pragma unroll
-        for (int o = lane; o < NU * NX; o += 64) Kg[o] = sK[o];
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NX, NX, NU, false, false, true>(sB, NU, sK, NX, sAcl, NX, lane, sA, NX);
-        else
-#endif
-#pragma unroll
-        for (int o = lane; o < NX * NX; o += 64) {
-            const int i = o / NX, jj = o % NX;
-            double s = sA[o];
-#pragma unroll
-            for (int u = 0; u < NU; u++) s = fma(sB[i * NU + u], sK[u * NX + jj], s);
-            sAcl[o] = s;
-        }
-        wla::wsync();
-        double *Ag = gAc + (size_t)k * NX * NX;
-#pragma unroll
-        for (int o = lane; o < NX * NX; o += 64) Ag[o] = sAcl[o];
-#if SWEEP_MFMA
-        if constexpr (NX >= 13) wla::gemm_mfma<NX, NX, NX, false, false>(sYm, NX, sAcl, NX, sSn, NX, lane);
-        else
-#endif
-        wla::gemm_blk<NX, NX, NX, false, false, 3, 2, false>(sYm, NX, sAcl, NX, sSn, NX, 1.0, lane);  // y (A + B K)
-        wla::wsync();
-#pragma unroll
-        for (int o = lane; o < NX * NX; o += 64) {
-            const int i = o / NX, jj = o % NX;
-            if (i >= jj) {
-                const double v = 0.5 * (sSn[o] + sSn[jj * NX + i]) + ((i == jj) ? sC[i] : 0.0);
-                sS[o] = v; sS[jj * NX + i] = v;
-            }
-        }
-        wla::wsync();
-    }
+    ric_recursion<NX, NU, true>(aa.s, b, 0, aa.Kc + (size_t)b * N * NU * NX, NU * NX, aa.Aclc + (size_t)b * N * NX * NX, lane, sm);
 }
 template <int NX, int NU>
 __global__ __launch_bounds__(64, SWEEP_WAVES_PER_SIMD) void k_sweep_ric1(SweepSharedArgs aa) {
@@ -2057,9 +1967,6 @@ __global__ __launch_bounds__(64, SWEEP_WAVES_PER_SIMD) void k_sweep_ric1(SweepSh
     sweep_ric1_dev<NX, NU>(aa, b, threadIdx.x, sm);
 }
 
-template <int NX, int NU>
-__host__ __device__ constexpr int sweep_prop_lds_doubles() { return 5 * NX * NX + 3 * NX * NU + 8; }
-
 // Phi propagation of TWO disturbance columns j0, j0 + 1 (ncols = 1: only j0) of one instance by one wave: per stage K_k and A_k + B_k K_k go to LDS
 // once and serve both columns, whose products are independent chains on the matrix core (the wave waits on dependent LDS -> MFMA -> LDS round trips;
 // with two columns every such trip carries twice the work).  Column j0 + 1 starts one stage later.  Per column the arithmetic is that of a wave
@@ -2068,59 +1975,35 @@ template <int NX, int NU>
 __device__ __forceinline__ void sweep_prop_dev(const SweepSharedArgs &aa, int b, int j0, int ncols, int lane, double *sm) {
     const SweepArgs &a = aa.s;
     using L = Lay<NX, NU>;
-    constexpr int NZ = L::NZ, NI = L::NI, NIF = L::NIF, NW = NX;
+    using W = SweepPropLds<NX, NU>;
+    constexpr int NI = L::NI, NW = NX;
     const int N = a.N;
-    double *p = sm;
-    double *sAcl = p; p += NX * NX;
-    double *PcA = p; p += NX * NX; double *PnA = p; p += NX * NX;
-    double *PcB = p; p += NX * NX; double *PnB = p; p += NX * NX;
-    double *sK = p; p += NX * NU; double *sPuA = p; p += NU * NW; double *sPuB = p; p += NU * NW;
+    double *sAcl = sm + W::oAcl, *PcA = sm + W::oPcA, *PnA = sm + W::oPnA, *PcB = sm + W::oPcB, *PnB = sm + W::oPnB, *sK = sm + W::oK, *sPuA = sm + W::oPuA, *sPuB = sm + W::oPuB;
     const double *gKc = aa.Kc + (size_t)b * N * NU * NX, *gAc = aa.Aclc + (size_t)b * N * NX * NX;
-    double *beta = a.beta + (size_t)b * N * N * NI, *beta_f = a.beta_f + (size_t)b * (N + 1) * NIF;
+    double *beta = a.beta + (size_t)b * N * N * NI;
     const double *EgA = a.E + (a.E_per_instance ? (size_t)b * (N + 1) * NX * NW : 0) + (size_t)j0 * NX * NW;
     const bool two = ncols > 1;
 #pragma unroll
     for (int o = lane; o < NX * NW; o += 64) { PcA[o] = EgA[o]; if (two) PcB[o] = EgA[NX * NW + o]; }
     wla::wsync();
-    constexpr int RA = (NX * NX + 63) / 64, RB = (NX * NU + 63) / 64;
-    double rA[RA], rK[RB];
+    SweepBlock<NX * NX> rA;
+    SweepBlock<NX * NU> rK;
     double ctA = 0.0, ctB = 0.0;
     auto fetch2 = [&](int k) {
-        const double *Ak = gAc + (size_t)k * NX * NX, *Kk = gKc + (size_t)k * NU * NX;
-#pragma unroll
-        for (int r = 0; r < RA; r++) rA[r] = Ak[min(r * 64 + lane, NX * NX - 1)];
-#pragma unroll
-        for (int r = 0; r < RB; r++) rK[r] = Kk[min(r * 64 + lane, NX * NU - 1)];
+        rA.load(gAc + (size_t)k * NX * NX, lane);
+        rK.load(gKc + (size_t)k * NU * NX, lane);
     };
     // the row weights of the tube cost are batch constants: read once, ahead of the stage loop (a load inside it that is used at once would
     // land the next stage's fetch2 with it)
-    const int lz = min(lane, NZ - 1);
-    const double wreg = (lz < NX) ? a.cst.Qregd[lz] : a.cst.Rregd[lz - NX];
-    // row norms of [Phi_x; Phi_u] of column j at stage k -> beta, tube cost
+    const double wreg = row_weight<NX, NU>(a.cst, lane);
     auto norms = [&](const double *Pc, const double *sPu, int k, int j, double &ctube) {
-        const int g3 = lane / NZ, rw = lane - g3 * NZ;
-        const double *row = (rw < NX) ? Pc + rw * NW : sPu + (rw - NX) * NW;
-        double s = 0.0;
-        if (g3 < 3) {
-#pragma unroll
-            for (int q = 0; q < (NW + 2) / 3; q++) { const int w = 3 * q + g3; if (w < NW) s = fma(row[w], row[w], s); }
-        }
-        s = s + __shfl(s, lane + NZ) + __shfl(s, lane + 2 * NZ);
-        if (lane < NZ) {
-            const double wr = wreg;
-            ctube = fma(wr * wr, s, ctube);
-            s = fmax(s, a.eps);
-            double *bo = beta + ((size_t)k * N + j) * NI;
-            bo[lane] = s; bo[NZ + lane] = s;
-        }
+        tube_norms<NX, NU>(Pc, sPu, wreg, a.eps, beta + ((size_t)k * N + j) * NI, ctube, lane);
     };
-    constexpr bool PAIR = (SWEEP_MFMA != 0) && NX >= 13;
+    constexpr bool PAIR = sweep_mfma<NX>;
     if (j0 < N) fetch2(j0);
     for (int k = j0; k < N; k++) {
-#pragma unroll
-        for (int r = 0; r < RA; r++) { const int o = r * 64 + lane; if (o < NX * NX) sAcl[o] = rA[r]; }
-#pragma unroll
-        for (int r = 0; r < RB; r++) { const int o = r * 64 + lane; if (o < NX * NU) sK[o] = rK[r]; }
+        rA.store(sAcl, lane);
+        rK.store(sK, lane);
         wla::wsync();
         if (k + 1 < N) fetch2(k + 1);
         const bool bB = two && k > j0;      // column j0 + 1 has its first stage at k = j0 + 1
@@ -2129,52 +2012,29 @@ __device__ __forceinline__ void sweep_prop_dev(const SweepSharedArgs &aa, int b,
             wla::gemm_mfma_pair<NU, NX, NW, NX>(sK, NX, sAcl, NX, PcA, NW, sPuA, NW, PnA, NW, lane);
             if (bB) wla::gemm_mfma_pair<NU, NX, NW, NX>(sK, NX, sAcl, NX, PcB, NW, sPuB, NW, PnB, NW, lane);
         } else {
-            wla::gemm_blk<NU, NW, NX, false, false, 1, 2, false>(sK, NX, PcA, NW, sPuA, NW, 1.0, lane);  // Phi_u = K Phi_x
-            if (bB) wla::gemm_blk<NU, NW, NX, false, false, 1, 2, false>(sK, NX, PcB, NW, sPuB, NW, 1.0, lane);
+            sweep_gemm<NX, NU, NU, NW, NX>(sK, NX, PcA, NW, sPuA, NW, lane);  // Phi_u = K Phi_x
+            if (bB) sweep_gemm<NX, NU, NU, NW, NX>(sK, NX, PcB, NW, sPuB, NW, lane);
         }
         wla::wsync();
         norms(PcA, sPuA, k, j0, ctA);
         if (bB) norms(PcB, sPuB, k, j0 + 1, ctB);
         if constexpr (!PAIR) {
-            wla::gemm_blk<NX, NW, NX, false, false, 3, 2, false>(sAcl, NX, PcA, NW, PnA, NW, 1.0, lane);   // Phi_{k+1} = Acl Phi_k
-            if (bB) wla::gemm_blk<NX, NW, NX, false, false, 3, 2, false>(sAcl, NX, PcB, NW, PnB, NW, 1.0, lane);
+            sweep_gemm<NX, NU, NX, NW, NX>(sAcl, NX, PcA, NW, PnA, NW, lane);   // Phi_{k+1} = Acl Phi_k
+            if (bB) sweep_gemm<NX, NU, NX, NW, NX>(sAcl, NX, PcB, NW, PnB, NW, lane);
         }
         wla::wsync();
         { double *t = PcA; PcA = PnA; PnA = t; }
         if (bB) { double *t = PcB; PcB = PnB; PnB = t; }
     }
-    auto terminal = [&](const double *Pc, int j, double ctube) {
-        if (lane < NX) {
-            const double *row = Pc + lane * NW;
-            double s = 0.0;
-#pragma unroll
-            for (int w = 0; w < NW; w++) s = fma(row[w], row[w], s);
-            ctube = fma(a.cst.Qregfd[lane] * a.cst.Qregfd[lane], s, ctube);
-            s = fmax(s, a.eps);
-            beta_f[j * NIF + lane] = s; beta_f[j * NIF + NX + lane] = s;
-        }
-        ctube = wla::wave_sum(ctube);
-        if (lane == 0 && a.ct_part) a.ct_part[(size_t)b * (N + 1) + j] = ctube;
-    };
-    terminal(PcA, j0, ctA);
-    if (two) terminal(PcB, j0 + 1, ctB);
+    tube_terminal<NX, NU>(a, b, j0, PcA, ctA, lane);
+    if (two) tube_terminal<NX, NU>(a, b, j0 + 1, PcB, ctB, lane);
 }
 template <int NX, int NU>
 __global__ __launch_bounds__(64, 3) void k_sweep_prop(SweepSharedArgs aa) {
     const SweepArgs &a = aa.s;
     const int ncol = a.N + 1, npair = (ncol + 1) / 2;
     int b, jp;
-    {   // XCD-aware mapping: blocks i and i+8 share an XCD; all column pairs of an instance stay on one XCD (its K_k, A_k + B_k K_k stay in that L2)
-        const int bid = blockIdx.x;
-        const int Bfull = (a.B / 8) * 8;
-        if (bid < Bfull * npair) {
-            const int xcd = bid % 8, slot = bid / 8;
-            b = (slot / npair) * 8 + xcd; jp = slot % npair;
-        } else {
-            const int r = bid - Bfull * npair;
-            b = Bfull + r / npair; jp = r % npair;
-        }
-    }
+    xcd_block_map(blockIdx.x, a.B, npair, &b, &jp);
     if (b >= a.B) return;
     if (a.run && !a.run[b]) return;
     extern __shared__ double sm[];

@@ -160,6 +160,44 @@ def test_route_d_shared_kernels_against_the_per_column_kernel(model, N, variant)
     assert np.array_equal(out["cost_tube_value"], ra["cost_tube"][:3])
 
 
+@pytest.mark.parametrize("model,N", [("quadrotor", 2), ("rocket", 3)])
+def test_general_G_sweep_at_the_matrix_core_dimension_pairs(model, N):
+    """k_sweep_gen at (13, 4) and (17, 4): the only general-G fixture (tests/test_gpu_parity.py) is the pendulum's, (4, 1).  A general G
+    (2 nz + 3 rows) and Gf (2 nx + 1 rows), N(0, 1) / sqrt(nz) entries below the model's [I; -I] rows (so that C_uu + R_reg stays well conditioned),
+    eta and eta_f uniform at the scale of route a's eta for the same input set, pushed into slsqp_sweep and held against the longdouble sweep on
+    the same arrays, every instance."""
+    from types import SimpleNamespace
+    from robust_nonlinear_mpc_amd import BatchedFastSLS
+    B = 3
+    insts = make_case(model, N, "dense", B)
+    base, E = insts[0].m, insts[0].E
+    nx, nu, nz = base.nx, base.nu, base.nz
+    ni, nif = 2 * nz + 3, 2 * nx + 1
+    rng = np.random.default_rng(1900 + nx)
+    G, Gf = rng.normal(size=(ni, nz)) / np.sqrt(nz), rng.normal(size=(nif, nx)) / np.sqrt(nz)
+    G[:2 * nz], Gf[:2 * nx] = base.G, base.Gf
+    scale = float(np.abs(route_a(model, N, "dense")[1]["eta"]).max()) or 1.0
+    eta, eta_f = scale * rng.uniform(size=(B, N, N, ni)), scale * rng.uniform(size=(B, N + 1, nif))
+    m = SimpleNamespace(nx=nx, nu=nu, nw=base.nw, ni=ni, ni_f=nif, G=G, Gf=Gf, gf=np.zeros(nif), E=base.E, Q=base.Q, R=base.R, Qf=base.Qf)
+    f = BatchedFastSLS(N, m.Q, m.R, m, m.Qf, base.Q_reg, base.R_reg, base.Q_reg_f, batch=B)
+    A, Bm = stack(insts, "A"), stack(insts, "B")
+    f.update_dynamics_list(A, Bm, E, np.zeros((B, N, ni)), np.zeros((B, nif)), np.zeros((B, N, nx)))
+    out = f.sweep(eta, eta_f)
+    f.close()
+    worst = {}
+    for b in range(B):
+        ref = SR.sweep(A[b], Bm[b], E, G, Gf, eta[b], eta_f[b], base.Q_reg, base.R_reg, base.Q_reg_f, EPS)
+        want = float(ref["cost_tube"])
+        errs = {k: relerr(out[k][b], ref[k]) for k in ("K", "beta", "beta_f", "backoff", "backoff_f")}
+        errs["cost_tube"] = abs(out["cost_tube_value"][b] - want) / max(1.0, want)
+        for k, e in errs.items():
+            worst[k] = max(worst.get(k, 0.0), e)
+        print(f"general G {model} N{N} instance {b}:", {k: f"{e:.1e}" for k, e in errs.items()})
+        for k, e in errs.items():
+            assert e < TOL, (b, k, e)
+    print(f"general G {model} N{N} (eta scale {scale:.3g}) largest relative errors against the longdouble sweep:", {k: f"{v:.1e}" for k, v in worst.items()})
+
+
 @pytest.mark.parametrize("model,N", [("pendulum", 5), ("quadrotor", 5)])
 @pytest.mark.parametrize("variant", ["model", "dense", "nw"])
 def test_route_e_converge_mode_eta_is_exact(model, N, variant):
