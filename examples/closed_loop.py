@@ -10,6 +10,7 @@ fast_sls_rti_steps, step counts and (rocket) seed-s disturbance streams; B indep
     ... --reference neutral | figure8                                      # track the plant's neutral point / a figure of eight in x, y
     ... --plant-scale mass=1.15 --plant-spread 10                          # a true plant that differs from the controller's model (see --help)
     ... --model quadrotor --bound 5=-1.2:inf@3                             # a box that changes during the run: descent rate >= -1.2 from step 3 on
+    ... --solve-every 3                                                    # solve at steps 0, 3, 6, ...; the tube policy of the last solve acts in between
 
 The first nominal comes from the GPU initialiser (slsqp_nominal_solve) in place of IPOPT."""
 import argparse
@@ -47,6 +48,9 @@ def main():
     ap.add_argument("--bound", action="append", default=[], metavar="IDX=LO:HI[@ROW]",
                     help="component IDX of [x; u] is held to [LO, HI] from MPC step ROW on (default 0), inside the model's own box; inf / -inf: that side keeps "
                     "the model's bound (repeatable)")
+    ap.add_argument("--solve-every", type=int, default=1, metavar="M",
+                    help="the controller solves at steps 0, M, 2M, ... and holds its plan in between, the tube's feedback policy acting on the measured state "
+                    "(1 <= M <= N; above 1 the loop runs step by step)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -100,7 +104,8 @@ def main():
             bounds = box_bounds(m, Tb, spec)
         except ValueError as e:
             ap.error(str(e))
-    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P, bounds=bounds)
+    cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P, bounds=bounds,
+                       solve_every=a.solve_every)
     t0 = time.perf_counter()
     run = cl.run_decoupled if a.persistent else cl.run_on_device
     out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1)
@@ -109,6 +114,10 @@ def main():
     dist1 = np.linalg.norm(out["state_trajectory"][:, :, -1] - m.x_ref, axis=1).mean()
     print(f"{a.model}: {B} runs x {steps} MPC steps (N={N}, rti={cl.rti}) in {dt:.2f} s; nominal NLP solved for {np.mean(cl.nlp_status == 0):.3f}; "
           f"MPC steps solved {out['success'].mean():.3f}; mean |x - x_ref| {dist0:.3f} -> {dist1:.3f}; QP {out['t_qp'].sum():.0f} ms, sweeps {out['t_riccati'].sum():.0f} ms")
+    if a.solve_every > 1:
+        held = out["hold_index"] > 0
+        print(f"solve every {a.solve_every} steps: {held.mean():.3f} of the steps held; the tube policy ran on {out['hold_policy'][held].mean():.3f} of them "
+              f"(the rest had no valid plan and applied the nominal input)")
     if P is not None:
         du = out["disturbance_used"]
         print(f"plant mismatch: steps with disturbance_used > 1 (model error + noise outside the box the tubes assume): {np.mean(du > 1.0):.3f}; "

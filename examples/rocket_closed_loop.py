@@ -11,6 +11,7 @@ nominal NLP on the GPU (slsqp_nominal_solve, trust-region SCP from a hover roll-
 `--plant-scale NAME=FACTOR` (repeatable) and `--plant-spread PCT` make the TRUE plant differ from the controller's model: a rocket that is heavier,
 a servo that is slower, every parameter of seed s uniform within +-PCT % of its default.  The run then reports how often the model error plus the
 noise left the disturbance box the tubes were designed for (`disturbance_used` > 1) and the constraint violations of the measured states.
+`--solve-every M` runs the controller at 1/M of the plant's rate: a solve at steps 0, M, 2M, ..., the tube's feedback policy in between.
 """
 import argparse
 import os
@@ -40,6 +41,8 @@ def main():
                     help="the TRUE plant's parameter NAME is FACTOR x the controller's value, for every seed (repeatable), e.g. mass=1.15")
     ap.add_argument("--plant-spread", type=float, default=None, metavar="PCT",
                     help="every parameter of the true plant of seed s uniform within +-PCT %% of its default, drawn from a generator seeded with s (gimbal lengths excluded)")
+    ap.add_argument("--solve-every", type=int, default=1, metavar="M",
+                    help="the controller solves at steps 0, M, 2M, ... and holds its plan in between, the tube's feedback policy acting on the measured state (1 <= M <= N)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model("rocket")
@@ -51,7 +54,7 @@ def main():
     x0 = m.x_ref + a.x0_scale * (m.extra["x0"] - m.x_ref)
     t0 = time.perf_counter()
     r = run_monte_carlo(m, a.N, np.arange(a.seeds), a.steps, x0, solve_nominal=(a.init == "sqp"), slices=a.slices, continuation=a.continuation,
-                        budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P)
+                        budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P, solve_every=a.solve_every)
     dt = time.perf_counter() - t0
     ok = r["success"]
     if "nlp_status" in r:
@@ -60,6 +63,12 @@ def main():
     print(f"{a.seeds} seeds x {a.steps} MPC steps (N={a.N}) in {dt:.2f} s; solved steps: {ok.mean():.3f}; "
           f"final |pos| mean {np.linalg.norm(r['state_trajectory'][:, :3, -1], axis=1).mean():.3f} "
           f"(start {np.linalg.norm(x0[:3]):.3f}); largest stage-0 violation of the measured state {r['x0_violation'].max():.2e}; QP {r['t_qp'].sum():.1f} ms, Riccati sweeps {r['t_riccati'].sum():.1f} ms")
+    if a.solve_every > 1:
+        held = r["hold_index"] > 0
+        X = r["state_trajectory"]
+        viol = np.maximum(X - m.x_ub[None, :, None], m.x_lb[None, :, None] - X).max(axis=1)
+        print(f"solve every {a.solve_every} steps: {held.mean():.3f} of the steps held, the tube policy ran on {r['hold_policy'][held].mean():.3f} of them; "
+              f"measured states outside the state box: {np.mean(viol > 0):.4f} of the steps")
     if P is not None:
         X = r["state_trajectory"]      # (seeds, nx, steps): the measured states
         viol = np.maximum(X - m.x_ub[None, :, None], m.x_lb[None, :, None] - X).max(axis=1)

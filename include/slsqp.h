@@ -260,6 +260,31 @@ int slsqp_linearize(slsqp_handle *h, const double *X, const double *U, int loc);
    scp_delta_max (1) primal_infeasibility (1; max_k,i (ddyn(x_k,u_k) - x_{k+1})_i of the updated nominal, SCP_SLS_jit.py:449-456) + all names of the fast-SLS result (for each instance: of its last fast-SLS solve). */
 int slsqp_cl_init(slsqp_handle *h, const double *x_meas, const double *X_nom, const double *U_nom, const double *u_init, int loc);
 int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc, const slsqp_opts *opts);
+/* One closed-loop step WITHOUT a solve: the plan of the last slsqp_cl_step is held and its tube policy acts on the measured state -- the
+   disturbance-feedback gains K[k,j] of the Riccati sweep (Phi_u = K Phi_x, fast_SLS_jit.py:87-117) that the tightened QP assumed along the horizon.
+   Hold step k = 1, 2, ... is the k-th plant step since that solve (stage 0 of the plan was pinned to the state measured then); z_k, v_k the plan's
+   nominal at stage k, A_j, B_j the handle's linearisation and K what slsqp_get "K" returns, all as they stand after the solve.  Per instance, column
+   states xi_j (nx), j = 1..k:
+       e     = x_meas - z_k
+       xi_j <- (A_{k-1} + B_{k-1} K[k-1,j]) xi_j     1 <= j < k       the plan's prediction of the old columns
+       xi_k  = e - sum_{j<k} xi_j                                     what the plan did not predict: disturbance + model defect
+       u     = v_k + sum_{1<=j<=k} K[k,j] xi_j
+       x_meas <- plant(x_meas, u) + E w                               the plant step of slsqp_cl_step (plant parameters included)
+   The call shifts the nominal by one stage (the warm-start shift slsqp_cl_step applies at its top), so afterwards stage 0 of nominal_x / nominal_u is
+   z_k, v_k; the nominal is never overwritten with u.  It counts as a closed-loop step: the step count of the reference / bounds windows and the log
+   entry advance.  An instance whose last slsqp_cl_step ended with scp_success = 0 has no valid plan: it applies u = v_k (what a failed solved step
+   applies), keeps its xi, and reports hold_policy = 0.  The input is not clipped to the box.  k <= N - 1 (K has N rows).  The next slsqp_cl_step
+   solves from the held nominal; its QP warm sets move one stage while the horizon moved k + 1 (speed only: every answer is certified).
+   w (B,nx) disturbance sample or NULL.
+   Errors (< 0, slsqp_last_error; nothing changed): no slsqp_set_model; no slsqp_cl_step since slsqp_cl_init; the hold index would exceed N - 1; a
+   slsqp_cl_run / slsqp_cl_run_scp since the last slsqp_cl_step (they leave no per-batch plan); loc outside {SLSQP_HOST, SLSQP_DEVICE}.
+   slsqp_cl_init and slsqp_cl_step set the hold index back to 0.
+   Results (slsqp_get, slsqp_result_bytes): hold_index[int32] (1) hold steps since the last solve; hold_xi (N+1,nx) row j = xi_j, rows above the index
+   zero; hold_policy[int32] (1) of the last hold step: 1 the policy ran, 0 the nominal input was applied; u0, x_meas, model_err as after
+   slsqp_cl_step.  With slsqp_cl_log: log_hold[int32] (S) 0 for a solved step, k for hold step k; log_hold_policy[int32] (S); the entry's log_state and
+   log_u0 are the measured state and the applied input, log_nominal_* the shifted plan, log_backoff_* and log_success the last solve's,
+   log_scp_iterations 0 and log_x0_viol 0. */
+int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc);
 /* The whole closed loop with the instances advancing INDEPENDENTLY (rti = 1, one fast-SLS step, fp64, fuse_rti: the rocket script's setting):
    `steps` MPC steps of every instance, W (steps,B,nx) disturbance samples or NULL.  Per instance the same operations in the same order as `steps`
    calls of slsqp_cl_step (identical results), but in rounds: in a round an instance begins its next MPC step or resumes the QP solve that the

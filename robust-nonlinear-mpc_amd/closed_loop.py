@@ -22,7 +22,7 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None, solve_every=1):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
         state never fails a step on its own (slsqp_set_x0_box_tol).
@@ -30,7 +30,9 @@ class ClosedLoopMPC:
         takes the step-by-step loop, the persistent kernels being one wave per instance.
         reference: see set_reference (None: the cost is around the origin of the raw state, as in the reference's scripts).
         plant_params: see set_plant_params (None: the true plant is the controller's model).
-        bounds: see set_bounds (None: the model's box, the same for every instance and every step)."""
+        bounds: see set_bounds (None: the model's box, the same for every instance and every step).
+        solve_every: M of run / run_on_device / run_decoupled: the controller solves at steps 0, M, 2M, ... and holds its plan in between
+        (hold_step: the tube policy of the last solve acts on the measured state); 1 <= M <= N; 1 (default): a solve at every step."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -44,12 +46,19 @@ class ClosedLoopMPC:
         if solve_waves != 1:
             self.f.opts.solve_waves = int(solve_waves)
         self.steps_done = 0
+        self.solve_every = self._check_solve_every(solve_every)
         if reference is not None:
             self.set_reference(reference)
         if plant_params is not None:
             self.set_plant_params(plant_params)
         if bounds is not None:
             self.set_bounds(bounds)
+
+    def _check_solve_every(self, M):
+        M = self.solve_every if M is None else int(M)
+        if not 1 <= M <= self.N:
+            raise ValueError(f"solve_every must lie in 1..N = {self.N} (K has N rows: at most N - 1 hold steps between two solves), got {M}")
+        return M
 
     def set_bounds(self, bounds, gf=None):
         """The box in force from the next reset() on: a pair (g, gf) (tuple or list) or g, gf -- rows over MPC time in the model's layout [hi; -lo], (T,ni) / (T,ni_f)
@@ -138,18 +147,48 @@ class ClosedLoopMPC:
             t_qp_ms=f.timing_ms()["qp"], t_riccati_ms=f.timing_ms()["sweep"], t_jac_ms=f.timing_ms()["jac"],
         )
 
-    def run_on_device(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1):
+    def hold_step(self, w=None, fetch=True):
+        """One closed-loop step of the whole batch without a solve (BatchedFastSLS.hold_step): the plan of the last step() is held, its tube policy
+        gives the input from the measured state.  The keys of step(); `nominal_x` / `nominal_u` are the plan moved to this step, the back-offs and
+        `success` the last solve's, plus `state` (the measured state the input was computed for), `hold_index` and `hold_policy` (False: the instance
+        has no valid plan and applied the nominal input)."""
+        f, m, N = self.f, self.m, self.N
+        wv = None if w is None else _c(w)
+        state = f.get("x_meas", (m.nx,)) if fetch else None
+        f.hold_step(wv)
+        self.steps_done += 1
+        self._W_log.append(wv)
+        if not fetch:
+            return None
+        return dict(
+            u0=f.get("u0", (m.nu,)), x_next=f.get("x_meas", (m.nx,)), state=state,
+            nominal_x=f.get("nominal_x", (N + 1, m.nx)), nominal_u=f.get("nominal_u", (N, m.nu)),
+            backoff_x=f.get("backoff_x", (N + 1, m.nx)), backoff_u=f.get("backoff_u", (N, m.nu)),
+            success=f.get("scp_success", (), np.int32).astype(bool), status=f.get("status", (), np.int32),
+            scp_iterations=np.zeros(self.B, dtype=np.int32), primal_infeasibility=f.get("primal_infeasibility", ()),
+            x0_violation=np.zeros((self.B, 2)), hold_index=f.get("hold_index", (), np.int32), hold_policy=f.get("hold_policy", (), np.int32).astype(bool),
+            t_qp_ms=0.0, t_riccati_ms=0.0, t_jac_ms=0.0,
+        )
+
+    def run_on_device(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, solve_every=None):
         """Same result as run(), but the per-step records stay in device buffers (slsqp_cl_log) and are read back once at the end: the only
-        host -> device traffic per MPC step is the disturbance sample (B,nx)."""
+        host -> device traffic per MPC step is the disturbance sample (B,nx).  solve_every = M > 1 (None: the constructor's): see run()."""
         f, m, N, B = self.f, self.m, self.N, self.B
+        M = self._check_solve_every(solve_every)
         L.check(f.lib.slsqp_cl_log(f.h, int(steps)))
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
         t_qp, t_ric, t_jac = np.zeros((steps, 1)), np.zeros((steps, 1)), np.zeros((steps, 1))
         for i in range(steps):
-            self.step(None if W is None else W[i], fetch=False)
+            if i % M:
+                self.hold_step(None if W is None else W[i], fetch=False)
+            else:
+                self.step(None if W is None else W[i], fetch=False)
             t = f.timing_ms()
             t_qp[i], t_ric[i], t_jac[i] = t["qp"], t["sweep"], t["jac"]
-        return self._log_result(steps, t_jac, t_qp, t_ric)
+        out = self._log_result(steps, t_jac, t_qp, t_ric)
+        if M > 1:
+            out.update(hold_index=f.get("log_hold", (steps,), np.int32), hold_policy=f.get("log_hold_policy", (steps,), np.int32).astype(bool))
+        return out
 
     def _log_result(self, steps, t_jac, t_qp, t_ric):
         """The arrays of the device-side log (slsqp_cl_log) laid out like the reference's npz, batch axis first."""
@@ -186,7 +225,7 @@ class ClosedLoopMPC:
                 wm[:, i] += w
         return np.max(np.abs(wm), axis=2).T.copy()
 
-    def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0):
+    def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0, solve_every=None):
         """Same results as run_on_device() -- bit for bit -- with the instances advancing through their MPC steps independently, so nobody waits for
         the slowest instance of a step.
         rti = 1 with one fast-SLS step (the rocket script's setting): slsqp_cl_run.  With opts.cl_persistent (the default) the whole loop is ONE launch:
@@ -195,10 +234,13 @@ class ClosedLoopMPC:
         Every other setting slsqp_cl_step takes with a fixed number of fast-SLS steps (rti > 1, SCP converge mode rti <= 0, rti_steps > 1: the
         pendulum and quadrotor scripts, SCP_SLS's default): slsqp_cl_run_scp, always one persistent launch (budget_ms / cut_frac ignored).  Fast-SLS
         converge mode (fast_sls_rti_steps None), precision = 1 and SLSQP_FUSE_RTI=0 are refused with the library's message.
+        solve_every = M > 1 (None: the constructor's): the persistent kernels solve at every step, so the run takes the step-by-step loop (run_on_device), as
+        it does for solve_waves > 1.
         Adds `qp_stats` (B, steps, 2, 8) (next to `x0_violation` (B, steps, 2), which every logged run has), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the run's totals in their first entry."""
         f, m, N, B = self.f, self.m, self.N, self.B
-        if f.opts.solve_waves > 1:      # the persistent kernels are one wave per instance: the same loop, step by step (no qp_stats / loop_stats)
-            out = self.run_on_device(x0, steps, W, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
+        M = self._check_solve_every(solve_every)
+        if f.opts.solve_waves > 1 or M > 1:      # the persistent kernels are one wave per instance and solve at every step: the same loop, step by step (no qp_stats / loop_stats)
+            out = self.run_on_device(x0, steps, W, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation, solve_every=M)
             out["rounds"] = steps
             return out
         L.check(f.lib.slsqp_cl_log(f.h, int(steps)))
@@ -226,10 +268,13 @@ class ClosedLoopMPC:
             out["loop_stats"] = dict(waves=int(st[0]), busy_ms=float(st[1]), mpc_steps=int(st[2]), launch_ms=float(st[3]))
         return out
 
-    def run(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False):
+    def run(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, solve_every=None):
         """Closed loop of `steps` MPC steps from x0 (B,nx); W (steps,B,nx) disturbance samples or None.  Returns arrays laid out
-        like the reference's npz (expe/main_rocket_robust_closed_loop.py:189-206) with a leading batch axis."""
+        like the reference's npz (expe/main_rocket_robust_closed_loop.py:189-206) with a leading batch axis.
+        solve_every = M > 1 (None: the constructor's): a solve at steps 0, M, 2M, ..., hold_step() in between; the result then also holds `hold_index`
+        (B, steps) (0: a solved step, k: the k-th hold step since the solve) and `hold_policy` (B, steps) (the tube policy ran)."""
         m, N, B = self.m, self.N, self.B
+        M = self._check_solve_every(solve_every)
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal)
         out = dict(
             state_trajectory=np.zeros((B, m.nx, steps)), input_trajectory=np.zeros((B, m.nu, max(steps - 1, 0))),
@@ -239,9 +284,15 @@ class ClosedLoopMPC:
             success=np.zeros((B, steps), dtype=bool), scp_iterations=np.zeros((B, steps), dtype=np.int32),
             primal_infeasibility=np.full((B, steps), np.nan), x0_violation=np.zeros((B, steps, 2)),
         )
+        if M > 1:
+            out.update(hold_index=np.zeros((B, steps), dtype=np.int32), hold_policy=np.zeros((B, steps), dtype=bool))
         for i in range(steps):
-            r = self.step(None if W is None else W[i])
-            out["state_trajectory"][:, :, i] = r["nominal_x"][:, 0, :]
+            if i % M:
+                r = self.hold_step(None if W is None else W[i])
+                out["hold_index"][:, i], out["hold_policy"][:, i] = r["hold_index"], r["hold_policy"]
+            else:
+                r = self.step(None if W is None else W[i])
+            out["state_trajectory"][:, :, i] = r["state"] if i % M else r["nominal_x"][:, 0, :]
             if i < steps - 1:
                 out["input_trajectory"][:, :, i] = r["u0"]
             out["nominal_trajectory_x"][:, :, :, i] = r["nominal_x"].transpose(0, 2, 1)

@@ -19,6 +19,8 @@
 #include "slsqp_mw.hpp"
 #include "plant_params.hpp"
 #include "cl_bounds.hpp"
+#include "cl_hold.hpp"
+#include "cl_hold_kernel.hpp"
 
 using namespace slsqp;
 
@@ -83,6 +85,9 @@ struct slsqp_handle {
     // slsqp_cl_set_bounds: the packed rows (sets, T, ni + ni_f) (bnd_stride = T (ni + ni_f) per instance, 0 shared; bnd_rows NULL: none).  bnd_host: the packed
     // rows on the host (slsqp_get "bounds_g" / "bounds_gf"); g_raw_host / gf_raw_host: the model's box, served where no bounds are set.
     double *bnd_rows = nullptr; int bnd_T = 0; size_t bnd_stride = 0; std::vector<double> bnd_host, g_raw_host, gf_raw_host;
+    // slsqp_cl_hold_step: which hold step comes next (cl_hold.hpp) and, allocated by the first hold step, one buffer [xi (B,N+1,nx) | u (B,nu)] of the
+    // column states and the applied input, and the per-instance flag "the policy ran"; lg_hold / lg_hpol: their per-step log (part of the slsqp_cl_log buffers)
+    cl_hold::State hold; double *hold_xi = nullptr, *hold_u = nullptr; int *hold_policy = nullptr, *lg_hold = nullptr, *lg_hpol = nullptr;
     double *cr = nullptr;       // (B,N,3,nx,nx) scratch of the cyclic reduction (slsqp_mw.hpp), allocated by the first launch that needs it
     int ne_waves = 0;           // slsqp_ne_solve: the path whose factors the last factorising call left (0 = none)
     double x0_tol_dev = 0.0;    // the tolerance of the x0 gate the device currently holds (kkt[8 B]; written when a launch asks for another one)
@@ -346,6 +351,8 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     if (h->stage) hipFree(h->stage);
     if (h->cl_W) hipFree(h->cl_W);
     opt_clear(&h->ref_Y); opt_clear(&h->pp_P); opt_clear(&h->bnd_rows);
+    if (h->hold_xi) hipFree(h->hold_xi);
+    if (h->hold_policy) hipFree(h->hold_policy);
     if (h->qplog) hipFree(h->qplog);
     if (h->x0vlog) hipFree(h->x0vlog);
     if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
@@ -1738,6 +1745,8 @@ extern "C" long long slsqp_result_bytes(slsqp_handle *h, const char *name) {
     if (!strcmp(name, "model_err")) return (long long)sizeof(double) * h->d.nx;
     if (!strcmp(name, "bounds_g")) return (long long)sizeof(double) * h->d.ni * (h->bnd_rows ? h->bnd_T : 1);
     if (!strcmp(name, "bounds_gf")) return (long long)sizeof(double) * h->d.ni_f * (h->bnd_rows ? h->bnd_T : 1);
+    if (!strcmp(name, "hold_index") || !strcmp(name, "hold_policy")) return (long long)sizeof(int);
+    if (!strcmp(name, "hold_xi")) return (long long)sizeof(double) * (h->d.N + 1) * h->d.nx;
     auto it = h->named.find(name);
     return it == h->named.end() ? -1LL : (long long)it->second.second;
 }
@@ -1891,10 +1900,30 @@ static int get_bounds_named(slsqp_handle *h, const char *name, void *out, int lo
     return 1;
 }
 
+// slsqp_get names of the hold steps (slsqp_cl_hold_step): hold_index[int32] (1) hold steps since the last solve, hold_xi (N+1,nx) the column states
+// (rows above the index zero), hold_policy[int32] (1) of the last hold step; zeros on a handle that never held.  Returns 1 when `name` was one of
+// them and has been served, 0 when not, -1 on error.
+static int get_hold_named(slsqp_handle *h, const char *name, void *out, int loc) {
+    const bool is_k = !strcmp(name, "hold_index"), is_x = !strcmp(name, "hold_xi"), is_p = !strcmp(name, "hold_policy");
+    if (!is_k && !is_x && !is_p) return 0;
+    HIPCHK(hipStreamSynchronize(h->st));
+    const size_t B = h->B, nxi = B * (h->d.N + 1) * h->d.nx;
+    const hipMemcpyKind from_host = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice, from_dev = loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (is_k) { const std::vector<int> v(B, cl_hold::index(h->hold, h->cl_steps)); HIPCHK(hipMemcpy(out, v.data(), sizeof(int) * B, from_host)); }
+    else if (!h->hold_xi) {
+        if (is_x) { const std::vector<double> z(nxi, 0.0); HIPCHK(hipMemcpy(out, z.data(), sizeof(double) * nxi, from_host)); }
+        else { const std::vector<int> z(B, 0); HIPCHK(hipMemcpy(out, z.data(), sizeof(int) * B, from_host)); }
+    }
+    else if (is_x) HIPCHK(hipMemcpy(out, h->hold_xi, sizeof(double) * nxi, from_dev));
+    else HIPCHK(hipMemcpy(out, h->hold_policy, sizeof(int) * B, from_dev));
+    return 1;
+}
+
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
     if (const int r = get_plant_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_bounds_named(h, name, out, loc)) return r < 0 ? -1 : 0;
+    if (const int r = get_hold_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (!h->pp_P && h->lg_merr && !strcmp(name, "log_model_error")) HIPCHK(hipMemsetAsync(h->lg_merr, 0, sizeof(double) * (size_t)h->B * h->log_steps * h->d.nx, h->st));      // (a handle without parameters: all zeros, whatever an earlier run with parameters left)
     auto it = h->named.find(name);
     if (it == h->named.end()) return fail(std::string("unknown result name: ") + name);
@@ -2015,6 +2044,8 @@ extern "C" int slsqp_cl_init(slsqp_handle *h, const double *x_meas, const double
         HIPCHK(hipGetLastError());
     }
     h->cl_steps = 0;
+    cl_hold::on_init(h->hold);      // no plan to hold yet
+    if (h->lg_hold) HIPCHK(hipMemsetAsync(h->lg_hold, 0, sizeof(int) * B * h->log_steps * 2, h->st));      // (log_hold, log_hold_policy: solved steps never write them)
     HIPCHK(hipMemsetAsync(h->has_prev, 0, sizeof(int) * B, h->st));   // a fresh SCP_SLS object has no convergence history
     HIPCHK(hipStreamSynchronize(h->st));
     return slsqp_reset(h);
@@ -2083,9 +2114,9 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     HIPCHK(hipStreamSynchronize(h->st));
     h->log_steps = 0;
     free_all(h->log_owned);
-    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error"};
+    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy"};
     for (const char *nm : names) h->named.erase(nm);
-    h->lg_x0v = nullptr; h->lg_merr = nullptr;
+    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr;
     h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr;
     const slsqp_dims &d = h->d;
     const size_t B = h->B, S = max_steps, nX = (size_t)(d.N + 1) * d.nx, nU = (size_t)d.N * d.nu;
@@ -2094,7 +2125,8 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     rc |= dalloc(ow, &h->lg_x, B * S * nX); rc |= dalloc(ow, &h->lg_u, B * S * nU); rc |= dalloc(ow, &h->lg_bx, B * S * nX); rc |= dalloc(ow, &h->lg_bu, B * S * nU);
     rc |= dalloc(ow, &h->lg_state, B * S * d.nx); rc |= dalloc(ow, &h->lg_u0, B * S * d.nu); rc |= dalloc(ow, &h->lg_succ, B * S); rc |= dalloc(ow, &h->lg_it, B * S);
     rc |= dalloc(ow, &h->lg_pinf, B * S); rc |= dalloc(ow, &h->lg_x0v, B * S * 2); rc |= dalloc(ow, &h->lg_merr, B * S * d.nx);
-    if (rc) { free_all(ow); h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
+    rc |= dalloc(ow, &h->lg_hold, B * S * 2); h->lg_hpol = h->lg_hold ? h->lg_hold + B * S : nullptr;
+    if (rc) { free_all(ow); h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
     h->log_steps = max_steps;
     auto reg = [&](const char *nm, void *p, size_t bytes) { h->named[nm] = {p, bytes}; };
     reg("log_nominal_x", h->lg_x, sizeof(double) * S * nX); reg("log_nominal_u", h->lg_u, sizeof(double) * S * nU);
@@ -2102,6 +2134,7 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     reg("log_state", h->lg_state, sizeof(double) * S * d.nx); reg("log_u0", h->lg_u0, sizeof(double) * S * d.nu);
     reg("log_success", h->lg_succ, sizeof(int) * S); reg("log_scp_iterations", h->lg_it, sizeof(int) * S);
     reg("log_primal_infeasibility", h->lg_pinf, sizeof(double) * S); reg("log_x0_viol", h->lg_x0v, sizeof(double) * S * 2);
+    reg("log_hold", h->lg_hold, sizeof(int) * S); reg("log_hold_policy", h->lg_hpol, sizeof(int) * S);      // slsqp_cl_hold_step: 0 for a solved step, k for hold step k; whether the policy ran
     reg("log_model_error", h->lg_merr, sizeof(double) * S * d.nx);      // ddyn_p - ddyn of every step's plant step (slsqp_cl_set_plant_params; zeros without parameters)
     return 0;
 }
@@ -2177,6 +2210,49 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     HIPCHK(hipGetLastError());
     if (finish_enqueued(h, false)) return -1;
     h->cl_steps++;
+    return 0;
+}
+
+// One closed-loop step WITHOUT a solve: the one-stage shift slsqp_cl_step applies at its top, then k_cl_hold -- the tube policy
+// of the last solve on the measured state, and the plant step.  No slsqp_reset (K stays valid); slsqp_cl_step is not involved and finds, at its next
+// call, a nominal whose stage 0 is the plan's prediction of where the plant is.
+static int ensure_hold(slsqp_handle *h) {
+    if (h->hold_xi) return 0;
+    const size_t nxi = (size_t)h->B * (h->d.N + 1) * h->d.nx, nu = (size_t)h->B * h->d.nu;
+    double *buf = nullptr; int *pol = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (nxi + nu) + 64));
+    if (hipMalloc((void **)&pol, sizeof(int) * h->B + 64) != hipSuccess || hipMemset(buf, 0, sizeof(double) * (nxi + nu)) != hipSuccess || hipMemset(pol, 0, sizeof(int) * h->B) != hipSuccess) {
+        hipFree(buf); if (pol) hipFree(pol);
+        return fail("slsqp_cl_hold_step: allocation failed");
+    }
+    h->hold_xi = buf; h->hold_u = buf + nxi; h->hold_policy = pol;
+    return 0;
+}
+extern "C" int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc) {
+    hipSetDevice(h->dev);
+    std::string why;
+    const int k = cl_hold::next_index(h->hold, h->model_id >= 0, h->cl_steps, h->d.N, loc, &why);
+    if (!k) return fail("slsqp_cl_hold_step: " + why);
+    if (ensure_hold(h)) return -1;
+    const slsqp_dims &d = h->d;
+    const int gb = (h->B + 63) / 64;
+    const double *dw = nullptr;
+    if (w) { if (put(h, h->wbuf, w, sizeof(double) * (size_t)h->B * d.nx, loc)) return -1; dw = h->wbuf; }
+    const ClArgs a = cl_args(h, dw);
+    const ClOptions op = cl_options(h);
+    const bool log = h->log_steps > 0 && h->cl_steps < h->log_steps;
+    HoldArgs ha{a, k, h->A, h->Bm, h->K, h->Kc, h->stale, h->scp_success, h->hold_xi, h->hold_u, h->hold_policy, log ? h->log_steps : 0, h->cl_steps,
+                h->lg_state, h->lg_u0, h->lg_x0v, h->lg_it, h->lg_hold, h->lg_hpol};
+    if (with_model(h, [&](auto M) {
+            hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 1, 0);
+            if (log) hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, cl_log_args(h, nullptr, nullptr, h->cl_steps));      // nominal = the shifted plan, back-offs and success of the last solve; k_cl_hold writes the rest
+            with_flag(op.pp, [&](auto PP) { hipLaunchKernelGGL((k_cl_hold<M(), PP()>), dim3(h->B), dim3(64), 0, h->st, ha, op.pa); });
+        })) return -1;
+    if (log) h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};
+    HIPCHK(hipGetLastError());
+    if (finish_enqueued(h, false)) return -1;
+    h->cl_steps++;
+    cl_hold::on_hold(h->hold, k, h->cl_steps);
     return 0;
 }
 
@@ -2294,6 +2370,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     if (ctl[3] != 0 || unfinished != 0)
         return fail("slsqp_cl_run (persistent): the instance queue did not drain (err " + std::to_string(ctl[3]) + ", " + std::to_string(unfinished) + " instances short of their steps)");
     h->cl_steps = steps;
+    cl_hold::on_run(h->hold, h->cl_steps);      // (no per-batch plan: slsqp_cl_hold_step refuses until a slsqp_cl_step)
     h->call_id += (double)steps * max_it;
     if (rounds_out) *rounds_out = 1;
     return 0;
@@ -2418,6 +2495,7 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
     }
     tl_take(h);
     h->cl_steps = steps;
+    cl_hold::on_run(h->hold, h->cl_steps);
     h->call_id += steps;
     if (rounds_out) *rounds_out = rounds;
     return 0;

@@ -235,6 +235,15 @@ class BatchedFastSLS:
         L.check(self.lib.slsqp_cl_set_bounds(self.h, _ptr(g), _ptr(gf), int(g.shape[-2]), int(g.ndim == 3), L.HOST))
         self.bounds = (g, gf)
 
+    def hold_step(self, w=None):
+        """One closed-loop step without a solve (slsqp_cl_hold_step): the nominal moves one stage, the tube policy of the last slsqp_cl_step -- the
+        gains K of its Riccati sweep on the column states `hold_xi` -- gives the input, the plant steps.  w (B,nx) disturbance sample or None.  At
+        most N - 1 in a row; refused before the first solved step of a run.  get("hold_index", (), np.int32), get("hold_xi", (N + 1, nx)) and
+        get("hold_policy", (), np.int32) read its state, get("u0", (nu,)) / get("x_meas", (nx,)) what it applied and where the plant went."""
+        wv = None if w is None else _c(w)
+        assert wv is None or wv.shape == (self.B, self.m.nx)
+        L.check(self.lib.slsqp_cl_hold_step(self.h, _ptr(wv), L.HOST))
+
     def update_linear_cost(self, q):
         q = _c(q)
         assert q.shape == (self.B, self.n)

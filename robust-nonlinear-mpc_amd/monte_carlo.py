@@ -46,14 +46,14 @@ PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
 
 
 def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1,
-               reference=None, plant_params=None, bounds=None):
+               reference=None, plant_params=None, bounds=None, solve_every=1):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
-    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds)
+    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every)
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
     rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
     want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
-    if budget_ms != 0 and want and can_run_persistent(cl.rti, rti_steps, cl.f.opts):      # instances advance independently (slsqp_cl_run / slsqp_cl_run_scp): same bits
+    if solve_every == 1 and budget_ms != 0 and want and can_run_persistent(cl.rti, rti_steps, cl.f.opts):      # instances advance independently (slsqp_cl_run / slsqp_cl_run_scp): same bits
         out = cl.run_decoupled(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation, budget_ms=8.0 if budget_ms is None else budget_ms)
     else:
         out = cl.run_on_device(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation)
@@ -64,7 +64,8 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 
 
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
-                    budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None):
+                    budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None,
+                    solve_every=1):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
@@ -81,6 +82,9 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     bounds: the box of every seed over MPC time (ClosedLoopMPC.set_bounds: g or (g, gf)); arrays with a leading axis of len(seeds) ((S,T,ni),
     (S,T,ni_f)) are per seed and are cut with the seeds into shards and slices, as a per-seed reference is.  The result then holds
     `constraint_margin` (steps, seeds) and `bounds_g` / `bounds_gf` as given.
+    solve_every: M > 1 = every seed's controller solves at steps 0, M, 2M, ... and holds its plan in between, the tube policy of the last solve acting on
+    the measured state (ClosedLoopMPC.hold_step; 1 <= M <= N); the loops then run step by step and the result holds `hold_index` and `hold_policy`
+    (seeds, steps).  1 (default): today's loops, unchanged.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -130,6 +134,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["x0_box_tol"] = x0_box_tol
             if solve_waves != 1:
                 kw["solve_waves"] = solve_waves
+            if solve_every != 1:
+                kw["solve_every"] = solve_every
             kw.update(options(k))
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:

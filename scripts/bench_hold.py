@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""What holding an MPC solution costs and keeps: the rocket closed loop of bench.py (N = 20, the script's x0, seed-s noise streams) through
+ClosedLoopMPC.run_on_device with a solve every M steps and the tube's feedback policy in between (slsqp_cl_hold_step).
+
+    python scripts/bench_hold.py [--batch 4096] [--steps 30] [--M 1 2 3 5] [--reps 5] [--root DIR]
+
+Per M, one JSON line:
+  ms_per_step        median over --reps runs of the wall time of the loop (first slsqp_cl_step / slsqp_cl_hold_step to the last one's return; the
+                     reset before it and the read-back of the log after it are not timed) divided by the steps; `ms_per_step_runs` holds every run
+  solved_ok          share of the solved steps that succeeded
+  inside_box         share of all steps whose measured state lies inside the model's state box
+  tube_ratio_max     largest |x_meas - z_k|_i / backoff_x[k]_i over the hold steps on which the policy ran (the tubes are row 2-norms of the response
+                     to |w|_2 <= 1 while the samples are uniform in the box |w|_inf <= 1: a ratio above 1 is possible), with `tube_ratio_at` = where it
+                     occurred (instance, step, hold index k, state component, deviation, back-off); tube_ratio_p50 / _p99 the quantiles of the
+                     per-(instance, hold step) largest ratio and tube_exceeded the share of those above 1
+The nominal trajectory of the first step is solved once (slsqp_nominal_solve) and handed to every run, so all runs of all M start from the same plan.
+M = 1 does not name `solve_every` at all: with --root pointing at another checkout (with its library built) the same command measures that tree."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--N", type=int, default=20)
+    ap.add_argument("--M", type=int, nargs="+", default=[1, 2, 3, 5])
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose package is measured")
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.root))
+    from robust_nonlinear_mpc_amd import ClosedLoopMPC, disturbance_stream, get_model
+    m = get_model("rocket")
+    B, N, steps = a.batch, a.N, a.steps
+    x0 = np.tile(np.asarray(m.extra["x0"], dtype=float), (B, 1))
+    W = np.stack([disturbance_stream(s, steps, m.nx) for s in range(B)], axis=1)
+    cl = ClosedLoopMPC(m, N, B)
+    cl.reset(x0, solve_nominal=True, continuation=2)
+    X_nom, U_nom = cl.f.get("nominal_x", (N + 1, m.nx)), cl.f.get("nominal_u", (N, m.nu))
+    nlp_ok = float(np.mean(cl.nlp_status == 0))
+    cl.close()
+    for M in a.M:
+        cl = ClosedLoopMPC(m, N, B) if M == 1 else ClosedLoopMPC(m, N, B, solve_every=M)
+        mark = {}
+        reset, log_result = cl.reset, cl._log_result
+
+        def timed_reset(*args, **kw):
+            r = reset(*args, **kw)
+            mark["t0"] = time.perf_counter()
+            return r
+
+        def timed_log_result(*args, **kw):
+            mark["t1"] = time.perf_counter()
+            return log_result(*args, **kw)
+        cl.reset, cl._log_result = timed_reset, timed_log_result
+        runs, out = [], None
+        for _ in range(a.reps + 1):      # (the first run warms the code objects and the allocator: not counted)
+            out = cl.run_on_device(x0, steps, W, X_nom, U_nom)
+            runs.append(1e3 * (mark["t1"] - mark["t0"]) / steps)
+        cl.close()
+        runs = runs[1:]
+        X = out["state_trajectory"]                                     # (B, nx, steps): the measured state every step started from
+        inside = np.all((X <= m.x_ub[None, :, None]) & (X >= m.x_lb[None, :, None]), axis=1)
+        solved = np.arange(steps) % M == 0
+        rec = dict(M=M, batch=B, N=N, steps=steps, nlp_ok=nlp_ok, ms_per_step=float(np.median(runs)), ms_per_step_runs=[round(r, 4) for r in runs],
+                   solved_ok=float(out["success"][:, solved].mean()), inside_box=float(inside.mean()))
+        if M > 1:
+            per, at = [], None
+            for i in np.nonzero(~solved)[0]:
+                k = i % M
+                ran = np.nonzero(out["hold_policy"][:, i])[0]
+                if not len(ran):
+                    continue
+                dev, bo = np.abs(X[ran, :, i] - out["nominal_trajectory_x"][ran, :, 0, i]), out["backoff_trajectory_x"][ran, :, k, i]
+                r = dev / bo
+                per.append(r.max(axis=1))      # (NaN / inf where the plant has diverged: counted below)
+                r = np.where(np.isfinite(r), r, -1.0)
+                if at is None or r.max() > at["ratio"]:
+                    bi, c = np.unravel_index(np.argmax(r), r.shape)
+                    at = dict(ratio=float(r[bi, c]), instance=int(ran[bi]), step=int(i), k=int(k), component=int(c), deviation=float(dev[bi, c]), backoff=float(bo[bi, c]))
+            per = np.concatenate(per)
+            rec["tube_nonfinite"] = int(np.sum(~np.isfinite(per)))      # (instance, hold step) pairs of a plant that has diverged to inf / NaN
+            per = per[np.isfinite(per)]
+            rec.update(tube_ratio_max=float(per.max()), tube_ratio_p50=float(np.median(per)), tube_ratio_p99=float(np.quantile(per, 0.99)),
+                       tube_exceeded=float(np.mean(per > 1.0)), tube_ratio_at=at, policy_ran=float(out["hold_policy"][:, ~solved].mean()), inside_box_hold_steps=float(inside[:, ~solved].mean()),
+                       inside_box_solved_steps=float(inside[:, solved].mean()))
+        print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()
