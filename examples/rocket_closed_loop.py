@@ -11,7 +11,8 @@ nominal NLP on the GPU (slsqp_nominal_solve, trust-region SCP from a hover roll-
 `--plant-scale NAME=FACTOR` (repeatable) and `--plant-spread PCT` make the TRUE plant differ from the controller's model: a rocket that is heavier,
 a servo that is slower, every parameter of seed s uniform within +-PCT % of its default.  The run then reports how often the model error plus the
 noise left the disturbance box the tubes were designed for (`disturbance_used` > 1) and the constraint violations of the measured states.
-`--solve-every M` runs the controller at 1/M of the plant's rate: a solve at steps 0, M, 2M, ..., the tube's feedback policy in between.
+`--solve-every M` runs the controller at 1/M of the plant's rate: a solve at steps 0, M, 2M, ..., the tube's feedback policy in between; with
+`--persistent 1` the hold steps run inside the persistent launch (one launch for the whole loop), without it the loop is stepped.
 """
 import argparse
 import os
@@ -43,6 +44,8 @@ def main():
                     help="every parameter of the true plant of seed s uniform within +-PCT %% of its default, drawn from a generator seeded with s (gimbal lengths excluded)")
     ap.add_argument("--solve-every", type=int, default=1, metavar="M",
                     help="the controller solves at steps 0, M, 2M, ... and holds its plan in between, the tube's feedback policy acting on the measured state (1 <= M <= N)")
+    ap.add_argument("--persistent", type=int, default=None, choices=(0, 1), metavar="0|1",
+                    help="1: the persistent launch wherever the setting allows it, --solve-every M > 1 included; 0: never; default: the plant's default, and a stepped loop for M > 1")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model("rocket")
@@ -54,7 +57,8 @@ def main():
     x0 = m.x_ref + a.x0_scale * (m.extra["x0"] - m.x_ref)
     t0 = time.perf_counter()
     r = run_monte_carlo(m, a.N, np.arange(a.seeds), a.steps, x0, solve_nominal=(a.init == "sqp"), slices=a.slices, continuation=a.continuation,
-                        budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P, solve_every=a.solve_every)
+                        budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P, solve_every=a.solve_every,
+                        persistent=None if a.persistent is None else bool(a.persistent))
     dt = time.perf_counter() - t0
     ok = r["success"]
     if "nlp_status" in r:

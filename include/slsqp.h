@@ -283,8 +283,16 @@ int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc, const slsq
    zero; hold_policy[int32] (1) of the last hold step: 1 the policy ran, 0 the nominal input was applied; u0, x_meas, model_err as after
    slsqp_cl_step.  With slsqp_cl_log: log_hold[int32] (S) 0 for a solved step, k for hold step k; log_hold_policy[int32] (S); the entry's log_state and
    log_u0 are the measured state and the applied input, log_nominal_* the shifted plan, log_backoff_* and log_success the last solve's,
-   log_scp_iterations 0 and log_x0_viol 0. */
+   log_scp_iterations 0 and log_x0_viol 0.
+   The call does not read slsqp_cl_set_solve_every: a step-by-step caller decides itself which of its steps are solves.  The same hold step runs
+   inside the persistent launch of slsqp_cl_run for a handle with solve_every > 1 (below); after such a run the call is still refused until a
+   slsqp_cl_step. */
 int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc);
+/* M of slsqp_cl_run: the controller of every instance solves at its steps 0, M, 2M, ... and holds its plan at the others (the hold step above).  A
+   property of the handle like x0_box_tol (slsqp_opts keeps its layout), default 1 = a solve at every step.  1 <= M <= N; anything else is refused
+   (< 0, slsqp_last_error) and changes nothing.  slsqp_cl_step and slsqp_cl_hold_step ignore it. */
+int slsqp_cl_set_solve_every(slsqp_handle *h, int M);
+int slsqp_cl_get_solve_every(slsqp_handle *h);
 /* The whole closed loop with the instances advancing INDEPENDENTLY (rti = 1, one fast-SLS step, fp64, fuse_rti: the rocket script's setting):
    `steps` MPC steps of every instance, W (steps,B,nx) disturbance samples or NULL.  Per instance the same operations in the same order as `steps`
    calls of slsqp_cl_step (identical results), but in rounds: in a round an instance begins its next MPC step or resumes the QP solve that the
@@ -293,7 +301,13 @@ int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc);
    No instance waits for the slowest one of its step.  Call after slsqp_cl_init (+ slsqp_nominal_solve); per-step results through the device-side
    log (slsqp_cl_log with max_steps >= steps, before slsqp_cl_init), `log_qp_stats`[int32] (steps,2,8) and `log_x0_viol` (steps,2), the per-step
    copies of qp_stats and x0_viol (0 where the QP took no part).  *rounds_out (may be NULL): rounds taken.
-   With opts.cl_persistent (the default) there are no rounds at all: see slsqp_opts. */
+   With opts.cl_persistent (the default) there are no rounds at all: see slsqp_opts.
+   slsqp_cl_set_solve_every with M > 1 (persistent launch only; the round-based loop refuses, as does slsqp_cl_run_scp for any setting but rti = 1 with
+   rti_steps = 1): step s of an instance with s % M != 0 is the hold step k = s % M of slsqp_cl_hold_step, run by the wave that holds the instance --
+   the same device functions in the same order as that call's launches, same bits as a step-by-step loop of slsqp_cl_step / slsqp_cl_hold_step.  A wave
+   that has solved for an instance runs its following hold steps at once, before the instance goes back to the queue.  The entry of `log_qp_stats`
+   of a hold step says "took no part": status -1 in both slots, 0 everywhere else.  With slsqp_cl_log the run fills log_hold and log_hold_policy;
+   afterwards hold_index, hold_policy, hold_xi and u0 hold the state after the last step.  With M = 1 the call launches exactly what it always did. */
 int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc, const slsqp_opts *opts, double budget_ms, double cut_frac, int *rounds_out);
 /* `steps` MPC steps of every instance as ONE persistent launch, for any SCP setting of slsqp_cl_step (SCP_SLS.solve, SCP_SLS_jit.py:103-135):
    rti > 0: exactly rti SCP iterations per MPC step; rti <= 0: converge mode (opts.scp_eps, opts.max_scp_iter), every instance leaving the loop at

@@ -56,7 +56,7 @@ EXPORTS = [
     "slsqp_last_timing", "slsqp_kernel_timing", "slsqp_stream", "slsqp_set_model", "slsqp_set_E", "slsqp_linearize", "slsqp_cl_init", "slsqp_cl_step", "slsqp_nominal_solve", "slsqp_set", "slsqp_cl_log", "slsqp_selftest", "slsqp_result_bytes", "slsqp_cl_run", "slsqp_cl_run_stats", "slsqp_cl_run_scp", "slsqp_set_x0_box_tol", "slsqp_get_x0_box_tol",
     "slsqp_set_solve_waves", "slsqp_get_solve_waves", "slsqp_ne_solve", "slsqp_cl_set_reference",
     "slsqp_plant_param_count", "slsqp_plant_param_name", "slsqp_plant_param_defaults", "slsqp_cl_set_plant_params", "slsqp_cl_set_bounds",
-    "slsqp_cl_hold_step",
+    "slsqp_cl_hold_step", "slsqp_cl_set_solve_every", "slsqp_cl_get_solve_every",
 ]
 
 _lib = None
@@ -109,6 +109,8 @@ def load():
     lib.slsqp_cl_init.argtypes = [vp, dp, dp, dp, dp, C.c_int]
     lib.slsqp_cl_step.argtypes = [vp, C.c_int, dp, C.c_int, C.POINTER(Opts)]
     lib.slsqp_cl_hold_step.argtypes = [vp, dp, C.c_int]
+    lib.slsqp_cl_set_solve_every.argtypes = [vp, C.c_int]
+    lib.slsqp_cl_get_solve_every.argtypes = [vp]
     lib.slsqp_nominal_solve.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.POINTER(Opts)]
     lib.slsqp_cl_log.argtypes = [vp, C.c_int]
     lib.slsqp_cl_run.argtypes = [vp, C.c_int, dp, C.c_int, C.POINTER(Opts), C.c_double, C.c_double, C.POINTER(C.c_int)]

@@ -225,7 +225,7 @@ class ClosedLoopMPC:
                 wm[:, i] += w
         return np.max(np.abs(wm), axis=2).T.copy()
 
-    def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0, solve_every=None):
+    def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0, solve_every=None, persistent_hold=False):
         """Same results as run_on_device() -- bit for bit -- with the instances advancing through their MPC steps independently, so nobody waits for
         the slowest instance of a step.
         rti = 1 with one fast-SLS step (the rocket script's setting): slsqp_cl_run.  With opts.cl_persistent (the default) the whole loop is ONE launch:
@@ -234,15 +234,29 @@ class ClosedLoopMPC:
         Every other setting slsqp_cl_step takes with a fixed number of fast-SLS steps (rti > 1, SCP converge mode rti <= 0, rti_steps > 1: the
         pendulum and quadrotor scripts, SCP_SLS's default): slsqp_cl_run_scp, always one persistent launch (budget_ms / cut_frac ignored).  Fast-SLS
         converge mode (fast_sls_rti_steps None), precision = 1 and SLSQP_FUSE_RTI=0 are refused with the library's message.
-        solve_every = M > 1 (None: the constructor's): the persistent kernels solve at every step, so the run takes the step-by-step loop (run_on_device), as
-        it does for solve_waves > 1.
+        solve_every = M > 1 (None: the constructor's): by default the run takes the step-by-step loop (run_on_device), as it does for solve_waves > 1.
+        persistent_hold=True runs it as the persistent launch instead, the hold steps of an instance inside the loop of the wave that solved for it
+        (BatchedFastSLS.set_solve_every; rti = 1 with one fast-SLS step and opts.cl_persistent only, every other setting raises with the library's
+        message): the same bits, what a persistent run returns, plus `hold_index` and `hold_policy`.
         Adds `qp_stats` (B, steps, 2, 8) (next to `x0_violation` (B, steps, 2), which every logged run has), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the run's totals in their first entry."""
         f, m, N, B = self.f, self.m, self.N, self.B
         M = self._check_solve_every(solve_every)
-        if f.opts.solve_waves > 1 or M > 1:      # the persistent kernels are one wave per instance and solve at every step: the same loop, step by step (no qp_stats / loop_stats)
+        hold = M > 1 and persistent_hold
+        if f.opts.solve_waves > 1 or (M > 1 and not hold):      # the persistent kernels are one wave per instance; M > 1 without persistent_hold: the same loop, step by step (no qp_stats / loop_stats)
             out = self.run_on_device(x0, steps, W, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation, solve_every=M)
             out["rounds"] = steps
             return out
+        if hold and not (self.rti == 1 and f.opts.rti_steps == 1):      # (asked here, before anything is reset: the library's words)
+            raise RuntimeError(f"slsqp: slsqp_cl_run_scp: solve_every = {M} needs rti = 1 with one fast-SLS step (slsqp_cl_run's kernel): the general "
+                               "persistent loop keeps its gains per SCP iteration and solves at every step (use slsqp_cl_step / slsqp_cl_hold_step)")
+        f.set_solve_every(M if hold else 1)
+        try:
+            return self._run_persistent(x0, steps, W, X_nom, U_nom, solve_nominal, continuation, budget_ms, cut_frac, hold)
+        finally:
+            f.set_solve_every(1)      # (the handle's M is this call's: the next run says what it wants)
+
+    def _run_persistent(self, x0, steps, W, X_nom, U_nom, solve_nominal, continuation, budget_ms, cut_frac, hold):
+        f, m, N, B = self.f, self.m, self.N, self.B
         L.check(f.lib.slsqp_cl_log(f.h, int(steps)))
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
         Wc = None if W is None else _c(W)
@@ -266,6 +280,8 @@ class ClosedLoopMPC:
             st = (C.c_double * L.CL_RUN_STATS_LEN)()
             L.check(f.lib.slsqp_cl_run_stats(f.h, st, L.CL_RUN_STATS_LEN))
             out["loop_stats"] = dict(waves=int(st[0]), busy_ms=float(st[1]), mpc_steps=int(st[2]), launch_ms=float(st[3]))
+        if hold:
+            out.update(hold_index=f.get("log_hold", (steps,), np.int32), hold_policy=f.get("log_hold_policy", (steps,), np.int32).astype(bool))
         return out
 
     def run(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, solve_every=None):

@@ -8,7 +8,20 @@
 #define SLSQP_CL_HOLD_HPP
 #include <string>
 
+#ifdef __HIPCC__
+#define CL_HOLD_HD __host__ __device__
+#else
+#define CL_HOLD_HD
+#endif
+
 namespace cl_hold {
+
+// The schedule of a run that solves every M-th step (slsqp_cl_set_solve_every): step s = 0, 1, ... of a run is a solve when
+// hold_index_at is 0 and else the hold step of that index since the last solve.  One definition for the host and for the persistent kernel.
+CL_HOLD_HD inline bool valid_solve_every(int M, int N) { return M >= 1 && M <= N; }      // K has N rows: at most N - 1 hold steps between two solves
+CL_HOLD_HD inline int hold_index_at(int step, int M) { return M > 1 ? step % M : 0; }
+CL_HOLD_HD inline bool is_solve(int step, int M) { return hold_index_at(step, M) == 0; }
+inline int solves_in(int steps, int M) { return steps <= 0 ? 0 : (steps + M - 1) / M; }      // solves among the steps 0 .. steps - 1
 
 struct State {
     int k = 0;              // index of the last hold step (1 = the first plant step after a solve)
@@ -17,7 +30,8 @@ struct State {
 };
 
 inline void on_init(State &s) { s = State{}; }
-inline void on_run(State &s, int cl_steps_after) { s.run_steps = cl_steps_after; }
+// k_last > 0: the run's last step was the hold step of that index (a persistent run with solve_every > 1): "hold_index" serves it
+inline void on_run(State &s, int cl_steps_after, int k_last = 0) { s.run_steps = cl_steps_after; if (k_last > 0) { s.k = k_last; s.at_steps = cl_steps_after; } }
 inline void on_hold(State &s, int k, int cl_steps_after) { s.k = k; s.at_steps = cl_steps_after; }
 // "hold_index": hold steps since the last solve
 inline int index(const State &s, int cl_steps) { return cl_steps == s.at_steps ? s.k : 0; }

@@ -34,14 +34,21 @@ struct HoldArgs {
 // y = K[k-1,j] xi_j on the group's first NU lanes, then A xi_j + B y; A_{k-1}, B_{k-1} and the columns are read from global memory once, coalesced,
 // into LDS.  New column and the sum over the columns: lane i = row i.  Policy sum: lane j forms K[k,j] xi_j (k <= 63 columns), the NU sums go
 // through the crossbar.  Plant step: lane 0, the function the solved steps use, with u in the place of the first nominal input.
-template <int MODEL, bool PP>
-__global__ __launch_bounds__(64) void k_cl_hold(HoldArgs a, PlantArgs pa) {
+//
+// The work is written once, for one wave and one instance, and has two callers: k_cl_hold below (one block per instance, slsqp_cl_hold_step) and the
+// hold path of the persistent closed-loop kernel (k_cl_loop's HOLD variants), which passes its dynamic LDS.
+template <int MODEL>
+constexpr int cl_hold_lds_doubles() {      // sA | sB | sXi | sY
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    return NX * NX + NX * NU + 64 * NX + (64 / NX) * NU;
+}
+// xi, u and policy of hold step k of instance b (a.k is not read); ends with u in global memory for every lane of the wave
+template <int MODEL>
+__device__ __forceinline__ void cl_hold_wave(const HoldArgs &a, int b, int lane, int k, double *sm) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU, G = 64 / NX;
     static_assert(NU <= NX && G >= 1, "row i of y lives on lane i of a column's group");
-    __shared__ double sA[NX * NX], sB[NX * NU], sXi[64 * NX], sY[G * NU];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    if (b >= a.cl.B) return;
-    const int N = a.cl.N, k = a.k;
+    double *sA = sm, *sB = sA + NX * NX, *sXi = sB + NX * NU, *sY = sXi + 64 * NX;
+    const int N = a.cl.N;
     double *xi = a.xi + (size_t)b * (N + 1) * NX;
     const double *Un0 = a.cl.Un + (size_t)b * N * NU;
     const bool ok = a.scp_success[b] != 0;
@@ -110,13 +117,28 @@ __global__ __launch_bounds__(64) void k_cl_hold(HoldArgs a, PlantArgs pa) {
     }
     if (lane == 0) a.policy[b] = ok ? 1 : 0;
     wla::wsync_mem();      // u is in global memory for lane 0's plant step and for the log
-    if (a.S > 0 && a.step < a.S) {      // state and applied input of this step; no solve: 0 iterations, nothing on record for the stage-0 gate
-        const size_t e = (size_t)b * a.S + a.step;
+}
+// entry `step` of the closed-loop log as a hold step leaves it (a.S = 0: no log; a.step is not read): state and applied input of this step; no
+// solve: 0 iterations, nothing on record for the stage-0 gate
+template <int MODEL>
+__device__ __forceinline__ void cl_hold_log(const HoldArgs &a, int b, int lane, int k, int step) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    if (a.S > 0 && step < a.S) {
+        const bool ok = a.scp_success[b] != 0;
+        const size_t e = (size_t)b * a.S + step;
         if (lane < NX) a.lstate[e * NX + lane] = a.cl.xmeas[(size_t)b * NX + lane];
         if (lane < NU) a.lu0[e * NU + lane] = a.u[(size_t)b * NU + lane];
         if (lane == 0) { a.lit[e] = 0; a.lhold[e] = k; a.lpol[e] = ok ? 1 : 0; a.lx0v[e * 2] = 0.0; a.lx0v[e * 2 + 1] = 0.0; }
         wla::wsync_mem();      // the state is logged before lane 0 replaces it
     }
+}
+template <int MODEL, bool PP>
+__global__ __launch_bounds__(64) void k_cl_hold(HoldArgs a, PlantArgs pa) {
+    __shared__ double sm[cl_hold_lds_doubles<MODEL>()];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= a.cl.B) return;
+    cl_hold_wave<MODEL>(a, b, lane, a.k, sm);
+    cl_hold_log<MODEL>(a, b, lane, a.k, a.step);
     if (lane == 0) {
         ClArgs c = a.cl;
         c.N = 1; c.Un = a.u;      // "the first nominal input" of instance b is u[b]: the nominal itself stays the plan

@@ -76,6 +76,8 @@ struct slsqp_handle {
     int *qpstat;                // (B,2,8) per-QP statistics, see QpArgs::qpstat
     double *x0viol;             // (B,2) largest stage-0 violation of the instance's last first / last QP: part of the kkt allocation (x0_record, slsqp_kernels.hpp)
     double x0_box_tol = 0.0;    // slsqp_set_x0_box_tol: the tolerance the following launches ask for
+    int solve_every = 1;        // slsqp_cl_set_solve_every: M of slsqp_cl_run -- a solve at steps 0, M, 2M, ... of every instance, hold steps in between (1: a solve at every step)
+    std::vector<unsigned char> hold_blk_host;      // the HoldLoopArgs the host last wrote behind the ScpLoopArgs of loop_blk (runs with solve_every > 1 only)
     int solve_waves = 1;        // slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = k_qp_solve_mw (one workgroup of that many waves per instance)
     double *ref_Y = nullptr; int ref_T = 0; size_t ref_stride = 0;      // slsqp_cl_set_reference: packed rows [x_ref; u_ref] (T, nz), per instance with ref_stride = T nz, shared with 0; ref_T = 0: none
     double *zero_ref = nullptr;      // (nz) zeros: the one-row reference the persistent kernels take for a handle with parameters or bounds and no reference (cl_options)
@@ -117,20 +119,23 @@ struct slsqp_handle {
 
 // The per-handle closed-loop options.  The persistent kernels' variant VAR is a set of these bits; the instantiated sets are
 // the five of with_loop_var: an option that needs the tracked cost's code path (parameters, bounds) carries the REF bit, and a handle without a
-// reference then passes one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference.
-constexpr int VAR_REF = 1, VAR_PP = 2, VAR_BND = 4;
+// reference then passes one row of zeros, which tests/test_gpu_reference.py holds to be the bits of no reference.  HOLD (slsqp_cl_set_solve_every
+// with M > 1) comes with REF too and exists for k_cl_loop only: the sets 9, 11, 13, 15.
+constexpr int VAR_REF = 1, VAR_PP = 2, VAR_BND = 4, VAR_HOLD = 8;
 constexpr bool var_ref(int VAR) { return VAR & VAR_REF; }
 constexpr bool var_pp(int VAR) { return VAR & VAR_PP; }
 constexpr bool var_bnd(int VAR) { return VAR & VAR_BND; }
+constexpr bool var_hold(int VAR) { return VAR & VAR_HOLD; }
 // What a handle has set, asked by every launch site: ref / pp / bnd are the handle's own (the flags of the batch-wide kernels: REF and BND of k_lin_vec
 // and k_nom_eval, BND of k_tighten and k_rti_chain, pp for the plant step) and own_rf the handle's own reference, empty without one (what those two
 // kernels take); var, rf, pa are what the persistent kernels take (rf: own_rf, else the zero row where var has the REF bit, else empty; pa: empty
-// without parameters).
-struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; };
+// without parameters).  hold: the handle's solve_every is above 1 (read by slsqp_cl_run alone: slsqp_cl_step and slsqp_cl_hold_step ignore the setting).
+struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; bool hold; };
 static ClOptions cl_options(const slsqp_handle *h) {
     ClOptions o{};
     o.ref = h->ref_T > 0; o.pp = h->pp_P != nullptr; o.bnd = h->bnd_rows != nullptr;
-    o.var = ((o.ref || o.pp || o.bnd) ? VAR_REF : 0) | (o.pp ? VAR_PP : 0) | (o.bnd ? VAR_BND : 0);
+    o.hold = h->solve_every > 1;
+    o.var = ((o.ref || o.pp || o.bnd || o.hold) ? VAR_REF : 0) | (o.pp ? VAR_PP : 0) | (o.bnd ? VAR_BND : 0) | (o.hold ? VAR_HOLD : 0);
     if (o.ref) o.own_rf = RefArgs{h->ref_Y, h->ref_T, h->ref_stride};
     o.rf = (o.var && !o.ref) ? RefArgs{h->zero_ref, 1, 0} : o.own_rf;
     if (o.pp) o.pa = PlantArgs{h->pp_P, h->pp_stride, h->pp_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps};
@@ -149,9 +154,16 @@ static bool dispatch3(int i, F &&f) {
     }
     return false;
 }
-// the same among the instantiated variants of the persistent kernels
+// the same among the instantiated variants of the persistent kernels; hold_sets: those of k_cl_loop alone as well (f then guards what it
+// instantiates with var_hold(V()))
 template <class F>
-static bool with_loop_var(int var, F &&f) {
+static bool with_loop_var(int var, F &&f, bool hold_sets = false) {
+    if (hold_sets) switch (var) {
+    case VAR_HOLD | VAR_REF: f(std::integral_constant<int, VAR_HOLD | VAR_REF>{}); return true;
+    case VAR_HOLD | VAR_REF | VAR_PP: f(std::integral_constant<int, VAR_HOLD | VAR_REF | VAR_PP>{}); return true;
+    case VAR_HOLD | VAR_REF | VAR_BND: f(std::integral_constant<int, VAR_HOLD | VAR_REF | VAR_BND>{}); return true;
+    case VAR_HOLD | VAR_REF | VAR_PP | VAR_BND: f(std::integral_constant<int, VAR_HOLD | VAR_REF | VAR_PP | VAR_BND>{}); return true;
+    }
     switch (var) {
     case 0: f(std::integral_constant<int, 0>{}); return true;
     case VAR_REF: f(std::integral_constant<int, VAR_REF>{}); return true;
@@ -859,10 +871,19 @@ struct ScpLoopArgs {
     int *nsolves;
     BndArgs bd;      // slsqp_cl_set_bounds (the variants with VAR_BND only; behind everything else, so no other field moves)
 };
+// What the HOLD variants of k_cl_loop read besides: the arguments of the hold function (a.k and a.step are not read: every
+// instance is at its own step) and M.  It lies in the same device block BEHIND the ScpLoopArgs, at HOLD_BLK_OFFSET: ScpLoopArgs keeps its size and
+// every offset (bd stays its last field, tests/loop_args_check_main.cpp), and a run with M = 1 writes and reads the bytes it always did.
+struct HoldLoopArgs { HoldArgs a; int M; };
+constexpr size_t HOLD_BLK_OFFSET = (sizeof(ScpLoopArgs) + 15) & ~(size_t)15, LOOP_BLK_BYTES = 4096;
+static_assert(HOLD_BLK_OFFSET + sizeof(HoldLoopArgs) <= LOOP_BLK_BYTES, "slsqp_handle::loop_blk is 4096 bytes");
+__device__ __forceinline__ const HoldLoopArgs *hold_blk(const ScpLoopArgs *blk) { return (const HoldLoopArgs *)((const unsigned char *)blk + HOLD_BLK_OFFSET); }
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
-template <int MODEL, bool REF = false, bool BND = false>
-__device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const RefArgs *rf = nullptr, const BndArgs *bd = nullptr) {
+// HOLD (k_cl_loop's hold variants): held != 0 is a hold step of the instance, which takes the shift alone -- no solver reset, so stale, itnum, q
+// and call_ids stay and K stays valid; the rest of the hold step is cl_step_end's
+template <int MODEL, bool REF = false, bool BND = false, bool HOLD = false>
+__device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const RefArgs *rf = nullptr, const BndArgs *bd = nullptr, int held = 0) {
     const LoopArgs *Lp = &L_;
     const LoopArgs &L = args_here<true>(Lp);
     constexpr int NX = dyn::Dims<MODEL>::NX;
@@ -877,6 +898,7 @@ __device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const 
     // reset_warm_start (shift + solver reset) past the first step, call id, flags
     if (s > 0) {
         cl_shift_wave<MODEL>(L.cl, b, lane);
+        if constexpr (HOLD) { if (held) return; }
         for (int o = lane; o < L.n; o += 64) L.q[(size_t)b * L.n + o] = 0.0;
         const int st = L.stale[b];
         wla::wsync_mem();
@@ -894,8 +916,12 @@ __device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const 
     CLSTAMP(6);
 }
 // nominal += delta, primal infeasibility, log entry, plant + noise, step counter; returns the instance's new step count while it has steps left, else 0
-template <int MODEL, bool PP = false>
-__device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const PlantArgs *pa = nullptr) {
+// HOLD: at a step s of the instance that is no solve (cl_hold::hold_index_at(s, M) = k > 0; cl_step_begin has shifted the plan) the stages of
+// slsqp_cl_hold_step's launches in their order instead -- the log items of the entry (the shifted plan, the last solve's back-offs and success), the
+// hold function (xi, the policy's input u, hold_policy) in the LDS `sm`, the log fields k_cl_hold writes, "took no part" as the entry of log_qp_stats --
+// and then the SAME plant step, one call site, with u in the place of the first nominal input
+template <int MODEL, bool PP = false, bool HOLD = false>
+__device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const PlantArgs *pa = nullptr, const HoldLoopArgs *hp = nullptr, double *sm = nullptr) {
     const LoopArgs *Lp = &L_;
     const LoopArgs &L = args_here<true>(Lp);
     constexpr int NX = dyn::Dims<MODEL>::NX;
@@ -903,21 +929,46 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
 #ifdef CL_LOOP_STAMP
     unsigned long long ts_ = wall_clock64();
 #endif
-    if (lane == 0) L.scp_active[b] = 1;
-    wla::wsync_mem();
-    cl_scp_update_wave(L.cl, L.sa, b, lane);
-    wla::wsync_mem();
-    CLSTAMP(7);
-    if (L.sa.updated[b]) cl_infeas_wave<MODEL>(L.cl, L.pinf, b, lane);
-    wla::wsync_mem();
-    CLSTAMP(8);
-    if (L.have_log) {
-        const int per = 2 * ((L.lg.N + 1) * L.lg.NX + L.lg.N * L.lg.NU);
-        for (int o = lane; o < per; o += 64) cl_log_item(L.lg, b, o);
+    bool held = false;
+    if constexpr (HOLD) {
+        const HoldLoopArgs &H = args_here<true>(hp);
+        const int k = cl_hold::hold_index_at(s, H.M);
+        if (k) {
+            held = true;
+            if (L.have_log) {
+                const int per = 2 * ((L.lg.N + 1) * L.lg.NX + L.lg.N * L.lg.NU);
+                for (int o = lane; o < per; o += 64) cl_log_item(L.lg, b, o);
+                wla::wsync_mem();      // (lu0 of the entry is written again below, by other lanes)
+            }
+            cl_hold_wave<MODEL>(H.a, b, lane, k, sm);
+            cl_hold_log<MODEL>(H.a, b, lane, k, s);
+            if (L.c.qplog && s < L.c.log_steps) {      // no QP took part in this step: status -1 in both slots, 0 everywhere else, no stage-0 record
+                if (lane < 16) L.c.qplog[((size_t)b * L.c.log_steps + s) * 16 + lane] = (lane & 7) == 6 ? -1 : 0;
+                if (lane >= 16 && lane < 18) L.c.x0vlog[((size_t)b * L.c.log_steps + s) * 2 + (lane - 16)] = 0.0;
+            }
+        }
+    }
+    if (!held) {
+        if (lane == 0) L.scp_active[b] = 1;
+        wla::wsync_mem();
+        cl_scp_update_wave(L.cl, L.sa, b, lane);
+        wla::wsync_mem();
+        CLSTAMP(7);
+        if (L.sa.updated[b]) cl_infeas_wave<MODEL>(L.cl, L.pinf, b, lane);
+        wla::wsync_mem();
+        CLSTAMP(8);
+        if (L.have_log) {
+            const int per = 2 * ((L.lg.N + 1) * L.lg.NX + L.lg.N * L.lg.NU);
+            for (int o = lane; o < per; o += 64) cl_log_item(L.lg, b, o);
+        }
     }
     CLSTAMP(9);
     if (lane == 0) {
-        cl_plant_one<MODEL, PP>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
+        if constexpr (HOLD) {
+            ClArgs c = L.cl;
+            if (held) { c.N = 1; c.Un = args_here<true>(hp).a.u; }      // "the first nominal input" of instance b is u[b], as in k_cl_hold: the nominal itself stays the plan
+            cl_plant_one<MODEL, PP>(c, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
+        } else cl_plant_one<MODEL, PP>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
         L.stepno[b] = s + 1;
         if (L.busy) { atomicAdd(L.busy, wall_clock64() - L.t_begin[b]); atomicAdd(L.busy + 2, 1ULL); }
     }
@@ -931,6 +982,8 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
 // tightened row read blk->bd).  PP and BND come with REF only (1, 3, 5, 7: a handle without a reference passes one row of zeros).  A variant is passed
 // empty rf / pa where it reads none.  The three calls that name VAR, through var_ref / var_pp / var_bnd, are all that depends on it.  The statements
 // stand in the kernel, not in a function it calls, and the next per-handle option is a further VAR bit, not a further kernel (DESIGN.md sections 14, 16).
+// HOLD (9, 11, 13, 15; slsqp_cl_set_solve_every): the instance solves at its steps 0, M, 2M, ... only; at the others the loop
+// body runs the shift of cl_step_begin, no chain, and the hold path of cl_step_end.  Every statement HOLD adds is under if constexpr (var_hold(VAR)).
 template <int MODEL, int VAR>
 __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
@@ -956,15 +1009,22 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const
             if (lane == 0) atomicAdd(L.busy + 11, wall_clock64() - tp_);
 #endif
         }
-        cl_step_begin<MODEL, var_ref(VAR), var_bnd(VAR)>(L, b, lane, var_ref(VAR) ? &rf : nullptr, var_bnd(VAR) ? &blk->bd : nullptr);
+        bool solve = true;      // HOLD: the instance's step is a solve or a hold step (read again in cl_step_end: nothing of it is live across the chain)
+        if constexpr (var_hold(VAR)) solve = __builtin_amdgcn_readfirstlane(cl_hold::hold_index_at(L.stepno[b], args_here<true>(hold_blk(blk)).M)) == 0;
+        cl_step_begin<MODEL, var_ref(VAR), var_bnd(VAR), var_hold(VAR)>(L, b, lane, var_ref(VAR) ? &rf : nullptr, var_bnd(VAR) ? &blk->bd : nullptr, solve ? 0 : 1);
         b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
         asm volatile("" : "+v"(lane));
-        rti_chain_dev<NX, NU, true, var_bnd(VAR)>(L.c, b, lane, sm, var_bnd(VAR) ? &blk->bd : nullptr);
-        wla::wsync_mem();
+        if (solve) {
+            rti_chain_dev<NX, NU, true, var_bnd(VAR)>(L.c, b, lane, sm, var_bnd(VAR) ? &blk->bd : nullptr);
+            wla::wsync_mem();
+        }
         asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, var_pp(VAR)>(L, b, lane, var_pp(VAR) ? &pa : nullptr));
+        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, var_pp(VAR), var_hold(VAR)>(L, b, lane, var_pp(VAR) ? &pa : nullptr, var_hold(VAR) ? hold_blk(blk) : nullptr, sm));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
+        // HOLD: the hold steps that follow a solve (at most M - 1, fewer at the end of the run) run at once on this wave, without a queue round trip;
+        // the tail below then sees the step count the instance has reached
+        if constexpr (var_hold(VAR)) { if (!cl_hold::is_solve(next, args_here<true>(hold_blk(blk)).M)) continue; }
         const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
         // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
         // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
@@ -2213,9 +2273,19 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     return 0;
 }
 
+// M of slsqp_cl_run (and of slsqp_cl_run_scp where it forwards to slsqp_cl_run's kernel): a property of the handle like x0_box_tol, default 1.
+// 1 <= M <= N (K has N rows); anything else is refused and changes nothing.  slsqp_cl_step and slsqp_cl_hold_step do not read it.
+extern "C" int slsqp_cl_set_solve_every(slsqp_handle *h, int M) {
+    if (!cl_hold::valid_solve_every(M, h->d.N)) return fail("slsqp_cl_set_solve_every: M = " + std::to_string(M) + " outside 1 .. N = " + std::to_string(h->d.N) + " (K has N rows: at most N - 1 hold steps between two solves)");
+    h->solve_every = M;
+    return 0;
+}
+extern "C" int slsqp_cl_get_solve_every(slsqp_handle *h) { return h->solve_every; }
+
 // One closed-loop step WITHOUT a solve: the one-stage shift slsqp_cl_step applies at its top, then k_cl_hold -- the tube policy
 // of the last solve on the measured state, and the plant step.  No slsqp_reset (K stays valid); slsqp_cl_step is not involved and finds, at its next
-// call, a nominal whose stage 0 is the plan's prediction of where the plant is.
+// call, a nominal whose stage 0 is the plan's prediction of where the plant is.  The handle's solve_every is not read here: the caller decides which of
+// its steps are solves.  (The persistent launch runs the same stages per instance: cl_step_begin / cl_step_end with HOLD.)
 static int ensure_hold(slsqp_handle *h) {
     if (h->hold_xi) return 0;
     const size_t nxi = (size_t)h->B * (h->d.N + 1) * h->d.nx, nu = (size_t)h->B * h->d.nu;
@@ -2265,7 +2335,10 @@ __global__ void k_cl_begin_flags(int B, const int *begin, int *scp_success, int 
 template <int MODEL>
 static int launch_loop_t(slsqp_handle *h, bool S) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
-    const size_t lds = chain_lds_bytes<NX, NU>(h);
+    const ClOptions op = cl_options(h);      // (the bounds themselves are in the block: make_loop_block)
+    // (HOLD: the hold function works in the same dynamic LDS -- the larger of the two sizes; which one binds per model: DESIGN.md section 20)
+    const size_t lds = op.hold ? std::max(chain_lds_bytes<NX, NU>(h), sizeof(double) * (size_t)cl_hold_lds_doubles<MODEL>()) : chain_lds_bytes<NX, NU>(h);
+    if (op.hold && S) return fail("no persistent closed-loop kernel for solve_every > 1 with several SCP iterations or fast-SLS steps per MPC step");
     int cu = 0;
     if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, h->dev) != hipSuccess || cu <= 0) cu = 256;
     const int env_waves = getenv("SLSQP_LOOP_WAVES") ? atoi(getenv("SLSQP_LOOP_WAVES")) : 0;      // (tests / experiments: fewer waves than the GPU holds)
@@ -2273,14 +2346,14 @@ static int launch_loop_t(slsqp_handle *h, bool S) {
     const int grid = std::max(1, std::min(h->B, slots));
     h->cl_loop_waves = grid;
     const ScpLoopArgs *blk = (const ScpLoopArgs *)h->loop_blk;
-    const ClOptions op = cl_options(h);      // (the bounds themselves are in the block: make_loop_block)
     bool found = false;
     timed_launch(h, [&] {
         hipEventRecord(h->ev[8], h->st);
         found = with_loop_var(op.var, [&](auto V) {
-            if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of chain_lds_bytes)
+            if constexpr (var_hold(V())) hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);      // (k_cl_loop only: refused above for S)
+            else if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of chain_lds_bytes)
             else hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);
-        });
+        }, /* hold_sets */ !S);
         hipEventRecord(h->ev[9], h->st);
     });
     if (!found) return fail("no persistent closed-loop kernel for variant " + std::to_string(op.var));
@@ -2329,6 +2402,26 @@ static int write_loop_block(slsqp_handle *h, const ScpLoopArgs &S) {
     HIPCHK(hipMemcpyAsync(h->loop_blk, h->loop_blk_host.data(), sizeof S, hipMemcpyHostToDevice, h->st));
     return 0;
 }
+// what the HOLD variants read behind it (no HIP call in here; the buffers are ensure_hold's): the HoldArgs slsqp_cl_hold_step passes, with the log
+// of a run -- every instance at its own entry -- and M
+static HoldLoopArgs make_hold_block(slsqp_handle *h) {
+    HoldLoopArgs H;
+    memset(&H, 0, sizeof H);
+    HoldArgs &a = H.a;
+    a.cl = cl_args(h, nullptr);
+    a.A = h->A; a.Bm = h->Bm; a.K = h->K; a.Kc = h->Kc; a.stale = h->stale; a.scp_success = h->scp_success;
+    a.xi = h->hold_xi; a.u = h->hold_u; a.policy = h->hold_policy;
+    a.S = h->log_steps;
+    a.lstate = h->lg_state; a.lu0 = h->lg_u0; a.lx0v = h->lg_x0v; a.lit = h->lg_it; a.lhold = h->lg_hold; a.lpol = h->lg_hpol;      // (lx0v: the log's own buffer; the run's log_x0_viol is the block's x0vlog)
+    H.M = h->solve_every;
+    return H;
+}
+static int write_hold_block(slsqp_handle *h, const HoldLoopArgs &H) {
+    h->hold_blk_host.resize(sizeof H);
+    memcpy(h->hold_blk_host.data(), &H, sizeof H);
+    HIPCHK(hipMemcpyAsync(h->loop_blk + HOLD_BLK_OFFSET, h->hold_blk_host.data(), sizeof H, hipMemcpyHostToDevice, h->st));
+    return 0;
+}
 // scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp)
 static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out, bool scp = false, int scp_rti = 1) {
     const int max_it = !scp ? 1 : (scp_rti > 0 ? scp_rti : o.max_scp_iter);
@@ -2344,6 +2437,8 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     const ScpLoopArgs S = make_loop_block(h, steps, dW, o, scp, scp_rti);
     const LoopArgs &L = S.L;
     if (write_loop_block(h, S)) return -1;
+    const int M = scp ? 1 : h->solve_every;      // (slsqp_cl_run_scp has refused M > 1 for its own kernel)
+    if (M > 1 && (ensure_hold(h) || write_hold_block(h, make_hold_block(h)))) return -1;
     hipLaunchKernelGGL(k_clq_init, dim3(64), dim3(256), 0, h->st, B, L.Q);
     HIPCHK(hipMemsetAsync(h->cl_busy, 0, 16 * sizeof(unsigned long long), h->st));
     HIPCHK(hipMemsetAsync(h->cl_busy + 14, 0xFF, sizeof(unsigned long long), h->st));      // (CL_LOOP_STAMP builds: earliest wave start)
@@ -2370,8 +2465,8 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     if (ctl[3] != 0 || unfinished != 0)
         return fail("slsqp_cl_run (persistent): the instance queue did not drain (err " + std::to_string(ctl[3]) + ", " + std::to_string(unfinished) + " instances short of their steps)");
     h->cl_steps = steps;
-    cl_hold::on_run(h->hold, h->cl_steps);      // (no per-batch plan: slsqp_cl_hold_step refuses until a slsqp_cl_step)
-    h->call_id += (double)steps * max_it;
+    cl_hold::on_run(h->hold, h->cl_steps, cl_hold::hold_index_at(steps - 1, M));      // (no per-batch plan: slsqp_cl_hold_step refuses until a slsqp_cl_step; "hold_index": the last step's)
+    h->call_id += (double)cl_hold::solves_in(steps, M) * max_it;
     if (rounds_out) *rounds_out = 1;
     return 0;
 }
@@ -2430,6 +2525,8 @@ static int cl_run_prepare(slsqp_handle *h, int steps, const double *W, int loc, 
 // instance (50-90 block solves against a mean of 20: two thirds of a step's time is spent waiting for a few per cent of the instances); a round
 // lasts budget_ms at most, and ends earlier once cut_frac of its participants are done (0 < cut_frac < 1; the stragglers of a round then are cut as soon
 // as the bulk has finished, whatever time that took).  budget_ms <= 0: no time limit.  Results: the device-side log (slsqp_cl_log with max_steps >= steps), the final state, and log_qp_stats (steps, 2, 8).
+// slsqp_cl_set_solve_every with M > 1: the persistent launch runs k_cl_loop's HOLD variant -- steps 0, M, 2M, ... of an instance are solves, the others the
+// hold step of slsqp_cl_hold_step inside the loop of the wave that holds the instance; the rounds refuse.  M = 1: exactly the launches above.
 extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc, const slsqp_opts *opts, double budget_ms, double cut_frac, int *rounds_out) {
     hipSetDevice(h->dev);
     if (h->model_id < 0) return fail("slsqp_set_model must be called first");
@@ -2444,6 +2541,8 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         return fail("slsqp_cl_run needs the fused RTI chain: rti_steps = 1, fp64, fuse_rti = 1, box constraints (use slsqp_cl_step otherwise)");
     const int B = h->B, gbi = (B + 255) / 256, gb = (B + 63) / 64;
     const double *dW = nullptr;
+    if (h->solve_every > 1 && !o.cl_persistent)
+        return fail("slsqp_cl_run: solve_every = " + std::to_string(h->solve_every) + " runs in the persistent launch only (cl_persistent = 1): the round-based loop solves at every step (use slsqp_cl_step / slsqp_cl_hold_step)");
     if (cl_run_prepare(h, steps, W, loc, &dW)) return -1;
     if (o.cl_persistent) return cl_run_persistent(h, steps, dW, o, rounds_out);
     h->cl_budget = budget_ms > 0.0 ? (unsigned long long)(std::max(0.05, budget_ms) * 1e5) : (1ULL << 62);
@@ -2520,6 +2619,8 @@ extern "C" int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const doubl
     if (h->general_G) return fail("slsqp_cl_run_scp: box constraints only (general G: use the sweep-level boundary)");
     if (!(o.fuse_rti && chain_allowed() && sweep_shared_allowed())) return fail("slsqp_cl_run_scp needs the fused chain: fuse_rti = 1, SLSQP_FUSE_RTI and SLSQP_SWEEP_SHARED not 0 (use slsqp_cl_step otherwise)");
     if (rti <= 0 && o.max_scp_iter < 1) return fail("slsqp_cl_run_scp: converge mode needs max_scp_iter >= 1");
+    if (h->solve_every > 1 && !(rti == 1 && o.rti_steps == 1))
+        return fail("slsqp_cl_run_scp: solve_every = " + std::to_string(h->solve_every) + " needs rti = 1 with one fast-SLS step (slsqp_cl_run's kernel): the general persistent loop keeps its gains per SCP iteration and solves at every step (use slsqp_cl_step / slsqp_cl_hold_step)");
     const double *dW = nullptr;
     if (cl_run_prepare(h, steps, W, loc, &dW)) return -1;
     if (rti == 1 && o.rti_steps == 1) return cl_run_persistent(h, steps, dW, o, nullptr);

@@ -244,6 +244,15 @@ class BatchedFastSLS:
         assert wv is None or wv.shape == (self.B, self.m.nx)
         L.check(self.lib.slsqp_cl_hold_step(self.h, _ptr(wv), L.HOST))
 
+    def set_solve_every(self, M):
+        """M of the persistent closed loop (slsqp_cl_set_solve_every): slsqp_cl_run solves at steps 0, M, 2M, ... of every instance and runs hold
+        steps in between, inside its one launch.  1 <= M <= N, else refused with the handle unchanged; 1 (default): a solve at every step.
+        slsqp_cl_step and hold_step do not read it."""
+        L.check(self.lib.slsqp_cl_set_solve_every(self.h, int(M)))
+
+    def get_solve_every(self):
+        return int(self.lib.slsqp_cl_get_solve_every(self.h))
+
     def update_linear_cost(self, q):
         q = _c(q)
         assert q.shape == (self.B, self.n)

@@ -53,8 +53,10 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
     rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
     want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
-    if solve_every == 1 and budget_ms != 0 and want and can_run_persistent(cl.rti, rti_steps, cl.f.opts):      # instances advance independently (slsqp_cl_run / slsqp_cl_run_scp): same bits
-        out = cl.run_decoupled(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation, budget_ms=8.0 if budget_ms is None else budget_ms)
+    # solve_every > 1 inside the persistent launch: only when asked for (persistent=True), for rti = 1 with one fast-SLS step and the persistent variant
+    hold = solve_every > 1 and persistent is True and cl.rti == 1 and rti_steps == 1 and bool(cl.f.opts.cl_persistent) and solve_waves == 1
+    if (solve_every == 1 or hold) and budget_ms != 0 and want and can_run_persistent(cl.rti, rti_steps, cl.f.opts):      # instances advance independently (slsqp_cl_run / slsqp_cl_run_scp): same bits
+        out = cl.run_decoupled(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation, budget_ms=8.0 if budget_ms is None else budget_ms, persistent_hold=hold)
     else:
         out = cl.run_on_device(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation)
     if cl.nlp_status is not None:
@@ -84,7 +86,9 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     `constraint_margin` (steps, seeds) and `bounds_g` / `bounds_gf` as given.
     solve_every: M > 1 = every seed's controller solves at steps 0, M, 2M, ... and holds its plan in between, the tube policy of the last solve acting on
     the measured state (ClosedLoopMPC.hold_step; 1 <= M <= N); the loops then run step by step and the result holds `hold_index` and `hold_policy`
-    (seeds, steps).  1 (default): today's loops, unchanged.
+    (seeds, steps).  With persistent=True, where can_run_persistent and the setting allow (rti = 1 with one fast-SLS step, opts.cl_persistent), the
+    hold steps run inside the persistent launch instead (run_decoupled's persistent_hold): the same bits, plus `qp_stats`, `rounds`, `loop_stats`;
+    persistent=None keeps stepping.  1 (default): today's loops, unchanged.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading

@@ -2,7 +2,11 @@
 """What holding an MPC solution costs and keeps: the rocket closed loop of bench.py (N = 20, the script's x0, seed-s noise streams) through
 ClosedLoopMPC.run_on_device with a solve every M steps and the tube's feedback policy in between (slsqp_cl_hold_step).
 
-    python scripts/bench_hold.py [--batch 4096] [--steps 30] [--M 1 2 3 5] [--reps 5] [--root DIR]
+    python scripts/bench_hold.py [--batch 4096] [--steps 30] [--M 1 2 3 5] [--reps 5] [--root DIR] [--persistent]
+
+--persistent: the same loop as ONE persistent launch (ClosedLoopMPC.run_decoupled, for M > 1 with persistent_hold=True: the hold steps run inside the
+launch); the timed span is then reset's return to the launch's end (the upload of the noise samples included), and the line also
+holds `persistent`, `loop_stats` of the last run and `waves_busy` = busy_ms / (waves x launch's wall time), how busy the instance queue kept the waves.
 
 Per M, one JSON line:
   ms_per_step        median over --reps runs of the wall time of the loop (first slsqp_cl_step / slsqp_cl_hold_step to the last one's return; the
@@ -31,6 +35,7 @@ def main():
     ap.add_argument("--N", type=int, default=20)
     ap.add_argument("--M", type=int, nargs="+", default=[1, 2, 3, 5])
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--persistent", action="store_true", help="one persistent launch per run instead of one launch sequence per step")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose package is measured")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
@@ -60,7 +65,10 @@ def main():
         cl.reset, cl._log_result = timed_reset, timed_log_result
         runs, out = [], None
         for _ in range(a.reps + 1):      # (the first run warms the code objects and the allocator: not counted)
-            out = cl.run_on_device(x0, steps, W, X_nom, U_nom)
+            if a.persistent:
+                out = cl.run_decoupled(x0, steps, W, X_nom, U_nom) if M == 1 else cl.run_decoupled(x0, steps, W, X_nom, U_nom, persistent_hold=True)
+            else:
+                out = cl.run_on_device(x0, steps, W, X_nom, U_nom)
             runs.append(1e3 * (mark["t1"] - mark["t0"]) / steps)
         cl.close()
         runs = runs[1:]
@@ -69,6 +77,9 @@ def main():
         solved = np.arange(steps) % M == 0
         rec = dict(M=M, batch=B, N=N, steps=steps, nlp_ok=nlp_ok, ms_per_step=float(np.median(runs)), ms_per_step_runs=[round(r, 4) for r in runs],
                    solved_ok=float(out["success"][:, solved].mean()), inside_box=float(inside.mean()))
+        if a.persistent:
+            ls = out["loop_stats"]
+            rec.update(persistent=True, loop_stats=ls, waves_busy=float(ls["busy_ms"] / max(1e-9, ls["waves"] * runs[-1] * steps)))
         if M > 1:
             per, at = [], None
             for i in np.nonzero(~solved)[0]:
