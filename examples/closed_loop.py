@@ -11,6 +11,7 @@ fast_sls_rti_steps, step counts and (rocket) seed-s disturbance streams; B indep
     ... --plant-scale mass=1.15 --plant-spread 10                          # a true plant that differs from the controller's model (see --help)
     ... --model quadrotor --bound 5=-1.2:inf@3                             # a box that changes during the run: descent rate >= -1.2 from step 3 on
     ... --solve-every 3                                                    # solve at steps 0, 3, 6, ...; the tube policy of the last solve acts in between
+    ... --model rocket --persistent 1 --solve-every 5 --hold-trigger 0.75  # solve when the state leaves 0.75 x the plan's tube, or after 5 steps
 
 The first nominal comes from the GPU initialiser (slsqp_nominal_solve) in place of IPOPT."""
 import argparse
@@ -51,6 +52,9 @@ def main():
     ap.add_argument("--solve-every", type=int, default=1, metavar="M",
                     help="the controller solves at steps 0, M, 2M, ... and holds its plan in between, the tube's feedback policy acting on the measured state "
                     "(1 <= M <= N; above 1 the loop runs step by step)")
+    ap.add_argument("--hold-trigger", type=float, default=None, metavar="THETA",
+                    help="with --persistent 1 and --solve-every M > 1 (rti = 1 with one fast-SLS step: the rocket): an instance holds while its measured state stays "
+                    "inside THETA x the tube of its plan and solves when it does not, or after M steps at the latest")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -108,7 +112,8 @@ def main():
                        solve_every=a.solve_every)
     t0 = time.perf_counter()
     run = cl.run_decoupled if a.persistent else cl.run_on_device
-    out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1)
+    kw = {} if a.hold_trigger is None else dict(hold_trigger=a.hold_trigger, **(dict(persistent_hold=True) if a.persistent else {}))
+    out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1, **kw)
     dt = time.perf_counter() - t0
     dist0 = np.linalg.norm(out["state_trajectory"][:, :, 0] - m.x_ref, axis=1).mean()
     dist1 = np.linalg.norm(out["state_trajectory"][:, :, -1] - m.x_ref, axis=1).mean()
@@ -118,6 +123,9 @@ def main():
         held = out["hold_index"] > 0
         print(f"solve every {a.solve_every} steps: {held.mean():.3f} of the steps held; the tube policy ran on {out['hold_policy'][held].mean():.3f} of them "
               f"(the rest had no valid plan and applied the nominal input)")
+    if "solve_trigger" in out:
+        by = [float(np.mean(out["solve_trigger"] == c)) for c in (1, 2, 3)]
+        print(f"hold trigger {a.hold_trigger:g}: steps solved on schedule {by[0]:.3f}, because the state left {a.hold_trigger:g} x tube {by[1]:.3f}, after a failed solve {by[2]:.3f}")
     if P is not None:
         du = out["disturbance_used"]
         print(f"plant mismatch: steps with disturbance_used > 1 (model error + noise outside the box the tubes assume): {np.mean(du > 1.0):.3f}; "

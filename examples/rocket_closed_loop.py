@@ -46,6 +46,9 @@ def main():
                     help="the controller solves at steps 0, M, 2M, ... and holds its plan in between, the tube's feedback policy acting on the measured state (1 <= M <= N)")
     ap.add_argument("--persistent", type=int, default=None, choices=(0, 1), metavar="0|1",
                     help="1: the persistent launch wherever the setting allows it, --solve-every M > 1 included; 0: never; default: the plant's default, and a stepped loop for M > 1")
+    ap.add_argument("--hold-trigger", type=float, default=None, metavar="THETA",
+                    help="with --persistent 1 and --solve-every M > 1: a seed's controller holds while its measured state stays inside THETA x the tube of its plan "
+                    "and solves when it does not, or after M steps at the latest")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model("rocket")
@@ -58,7 +61,7 @@ def main():
     t0 = time.perf_counter()
     r = run_monte_carlo(m, a.N, np.arange(a.seeds), a.steps, x0, solve_nominal=(a.init == "sqp"), slices=a.slices, continuation=a.continuation,
                         budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P, solve_every=a.solve_every,
-                        persistent=None if a.persistent is None else bool(a.persistent))
+                        persistent=None if a.persistent is None else bool(a.persistent), hold_trigger=a.hold_trigger)
     dt = time.perf_counter() - t0
     ok = r["success"]
     if "nlp_status" in r:
@@ -73,6 +76,9 @@ def main():
         viol = np.maximum(X - m.x_ub[None, :, None], m.x_lb[None, :, None] - X).max(axis=1)
         print(f"solve every {a.solve_every} steps: {held.mean():.3f} of the steps held, the tube policy ran on {r['hold_policy'][held].mean():.3f} of them; "
               f"measured states outside the state box: {np.mean(viol > 0):.4f} of the steps")
+    if "solve_trigger" in r:
+        by = [float(np.mean(r["solve_trigger"] == c)) for c in (1, 2, 3)]
+        print(f"hold trigger {a.hold_trigger:g}: steps solved on schedule {by[0]:.3f}, because the state left {a.hold_trigger:g} x tube {by[1]:.3f}, after a failed solve {by[2]:.3f}")
     if P is not None:
         X = r["state_trajectory"]      # (seeds, nx, steps): the measured states
         viol = np.maximum(X - m.x_ub[None, :, None], m.x_lb[None, :, None] - X).max(axis=1)

@@ -293,6 +293,25 @@ int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc);
    (< 0, slsqp_last_error) and changes nothing.  slsqp_cl_step and slsqp_cl_hold_step ignore it. */
 int slsqp_cl_set_solve_every(slsqp_handle *h, int M);
 int slsqp_cl_get_solve_every(slsqp_handle *h);
+/* Event-triggered solves: theta of slsqp_cl_run with M > 1 (persistent launch).  An instance holds its plan while its measured state stays inside the
+   fraction theta of the tube that plan computed and solves as soon as it does not, or after M steps at the latest (M is then a cap, not a period).
+   A property of the handle, default +INFINITY = off: the fixed period above, the same launch and the same bits.  theta in [0, +INFINITY]; a negative
+   or NaN theta is refused (< 0, slsqp_last_error) and changes nothing.  slsqp_cl_step and slsqp_cl_hold_step do not read it; M = 1 ignores it.
+   Per instance, about to begin its closed-loop step s >= 1, with k_prev the hold index of step s - 1 (0: a solve), k = k_prev + 1, x = x_meas, z =
+   stage 1 of its nominal (z_k of the plan: a hold step shifts before it acts), bo = row k of the last solve's backoff_x, plan_ok = its scp_success:
+       r = max_i |x_i - z_i| / bo_i      plain fp64; bo_i = 0: 0 if x_i == z_i, else +inf; a NaN term counts as +inf
+       solve_trigger 1  s == 0 or k >= M     a scheduled solve
+                     3  !plan_ok             the last solve failed, there is no tube to hold: solve again now
+                     2  !(r <= theta)        the state left theta x tube: solve
+                     0  otherwise            hold step k
+   in this precedence.  With slsqp_cl_log the run fills log_tube_ratio (S): r where it was evaluated (s >= 1 and plan_ok), else 0, and
+   log_solve_trigger[int32] (S): the code; both are zeros after every other kind of run.  After an event-triggered run hold_index is per instance. */
+int slsqp_cl_set_hold_trigger(slsqp_handle *h, double theta);
+double slsqp_cl_get_hold_trigger(slsqp_handle *h);
+/* out (B): the tube ratio r above of every instance for the hold step slsqp_cl_hold_step would run next; +INFINITY for an instance without a valid
+   plan (scp_success = 0).  For a step-by-step caller that decides itself (for the whole batch) when to solve.  The refusals are those of
+   slsqp_cl_hold_step; the call changes nothing in the handle. */
+int slsqp_cl_tube_ratio(slsqp_handle *h, double *out, int loc);
 /* The whole closed loop with the instances advancing INDEPENDENTLY (rti = 1, one fast-SLS step, fp64, fuse_rti: the rocket script's setting):
    `steps` MPC steps of every instance, W (steps,B,nx) disturbance samples or NULL.  Per instance the same operations in the same order as `steps`
    calls of slsqp_cl_step (identical results), but in rounds: in a round an instance begins its next MPC step or resumes the QP solve that the

@@ -22,7 +22,7 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None, solve_every=1):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
         state never fails a step on its own (slsqp_set_x0_box_tol).
@@ -32,7 +32,9 @@ class ClosedLoopMPC:
         plant_params: see set_plant_params (None: the true plant is the controller's model).
         bounds: see set_bounds (None: the model's box, the same for every instance and every step).
         solve_every: M of run / run_on_device / run_decoupled: the controller solves at steps 0, M, 2M, ... and holds its plan in between
-        (hold_step: the tube policy of the last solve acts on the measured state); 1 <= M <= N; 1 (default): a solve at every step."""
+        (hold_step: the tube policy of the last solve acts on the measured state); 1 <= M <= N; 1 (default): a solve at every step.
+        hold_trigger: theta of run_decoupled(..., persistent_hold=True): an instance holds while its measured state stays inside theta x the tube of
+        its plan and solves when it does not, or after M steps at the latest; None or inf (default): off, the fixed period."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -47,6 +49,7 @@ class ClosedLoopMPC:
             self.f.opts.solve_waves = int(solve_waves)
         self.steps_done = 0
         self.solve_every = self._check_solve_every(solve_every)
+        self.hold_trigger = self._check_hold_trigger(hold_trigger, first=True)
         if reference is not None:
             self.set_reference(reference)
         if plant_params is not None:
@@ -59,6 +62,21 @@ class ClosedLoopMPC:
         if not 1 <= M <= self.N:
             raise ValueError(f"solve_every must lie in 1..N = {self.N} (K has N rows: at most N - 1 hold steps between two solves), got {M}")
         return M
+
+    def _check_hold_trigger(self, theta, first=False):
+        theta = (float("inf") if first else self.hold_trigger) if theta is None else float(theta)
+        if not theta >= 0.0:
+            raise ValueError(f"hold_trigger must lie in [0, inf] (a fraction of the tube; inf = off), got {theta}")
+        return theta
+
+    def _no_trigger(self, theta, who):
+        if self._check_hold_trigger(theta) < float("inf"):
+            raise ValueError(f"{who}: hold_trigger runs in the persistent launch only: run_decoupled(..., solve_every=M, persistent_hold=True, hold_trigger=theta) "
+                             "(a batch that steps together has one schedule; tube_ratio() gives a step-by-step caller the quantity to decide on)")
+
+    def tube_ratio(self):
+        """(B,) the tube ratio of every instance for the hold step that hold_step() would run next (BatchedFastSLS.tube_ratio)."""
+        return self.f.tube_ratio()
 
     def set_bounds(self, bounds, gf=None):
         """The box in force from the next reset() on: a pair (g, gf) (tuple or list) or g, gf -- rows over MPC time in the model's layout [hi; -lo], (T,ni) / (T,ni_f)
@@ -170,11 +188,12 @@ class ClosedLoopMPC:
             t_qp_ms=0.0, t_riccati_ms=0.0, t_jac_ms=0.0,
         )
 
-    def run_on_device(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, solve_every=None):
+    def run_on_device(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, solve_every=None, hold_trigger=None):
         """Same result as run(), but the per-step records stay in device buffers (slsqp_cl_log) and are read back once at the end: the only
         host -> device traffic per MPC step is the disturbance sample (B,nx).  solve_every = M > 1 (None: the constructor's): see run()."""
         f, m, N, B = self.f, self.m, self.N, self.B
         M = self._check_solve_every(solve_every)
+        self._no_trigger(hold_trigger, "run_on_device")
         L.check(f.lib.slsqp_cl_log(f.h, int(steps)))
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
         t_qp, t_ric, t_jac = np.zeros((steps, 1)), np.zeros((steps, 1)), np.zeros((steps, 1))
@@ -225,7 +244,7 @@ class ClosedLoopMPC:
                 wm[:, i] += w
         return np.max(np.abs(wm), axis=2).T.copy()
 
-    def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0, solve_every=None, persistent_hold=False):
+    def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0, solve_every=None, persistent_hold=False, hold_trigger=None):
         """Same results as run_on_device() -- bit for bit -- with the instances advancing through their MPC steps independently, so nobody waits for
         the slowest instance of a step.
         rti = 1 with one fast-SLS step (the rocket script's setting): slsqp_cl_run.  With opts.cl_persistent (the default) the whole loop is ONE launch:
@@ -238,22 +257,30 @@ class ClosedLoopMPC:
         persistent_hold=True runs it as the persistent launch instead, the hold steps of an instance inside the loop of the wave that solved for it
         (BatchedFastSLS.set_solve_every; rti = 1 with one fast-SLS step and opts.cl_persistent only, every other setting raises with the library's
         message): the same bits, what a persistent run returns, plus `hold_index` and `hold_policy`.
+        hold_trigger = theta < inf (None: the constructor's; with persistent_hold and M > 1 only, anything else raises): event-triggered solves -- an
+        instance holds while its tube ratio is <= theta and solves when it is not, or after M steps at the latest (slsqp_cl_set_hold_trigger); the result
+        then also holds `tube_ratio` (B, steps) and `solve_trigger` (B, steps) (0 hold, 1 scheduled, 2 left theta x tube, 3 the last solve had failed).
         Adds `qp_stats` (B, steps, 2, 8) (next to `x0_violation` (B, steps, 2), which every logged run has), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the run's totals in their first entry."""
         f, m, N, B = self.f, self.m, self.N, self.B
         M = self._check_solve_every(solve_every)
         hold = M > 1 and persistent_hold
+        theta = self._check_hold_trigger(hold_trigger)
+        if not persistent_hold:
+            self._no_trigger(theta, "run_decoupled without persistent_hold")
         if f.opts.solve_waves > 1 or (M > 1 and not hold):      # the persistent kernels are one wave per instance; M > 1 without persistent_hold: the same loop, step by step (no qp_stats / loop_stats)
-            out = self.run_on_device(x0, steps, W, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation, solve_every=M)
+            out = self.run_on_device(x0, steps, W, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation, solve_every=M, hold_trigger=theta)      # (a finite theta raises there)
             out["rounds"] = steps
             return out
         if hold and not (self.rti == 1 and f.opts.rti_steps == 1):      # (asked here, before anything is reset: the library's words)
             raise RuntimeError(f"slsqp: slsqp_cl_run_scp: solve_every = {M} needs rti = 1 with one fast-SLS step (slsqp_cl_run's kernel): the general "
                                "persistent loop keeps its gains per SCP iteration and solves at every step (use slsqp_cl_step / slsqp_cl_hold_step)")
         f.set_solve_every(M if hold else 1)
+        f.set_hold_trigger(theta if hold else None)
         try:
             return self._run_persistent(x0, steps, W, X_nom, U_nom, solve_nominal, continuation, budget_ms, cut_frac, hold)
         finally:
-            f.set_solve_every(1)      # (the handle's M is this call's: the next run says what it wants)
+            f.set_solve_every(1)      # (the handle's M and theta are this call's: the next run says what it wants)
+            f.set_hold_trigger(None)
 
     def _run_persistent(self, x0, steps, W, X_nom, U_nom, solve_nominal, continuation, budget_ms, cut_frac, hold):
         f, m, N, B = self.f, self.m, self.N, self.B
@@ -282,15 +309,18 @@ class ClosedLoopMPC:
             out["loop_stats"] = dict(waves=int(st[0]), busy_ms=float(st[1]), mpc_steps=int(st[2]), launch_ms=float(st[3]))
         if hold:
             out.update(hold_index=f.get("log_hold", (steps,), np.int32), hold_policy=f.get("log_hold_policy", (steps,), np.int32).astype(bool))
+            if f.get_hold_trigger() < float("inf"):
+                out.update(tube_ratio=f.get("log_tube_ratio", (steps,)), solve_trigger=f.get("log_solve_trigger", (steps,), np.int32))
         return out
 
-    def run(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, solve_every=None):
+    def run(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, solve_every=None, hold_trigger=None):
         """Closed loop of `steps` MPC steps from x0 (B,nx); W (steps,B,nx) disturbance samples or None.  Returns arrays laid out
         like the reference's npz (expe/main_rocket_robust_closed_loop.py:189-206) with a leading batch axis.
         solve_every = M > 1 (None: the constructor's): a solve at steps 0, M, 2M, ..., hold_step() in between; the result then also holds `hold_index`
         (B, steps) (0: a solved step, k: the k-th hold step since the solve) and `hold_policy` (B, steps) (the tube policy ran)."""
         m, N, B = self.m, self.N, self.B
         M = self._check_solve_every(solve_every)
+        self._no_trigger(hold_trigger, "run")
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal)
         out = dict(
             state_trajectory=np.zeros((B, m.nx, steps)), input_trajectory=np.zeros((B, m.nu, max(steps - 1, 0))),

@@ -23,15 +23,41 @@ CL_HOLD_HD inline int hold_index_at(int step, int M) { return M > 1 ? step % M :
 CL_HOLD_HD inline bool is_solve(int step, int M) { return hold_index_at(step, M) == 0; }
 inline int solves_in(int steps, int M) { return steps <= 0 ? 0 : (steps + M - 1) / M; }      // solves among the steps 0 .. steps - 1
 
+// The event-triggered schedule (slsqp_cl_set_hold_trigger): an instance holds while its measured state stays inside the
+// fraction theta of the tube its plan computed, and solves when it does not, or after M steps at the latest.  theta = +inf (the default): off, the
+// schedule above.  One definition for the host, the persistent kernel, slsqp_cl_tube_ratio and tests/hold_trigger_ref.py.
+CL_HOLD_HD inline bool valid_trigger(double theta) { return theta >= 0.0; }      // [0, +inf]; a NaN is refused
+CL_HOLD_HD inline bool trigger_on(double theta, int M) { return M > 1 && theta <= 1.7976931348623157e308; }
+// component i of the tube ratio: |x - z| / bo in plain fp64; a tube of zero width holds exactly its centre; a NaN counts as outside every tube
+CL_HOLD_HD inline double tube_term(double x, double z, double bo) {
+    if (bo == 0.0) return x == z ? 0.0 : __builtin_huge_val();
+    const double t = __builtin_fabs(x - z) / bo;
+    return t == t ? t : __builtin_huge_val();
+}
+enum Trigger { TRIG_HOLD = 0, TRIG_SCHEDULED = 1, TRIG_TUBE = 2, TRIG_FAILED = 3 };
+// What an instance does at its step s: k_prev is the hold index of step s - 1 (0: a solve), k = k_prev + 1 the hold step that would come next,
+// plan_ok the success of its last solve, r the tube ratio of the measured state at stage k of that plan (read only where s >= 1 and plan_ok).
+// TRIG_HOLD: hold step k; every other code: solve.
+CL_HOLD_HD inline int decide(int s, int k_prev, int M, bool plan_ok, double r, double theta) {
+    if (s == 0 || k_prev + 1 >= M) return TRIG_SCHEDULED;
+    if (!plan_ok) return TRIG_FAILED;
+    if (!(r <= theta)) return TRIG_TUBE;      // (a NaN ratio triggers)
+    return TRIG_HOLD;
+}
+
 struct State {
     int k = 0;              // index of the last hold step (1 = the first plant step after a solve)
     int at_steps = -1;      // the handle's step count right after that hold step (-1: none since slsqp_cl_init)
     int run_steps = -1;     // the step count a persistent / round-based run left behind (-1: none since slsqp_cl_init)
+    int dev_steps = -1;     // the step count an event-triggered run left behind: "hold_index" is the per-instance device array (-1: none since slsqp_cl_init)
 };
 
 inline void on_init(State &s) { s = State{}; }
 // k_last > 0: the run's last step was the hold step of that index (a persistent run with solve_every > 1): "hold_index" serves it
 inline void on_run(State &s, int cl_steps_after, int k_last = 0) { s.run_steps = cl_steps_after; if (k_last > 0) { s.k = k_last; s.at_steps = cl_steps_after; } }
+// an event-triggered run: every instance ends at its own index
+inline void on_triggered_run(State &s, int cl_steps_after) { s.run_steps = cl_steps_after; s.dev_steps = cl_steps_after; }
+inline bool index_per_instance(const State &s, int cl_steps) { return cl_steps == s.dev_steps; }
 inline void on_hold(State &s, int k, int cl_steps_after) { s.k = k; s.at_steps = cl_steps_after; }
 // "hold_index": hold steps since the last solve
 inline int index(const State &s, int cl_steps) { return cl_steps == s.at_steps ? s.k : 0; }

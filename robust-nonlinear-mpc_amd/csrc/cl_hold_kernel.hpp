@@ -11,6 +11,7 @@
 // The caller has shifted the nominal by one stage, so z_k, v_k are stage 0 of Xn / Un; A, B, K are indexed from the solve.
 #ifndef SLSQP_CL_HOLD_KERNEL_HPP
 #define SLSQP_CL_HOLD_KERNEL_HPP
+#include "cl_hold.hpp"
 #include "slsqp_kernels.hpp"
 
 namespace slsqp {
@@ -131,6 +132,27 @@ __device__ __forceinline__ void cl_hold_log(const HoldArgs &a, int b, int lane, 
         if (lane == 0) { a.lit[e] = 0; a.lhold[e] = k; a.lpol[e] = ok ? 1 : 0; a.lx0v[e * 2] = 0.0; a.lx0v[e * 2 + 1] = 0.0; }
         wla::wsync_mem();      // the state is logged before lane 0 replaces it
     }
+}
+// The tube ratio of instance b for the hold step k that would come next (cl_hold.hpp): max_i |x_meas_i - z_i| / backoff_x[k, i],
+// z stage 1 of the nominal as it stands (the plan's stage k: a hold step shifts before it acts).  Lane i takes component i; the lanes above NX hold 0,
+// no term is negative or a NaN (cl_hold::tube_term), so the crossbar's max is the max in ascending i.  Every lane returns it.  Reads only.
+// Two callers: k_cl_tube_ratio below (slsqp_cl_tube_ratio) and the event-triggered HOLD variants of the persistent closed-loop kernel.
+template <int MODEL>
+__device__ __forceinline__ double cl_tube_ratio_wave(const ClArgs &cl, const double *backoff_x, int b, int lane, int k) {
+    constexpr int NX = dyn::Dims<MODEL>::NX;
+    static_assert(NX <= 64, "lane i takes component i");
+    const size_t row = (size_t)b * (cl.N + 1) * NX;
+    double t = 0.0;
+    if (lane < NX) t = cl_hold::tube_term(cl.xmeas[(size_t)b * NX + lane], cl.Xn[row + NX + lane], backoff_x[row + (size_t)k * NX + lane]);
+    return wla::wave_max(t);
+}
+// one wave per instance: out[b] = the ratio for hold step k, +inf for an instance without a valid plan
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_cl_tube_ratio(ClArgs cl, const double *backoff_x, const int *scp_success, int k, double *out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= cl.B) return;
+    const double r = scp_success[b] != 0 ? cl_tube_ratio_wave<MODEL>(cl, backoff_x, b, lane, k) : INFINITY;
+    if (lane == 0) out[b] = r;
 }
 template <int MODEL, bool PP>
 __global__ __launch_bounds__(64) void k_cl_hold(HoldArgs a, PlantArgs pa) {

@@ -77,6 +77,8 @@ struct slsqp_handle {
     double *x0viol;             // (B,2) largest stage-0 violation of the instance's last first / last QP: part of the kkt allocation (x0_record, slsqp_kernels.hpp)
     double x0_box_tol = 0.0;    // slsqp_set_x0_box_tol: the tolerance the following launches ask for
     int solve_every = 1;        // slsqp_cl_set_solve_every: M of slsqp_cl_run -- a solve at steps 0, M, 2M, ... of every instance, hold steps in between (1: a solve at every step)
+    double hold_trigger = INFINITY;      // slsqp_cl_set_hold_trigger: theta of slsqp_cl_run with solve_every > 1 -- an instance holds while its tube ratio is <= theta (+inf: off, the fixed period)
+    int *hold_k = nullptr, *lg_trig = nullptr; double *lg_ratio = nullptr;      // (B) per-instance hold index of an event-triggered run (ensure_hold); its per-step reason codes and ratios (slsqp_cl_log)
     std::vector<unsigned char> hold_blk_host;      // the HoldLoopArgs the host last wrote behind the ScpLoopArgs of loop_blk (runs with solve_every > 1 only)
     int solve_waves = 1;        // slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = k_qp_solve_mw (one workgroup of that many waves per instance)
     double *ref_Y = nullptr; int ref_T = 0; size_t ref_stride = 0;      // slsqp_cl_set_reference: packed rows [x_ref; u_ref] (T, nz), per instance with ref_stride = T nz, shared with 0; ref_T = 0: none
@@ -874,7 +876,11 @@ struct ScpLoopArgs {
 // What the HOLD variants of k_cl_loop read besides: the arguments of the hold function (a.k and a.step are not read: every
 // instance is at its own step) and M.  It lies in the same device block BEHIND the ScpLoopArgs, at HOLD_BLK_OFFSET: ScpLoopArgs keeps its size and
 // every offset (bd stays its last field, tests/loop_args_check_main.cpp), and a run with M = 1 writes and reads the bytes it always did.
-struct HoldLoopArgs { HoldArgs a; int M; };
+// Event-triggered runs (slsqp_cl_set_hold_trigger) read the fields behind M: theta (+inf: off -- none of the others is read),
+// the last solve's backoff_x, the per-instance hold index that replaces hold_index_at(stepno, M), and the log of ratio and reason code.
+struct HoldLoopArgs { HoldArgs a; int M; double theta; const double *backoff_x; int *hold_k; double *lratio; int *ltrig; };
+// the hold index of instance b at its step s: the one the wave that ran step s - 1 decided, or the fixed period's (wave-uniform)
+__device__ __forceinline__ int loop_hold_index(const HoldLoopArgs &H, int b, int s) { return cl_hold::trigger_on(H.theta, H.M) ? H.hold_k[b] : cl_hold::hold_index_at(s, H.M); }
 constexpr size_t HOLD_BLK_OFFSET = (sizeof(ScpLoopArgs) + 15) & ~(size_t)15, LOOP_BLK_BYTES = 4096;
 static_assert(HOLD_BLK_OFFSET + sizeof(HoldLoopArgs) <= LOOP_BLK_BYTES, "slsqp_handle::loop_blk is 4096 bytes");
 __device__ __forceinline__ const HoldLoopArgs *hold_blk(const ScpLoopArgs *blk) { return (const HoldLoopArgs *)((const unsigned char *)blk + HOLD_BLK_OFFSET); }
@@ -921,7 +927,7 @@ __device__ CLW_FN void cl_step_begin(const LoopArgs &L_, int b, int lane, const 
 // hold function (xi, the policy's input u, hold_policy) in the LDS `sm`, the log fields k_cl_hold writes, "took no part" as the entry of log_qp_stats --
 // and then the SAME plant step, one call site, with u in the place of the first nominal input
 template <int MODEL, bool PP = false, bool HOLD = false>
-__device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const PlantArgs *pa = nullptr, const HoldLoopArgs *hp = nullptr, double *sm = nullptr) {
+__device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const PlantArgs *pa = nullptr, const HoldLoopArgs *hp = nullptr, double *sm = nullptr, int *knext = nullptr) {
     const LoopArgs *Lp = &L_;
     const LoopArgs &L = args_here<true>(Lp);
     constexpr int NX = dyn::Dims<MODEL>::NX;
@@ -930,9 +936,11 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
     unsigned long long ts_ = wall_clock64();
 #endif
     bool held = false;
+    int kprev = 0;      // HOLD: the hold index of this step
     if constexpr (HOLD) {
         const HoldLoopArgs &H = args_here<true>(hp);
-        const int k = cl_hold::hold_index_at(s, H.M);
+        const int k = loop_hold_index(H, b, s);
+        kprev = k;
         if (k) {
             held = true;
             if (L.have_log) {
@@ -974,7 +982,32 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
     }
     wla::wsync_mem();
     CLSTAMP(10);
-    return (s + 1 < L.steps) ? s + 1 : 0;
+    const int next = (s + 1 < L.steps) ? s + 1 : 0;
+    if constexpr (HOLD) {
+        // what the instance does at its next step, decided here: x_meas is new and the plan not yet shifted again.  Event-triggered: the tube ratio
+        // of the hold step that would come next and cl_hold::decide, stored per instance for the loop top and for this function at step s + 1
+        const HoldLoopArgs &H = args_here<true>(hp);
+        if (!cl_hold::trigger_on(H.theta, H.M)) *knext = cl_hold::hold_index_at(next, H.M);
+        else {
+            *knext = 0;
+            const bool lg = H.a.S > 0;
+            if (s == 0 && lg && lane == 0) { H.ltrig[(size_t)b * H.a.S] = cl_hold::TRIG_SCHEDULED; H.lratio[(size_t)b * H.a.S] = 0.0; }
+            if (next) {
+                const bool ok = H.a.scp_success[b] != 0;
+                const int kn = kprev + 1;
+                double r = 0.0;
+                if (ok && kn <= H.a.cl.N) r = cl_tube_ratio_wave<MODEL>(H.a.cl, H.backoff_x, b, lane, kn);
+                const int code = cl_hold::decide(next, kprev, H.M, ok, r, H.theta);
+                *knext = code == cl_hold::TRIG_HOLD ? kn : 0;
+                if (lane == 0) {
+                    H.hold_k[b] = *knext;
+                    if (lg && next < H.a.S) { H.ltrig[(size_t)b * H.a.S + next] = code; H.lratio[(size_t)b * H.a.S + next] = r; }
+                }
+                wla::wsync_mem();
+            }
+        }
+    }
+    return next;
 }
 // The persistent closed loop, ONE body with five variants, VAR a set of the bits VAR_REF / VAR_PP / VAR_BND (cl_options).  0: plain; REF: tracks a
 // reference (slsqp_cl_set_reference: the linear cost of cl_step_begin reads rf); PP: steps the plant with the instance's own parameters
@@ -1010,7 +1043,7 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const
 #endif
         }
         bool solve = true;      // HOLD: the instance's step is a solve or a hold step (read again in cl_step_end: nothing of it is live across the chain)
-        if constexpr (var_hold(VAR)) solve = __builtin_amdgcn_readfirstlane(cl_hold::hold_index_at(L.stepno[b], args_here<true>(hold_blk(blk)).M)) == 0;
+        if constexpr (var_hold(VAR)) solve = __builtin_amdgcn_readfirstlane(loop_hold_index(args_here<true>(hold_blk(blk)), b, L.stepno[b])) == 0;
         cl_step_begin<MODEL, var_ref(VAR), var_bnd(VAR), var_hold(VAR)>(L, b, lane, var_ref(VAR) ? &rf : nullptr, var_bnd(VAR) ? &blk->bd : nullptr, solve ? 0 : 1);
         b = __builtin_amdgcn_readfirstlane(b);      // (across a call the compiler may park it in a vector register)
         asm volatile("" : "+v"(lane));
@@ -1019,12 +1052,13 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop(const
             wla::wsync_mem();
         }
         asm volatile("" : "+v"(lane));
-        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, var_pp(VAR), var_hold(VAR)>(L, b, lane, var_pp(VAR) ? &pa : nullptr, var_hold(VAR) ? hold_blk(blk) : nullptr, sm));
+        int knext = 0;      // HOLD: the hold index of the instance's next step (0: a solve)
+        const int next = __builtin_amdgcn_readfirstlane(cl_step_end<MODEL, var_pp(VAR), var_hold(VAR)>(L, b, lane, var_pp(VAR) ? &pa : nullptr, var_hold(VAR) ? hold_blk(blk) : nullptr, sm, &knext));
         b = __builtin_amdgcn_readfirstlane(b);
         if (!next) { b = -1; continue; }
         // HOLD: the hold steps that follow a solve (at most M - 1, fewer at the end of the run) run at once on this wave, without a queue round trip;
         // the tail below then sees the step count the instance has reached
-        if constexpr (var_hold(VAR)) { if (!cl_hold::is_solve(next, args_here<true>(hold_blk(blk)).M)) continue; }
+        if constexpr (var_hold(VAR)) { if (__builtin_amdgcn_readfirstlane(knext)) continue; }
         const LoopArgs &Lt = args_here<true>(blk).L;      // (the tail's few fields, read here and not held across the step)
         // An instance that is behind the batch's mean progress keeps its wave and goes straight on (a few instances are slow in MANY of their
         // steps: queueing after each of them they would finish long after the others, with the GPU nearly empty); the others queue up, so the
@@ -1969,7 +2003,8 @@ static int get_hold_named(slsqp_handle *h, const char *name, void *out, int loc)
     HIPCHK(hipStreamSynchronize(h->st));
     const size_t B = h->B, nxi = B * (h->d.N + 1) * h->d.nx;
     const hipMemcpyKind from_host = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice, from_dev = loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (is_k) { const std::vector<int> v(B, cl_hold::index(h->hold, h->cl_steps)); HIPCHK(hipMemcpy(out, v.data(), sizeof(int) * B, from_host)); }
+    if (is_k && cl_hold::index_per_instance(h->hold, h->cl_steps) && h->hold_k) HIPCHK(hipMemcpy(out, h->hold_k, sizeof(int) * B, from_dev));      // (an event-triggered run: every instance at its own index)
+    else if (is_k) { const std::vector<int> v(B, cl_hold::index(h->hold, h->cl_steps)); HIPCHK(hipMemcpy(out, v.data(), sizeof(int) * B, from_host)); }
     else if (!h->hold_xi) {
         if (is_x) { const std::vector<double> z(nxi, 0.0); HIPCHK(hipMemcpy(out, z.data(), sizeof(double) * nxi, from_host)); }
         else { const std::vector<int> z(B, 0); HIPCHK(hipMemcpy(out, z.data(), sizeof(int) * B, from_host)); }
@@ -2106,6 +2141,7 @@ extern "C" int slsqp_cl_init(slsqp_handle *h, const double *x_meas, const double
     h->cl_steps = 0;
     cl_hold::on_init(h->hold);      // no plan to hold yet
     if (h->lg_hold) HIPCHK(hipMemsetAsync(h->lg_hold, 0, sizeof(int) * B * h->log_steps * 2, h->st));      // (log_hold, log_hold_policy: solved steps never write them)
+    if (h->lg_ratio) { HIPCHK(hipMemsetAsync(h->lg_ratio, 0, sizeof(double) * B * h->log_steps, h->st)); HIPCHK(hipMemsetAsync(h->lg_trig, 0, sizeof(int) * B * h->log_steps, h->st)); }      // (written by event-triggered runs only)
     HIPCHK(hipMemsetAsync(h->has_prev, 0, sizeof(int) * B, h->st));   // a fresh SCP_SLS object has no convergence history
     HIPCHK(hipStreamSynchronize(h->st));
     return slsqp_reset(h);
@@ -2174,9 +2210,9 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     HIPCHK(hipStreamSynchronize(h->st));
     h->log_steps = 0;
     free_all(h->log_owned);
-    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy"};
+    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy", "log_tube_ratio", "log_solve_trigger"};
     for (const char *nm : names) h->named.erase(nm);
-    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr;
+    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr;
     h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr;
     const slsqp_dims &d = h->d;
     const size_t B = h->B, S = max_steps, nX = (size_t)(d.N + 1) * d.nx, nU = (size_t)d.N * d.nu;
@@ -2186,7 +2222,8 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     rc |= dalloc(ow, &h->lg_state, B * S * d.nx); rc |= dalloc(ow, &h->lg_u0, B * S * d.nu); rc |= dalloc(ow, &h->lg_succ, B * S); rc |= dalloc(ow, &h->lg_it, B * S);
     rc |= dalloc(ow, &h->lg_pinf, B * S); rc |= dalloc(ow, &h->lg_x0v, B * S * 2); rc |= dalloc(ow, &h->lg_merr, B * S * d.nx);
     rc |= dalloc(ow, &h->lg_hold, B * S * 2); h->lg_hpol = h->lg_hold ? h->lg_hold + B * S : nullptr;
-    if (rc) { free_all(ow); h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
+    rc |= dalloc(ow, &h->lg_ratio, B * S); rc |= dalloc(ow, &h->lg_trig, B * S);
+    if (rc) { free_all(ow); h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
     h->log_steps = max_steps;
     auto reg = [&](const char *nm, void *p, size_t bytes) { h->named[nm] = {p, bytes}; };
     reg("log_nominal_x", h->lg_x, sizeof(double) * S * nX); reg("log_nominal_u", h->lg_u, sizeof(double) * S * nU);
@@ -2195,6 +2232,7 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     reg("log_success", h->lg_succ, sizeof(int) * S); reg("log_scp_iterations", h->lg_it, sizeof(int) * S);
     reg("log_primal_infeasibility", h->lg_pinf, sizeof(double) * S); reg("log_x0_viol", h->lg_x0v, sizeof(double) * S * 2);
     reg("log_hold", h->lg_hold, sizeof(int) * S); reg("log_hold_policy", h->lg_hpol, sizeof(int) * S);      // slsqp_cl_hold_step: 0 for a solved step, k for hold step k; whether the policy ran
+    reg("log_tube_ratio", h->lg_ratio, sizeof(double) * S); reg("log_solve_trigger", h->lg_trig, sizeof(int) * S);      // an event-triggered slsqp_cl_run (slsqp_cl_set_hold_trigger): the ratio where it was evaluated, the reason code of cl_hold::decide; zeros from every other run
     reg("log_model_error", h->lg_merr, sizeof(double) * S * d.nx);      // ddyn_p - ddyn of every step's plant step (slsqp_cl_set_plant_params; zeros without parameters)
     return 0;
 }
@@ -2281,6 +2319,14 @@ extern "C" int slsqp_cl_set_solve_every(slsqp_handle *h, int M) {
     return 0;
 }
 extern "C" int slsqp_cl_get_solve_every(slsqp_handle *h) { return h->solve_every; }
+// theta of the event-triggered schedule of slsqp_cl_run with M > 1: a property of the handle, default +inf = off (the fixed
+// period).  Anything outside [0, +inf], a NaN included, is refused and changes nothing.  slsqp_cl_step and slsqp_cl_hold_step do not read it.
+extern "C" int slsqp_cl_set_hold_trigger(slsqp_handle *h, double theta) {
+    if (!cl_hold::valid_trigger(theta)) return fail("slsqp_cl_set_hold_trigger: theta = " + std::to_string(theta) + " outside [0, +inf] (a fraction of the tube; +inf = off)");
+    h->hold_trigger = theta;
+    return 0;
+}
+extern "C" double slsqp_cl_get_hold_trigger(slsqp_handle *h) { return h->hold_trigger; }
 
 // One closed-loop step WITHOUT a solve: the one-stage shift slsqp_cl_step applies at its top, then k_cl_hold -- the tube policy
 // of the last solve on the measured state, and the plant step.  No slsqp_reset (K stays valid); slsqp_cl_step is not involved and finds, at its next
@@ -2291,11 +2337,11 @@ static int ensure_hold(slsqp_handle *h) {
     const size_t nxi = (size_t)h->B * (h->d.N + 1) * h->d.nx, nu = (size_t)h->B * h->d.nu;
     double *buf = nullptr; int *pol = nullptr;
     HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (nxi + nu) + 64));
-    if (hipMalloc((void **)&pol, sizeof(int) * h->B + 64) != hipSuccess || hipMemset(buf, 0, sizeof(double) * (nxi + nu)) != hipSuccess || hipMemset(pol, 0, sizeof(int) * h->B) != hipSuccess) {
+    if (hipMalloc((void **)&pol, sizeof(int) * 2 * h->B + 64) != hipSuccess || hipMemset(buf, 0, sizeof(double) * (nxi + nu)) != hipSuccess || hipMemset(pol, 0, sizeof(int) * 2 * h->B) != hipSuccess) {      // [hold_policy | hold_k]
         hipFree(buf); if (pol) hipFree(pol);
         return fail("slsqp_cl_hold_step: allocation failed");
     }
-    h->hold_xi = buf; h->hold_u = buf + nxi; h->hold_policy = pol;
+    h->hold_xi = buf; h->hold_u = buf + nxi; h->hold_policy = pol; h->hold_k = pol + h->B;
     return 0;
 }
 extern "C" int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc) {
@@ -2323,6 +2369,24 @@ extern "C" int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc) {
     if (finish_enqueued(h, false)) return -1;
     h->cl_steps++;
     cl_hold::on_hold(h->hold, k, h->cl_steps);
+    return 0;
+}
+
+// The tube ratio of every instance for the hold step slsqp_cl_hold_step would run next (its refusals apply); +inf for an instance without a valid
+// plan.  out (B).  Changes nothing in the handle.
+extern "C" int slsqp_cl_tube_ratio(slsqp_handle *h, double *out, int loc) {
+    hipSetDevice(h->dev);
+    std::string why;
+    const int k = cl_hold::next_index(h->hold, h->model_id >= 0, h->cl_steps, h->d.N, loc, &why);
+    if (!k) return fail("slsqp_cl_tube_ratio: " + why);
+    if (!out) return fail("slsqp_cl_tube_ratio: out is NULL");
+    double *dout = loc == SLSQP_DEVICE ? out : stage_buf(h, sizeof(double) * (size_t)h->B);
+    if (!dout) return -1;
+    const ClArgs a = cl_args(h, nullptr);
+    if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_tube_ratio<M()>), dim3(h->B), dim3(64), 0, h->st, a, h->backoff_x, h->scp_success, k, dout); })) return -1;
+    HIPCHK(hipGetLastError());
+    if (loc != SLSQP_DEVICE) HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * (size_t)h->B, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
     return 0;
 }
 
@@ -2414,6 +2478,7 @@ static HoldLoopArgs make_hold_block(slsqp_handle *h) {
     a.S = h->log_steps;
     a.lstate = h->lg_state; a.lu0 = h->lg_u0; a.lx0v = h->lg_x0v; a.lit = h->lg_it; a.lhold = h->lg_hold; a.lpol = h->lg_hpol;      // (lx0v: the log's own buffer; the run's log_x0_viol is the block's x0vlog)
     H.M = h->solve_every;
+    H.theta = h->hold_trigger; H.backoff_x = h->backoff_x; H.hold_k = h->hold_k; H.lratio = h->lg_ratio; H.ltrig = h->lg_trig;
     return H;
 }
 static int write_hold_block(slsqp_handle *h, const HoldLoopArgs &H) {
@@ -2439,6 +2504,8 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     if (write_loop_block(h, S)) return -1;
     const int M = scp ? 1 : h->solve_every;      // (slsqp_cl_run_scp has refused M > 1 for its own kernel)
     if (M > 1 && (ensure_hold(h) || write_hold_block(h, make_hold_block(h)))) return -1;
+    const bool triggered = cl_hold::trigger_on(h->hold_trigger, M);      // every instance on its own schedule: its first step is a solve
+    if (triggered) HIPCHK(hipMemsetAsync(h->hold_k, 0, sizeof(int) * (size_t)B, h->st));
     hipLaunchKernelGGL(k_clq_init, dim3(64), dim3(256), 0, h->st, B, L.Q);
     HIPCHK(hipMemsetAsync(h->cl_busy, 0, 16 * sizeof(unsigned long long), h->st));
     HIPCHK(hipMemsetAsync(h->cl_busy + 14, 0xFF, sizeof(unsigned long long), h->st));      // (CL_LOOP_STAMP builds: earliest wave start)
@@ -2465,8 +2532,13 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     if (ctl[3] != 0 || unfinished != 0)
         return fail("slsqp_cl_run (persistent): the instance queue did not drain (err " + std::to_string(ctl[3]) + ", " + std::to_string(unfinished) + " instances short of their steps)");
     h->cl_steps = steps;
-    cl_hold::on_run(h->hold, h->cl_steps, cl_hold::hold_index_at(steps - 1, M));      // (no per-batch plan: slsqp_cl_hold_step refuses until a slsqp_cl_step; "hold_index": the last step's)
-    h->call_id += (double)cl_hold::solves_in(steps, M) * max_it;
+    if (triggered) {      // the solves per instance are the run's to decide: the ids stay distinct and increasing under the upper bound; "hold_index": the device array
+        cl_hold::on_triggered_run(h->hold, h->cl_steps);
+        h->call_id += (double)steps * max_it;
+    } else {
+        cl_hold::on_run(h->hold, h->cl_steps, cl_hold::hold_index_at(steps - 1, M));      // (no per-batch plan: slsqp_cl_hold_step refuses until a slsqp_cl_step; "hold_index": the last step's)
+        h->call_id += (double)cl_hold::solves_in(steps, M) * max_it;
+    }
     if (rounds_out) *rounds_out = 1;
     return 0;
 }

@@ -253,6 +253,22 @@ class BatchedFastSLS:
     def get_solve_every(self):
         return int(self.lib.slsqp_cl_get_solve_every(self.h))
 
+    def set_hold_trigger(self, theta):
+        """theta of the event-triggered persistent closed loop (slsqp_cl_set_hold_trigger): with solve_every = M > 1 an instance of slsqp_cl_run holds
+        while its tube ratio (tube_ratio) is <= theta and solves as soon as it is not, or after M steps at the latest.  theta in [0, inf]; None or inf
+        (default): off, the fixed period.  A negative or NaN theta is refused with the handle unchanged.  slsqp_cl_step and hold_step do not read it."""
+        L.check(self.lib.slsqp_cl_set_hold_trigger(self.h, float("inf") if theta is None else float(theta)))
+
+    def get_hold_trigger(self):
+        return float(self.lib.slsqp_cl_get_hold_trigger(self.h))
+
+    def tube_ratio(self):
+        """(B,) max_i |x_meas_i - z_i| / backoff_x[k, i] of every instance for the hold step k that hold_step would run next (slsqp_cl_tube_ratio), z
+        stage k of the plan; inf for an instance without a valid plan.  Refused where hold_step is; changes nothing."""
+        out = np.empty(self.B)
+        L.check(self.lib.slsqp_cl_tube_ratio(self.h, _ptr(out), L.HOST))
+        return out
+
     def update_linear_cost(self, q):
         q = _c(q)
         assert q.shape == (self.B, self.n)

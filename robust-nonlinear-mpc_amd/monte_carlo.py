@@ -46,15 +46,18 @@ PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
 
 
 def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1,
-               reference=None, plant_params=None, bounds=None, solve_every=1):
+               reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
-    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every)
+    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every, hold_trigger=hold_trigger)
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
     rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
     want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
     # solve_every > 1 inside the persistent launch: only when asked for (persistent=True), for rti = 1 with one fast-SLS step and the persistent variant
     hold = solve_every > 1 and persistent is True and cl.rti == 1 and rti_steps == 1 and bool(cl.f.opts.cl_persistent) and solve_waves == 1
+    if cl.hold_trigger < float("inf") and not hold:
+        cl.close()
+        raise ValueError("run_monte_carlo: hold_trigger runs in the persistent launch only: pass solve_every = M > 1 and persistent=True (rti = 1 with one fast-SLS step, opts.cl_persistent, solve_waves = 1)")
     if (solve_every == 1 or hold) and budget_ms != 0 and want and can_run_persistent(cl.rti, rti_steps, cl.f.opts):      # instances advance independently (slsqp_cl_run / slsqp_cl_run_scp): same bits
         out = cl.run_decoupled(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation, budget_ms=8.0 if budget_ms is None else budget_ms, persistent_hold=hold)
     else:
@@ -67,7 +70,7 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
                     budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None,
-                    solve_every=1):
+                    solve_every=1, hold_trigger=None):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
@@ -89,6 +92,9 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     (seeds, steps).  With persistent=True, where can_run_persistent and the setting allow (rti = 1 with one fast-SLS step, opts.cl_persistent), the
     hold steps run inside the persistent launch instead (run_decoupled's persistent_hold): the same bits, plus `qp_stats`, `rounds`, `loop_stats`;
     persistent=None keeps stepping.  1 (default): today's loops, unchanged.
+    hold_trigger: theta < inf = event-triggered solves (ClosedLoopMPC.run_decoupled's hold_trigger): with solve_every = M > 1 and persistent=True a seed's
+    controller holds while its state stays inside theta x its tube and solves when it does not, or after M steps at the latest; the result then holds
+    `tube_ratio` and `solve_trigger` (seeds, steps).  Without persistent=True it raises.  None (default): off.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -140,6 +146,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["solve_waves"] = solve_waves
             if solve_every != 1:
                 kw["solve_every"] = solve_every
+            if hold_trigger is not None:
+                kw["hold_trigger"] = hold_trigger
             kw.update(options(k))
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:

@@ -2,11 +2,16 @@
 """What holding an MPC solution costs and keeps: the rocket closed loop of bench.py (N = 20, the script's x0, seed-s noise streams) through
 ClosedLoopMPC.run_on_device with a solve every M steps and the tube's feedback policy in between (slsqp_cl_hold_step).
 
-    python scripts/bench_hold.py [--batch 4096] [--steps 30] [--M 1 2 3 5] [--reps 5] [--root DIR] [--persistent]
+    python scripts/bench_hold.py [--batch 4096] [--steps 30] [--M 1 2 3 5] [--reps 5] [--root DIR] [--persistent [--trigger THETA]]
 
 --persistent: the same loop as ONE persistent launch (ClosedLoopMPC.run_decoupled, for M > 1 with persistent_hold=True: the hold steps run inside the
 launch); the timed span is then reset's return to the launch's end (the upload of the noise samples included), and the line also
 holds `persistent`, `loop_stats` of the last run and `waves_busy` = busy_ms / (waves x launch's wall time), how busy the instance queue kept the waves.
+
+--persistent --trigger THETA: event-triggered solves (run_decoupled's hold_trigger): an instance holds while its state stays
+inside THETA x its tube and solves when it does not, or after M steps at the latest.  The line then also holds `trigger`, `solved_share` (the share of
+instance-steps that solved) and `solved_by_reason` (its split: 1 scheduled, 2 the state left THETA x tube, 3 the last solve had failed), and the tube
+quantiles are those of the logged `tube_ratio` over the instance-steps where it was evaluated.  THETA = inf is the fixed period.
 
 Per M, one JSON line:
   ms_per_step        median over --reps runs of the wall time of the loop (first slsqp_cl_step / slsqp_cl_hold_step to the last one's return; the
@@ -36,8 +41,12 @@ def main():
     ap.add_argument("--M", type=int, nargs="+", default=[1, 2, 3, 5])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--persistent", action="store_true", help="one persistent launch per run instead of one launch sequence per step")
+    ap.add_argument("--trigger", type=float, default=None, help="theta of the event-triggered schedule (with --persistent and M > 1; inf or absent: the fixed period)")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose package is measured")
     a = ap.parse_args()
+    triggered = a.trigger is not None and a.trigger < float("inf")
+    if triggered and not a.persistent:
+        ap.error("--trigger needs --persistent: the event-triggered schedule runs in the persistent launch only")
     sys.path.insert(0, os.path.abspath(a.root))
     from robust_nonlinear_mpc_amd import ClosedLoopMPC, disturbance_stream, get_model
     m = get_model("rocket")
@@ -66,7 +75,10 @@ def main():
         runs, out = [], None
         for _ in range(a.reps + 1):      # (the first run warms the code objects and the allocator: not counted)
             if a.persistent:
-                out = cl.run_decoupled(x0, steps, W, X_nom, U_nom) if M == 1 else cl.run_decoupled(x0, steps, W, X_nom, U_nom, persistent_hold=True)
+                if M > 1 and triggered:
+                    out = cl.run_decoupled(x0, steps, W, X_nom, U_nom, persistent_hold=True, hold_trigger=a.trigger)
+                else:
+                    out = cl.run_decoupled(x0, steps, W, X_nom, U_nom) if M == 1 else cl.run_decoupled(x0, steps, W, X_nom, U_nom, persistent_hold=True)
             else:
                 out = cl.run_on_device(x0, steps, W, X_nom, U_nom)
             runs.append(1e3 * (mark["t1"] - mark["t0"]) / steps)
@@ -77,10 +89,22 @@ def main():
         solved = np.arange(steps) % M == 0
         rec = dict(M=M, batch=B, N=N, steps=steps, nlp_ok=nlp_ok, ms_per_step=float(np.median(runs)), ms_per_step_runs=[round(r, 4) for r in runs],
                    solved_ok=float(out["success"][:, solved].mean()), inside_box=float(inside.mean()))
+        if "solve_trigger" in out:      # every instance on its own schedule
+            did = out["hold_index"] == 0
+            trig, r = out["solve_trigger"], out["tube_ratio"]
+            ev = np.zeros_like(did)
+            ev[:, 1:] = out["success"][:, :-1]
+            per = r[ev]
+            rec.update(trigger=a.trigger, solved_ok=float(out["success"][did].mean()), solved_share=float(did.mean()),
+                       solved_by_reason={str(c): float(np.mean(trig == c)) for c in (1, 2, 3)}, policy_ran=float(out["hold_policy"][~did].mean()) if (~did).any() else 0.0,
+                       inside_box_hold_steps=float(inside[~did].mean()) if (~did).any() else 0.0, inside_box_solved_steps=float(inside[did].mean()),
+                       tube_nonfinite=int(np.sum(~np.isfinite(per))))
+            per = per[np.isfinite(per)]
+            rec.update(tube_ratio_max=float(per.max()), tube_ratio_p50=float(np.median(per)), tube_ratio_p99=float(np.quantile(per, 0.99)), tube_exceeded=float(np.mean(per > 1.0)))
         if a.persistent:
             ls = out["loop_stats"]
             rec.update(persistent=True, loop_stats=ls, waves_busy=float(ls["busy_ms"] / max(1e-9, ls["waves"] * runs[-1] * steps)))
-        if M > 1:
+        if M > 1 and "solve_trigger" not in out:
             per, at = [], None
             for i in np.nonzero(~solved)[0]:
                 k = i % M
