@@ -55,6 +55,8 @@ def main():
     ap.add_argument("--hold-trigger", type=float, default=None, metavar="THETA",
                     help="with --persistent 1 and --solve-every M > 1 (rti = 1 with one fast-SLS step: the rocket): an instance holds while its measured state stays "
                     "inside THETA x the tube of its plan and solves when it does not, or after M steps at the latest")
+    ap.add_argument("--plan-fallback", action="store_true",
+                    help="a step that applies no freshly certified plan (a failed solve, a hold step) runs the tube policy of the run's last plan that succeeded")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -109,7 +111,7 @@ def main():
         except ValueError as e:
             ap.error(str(e))
     cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P, bounds=bounds,
-                       solve_every=a.solve_every)
+                       solve_every=a.solve_every, plan_fallback=a.plan_fallback)
     t0 = time.perf_counter()
     run = cl.run_decoupled if a.persistent else cl.run_on_device
     kw = {} if a.hold_trigger is None else dict(hold_trigger=a.hold_trigger, **(dict(persistent_hold=True) if a.persistent else {}))
@@ -119,6 +121,10 @@ def main():
     dist1 = np.linalg.norm(out["state_trajectory"][:, :, -1] - m.x_ref, axis=1).mean()
     print(f"{a.model}: {B} runs x {steps} MPC steps (N={N}, rti={cl.rti}) in {dt:.2f} s; nominal NLP solved for {np.mean(cl.nlp_status == 0):.3f}; "
           f"MPC steps solved {out['success'].mean():.3f}; mean |x - x_ref| {dist0:.3f} -> {dist1:.3f}; QP {out['t_qp'].sum():.0f} ms, sweeps {out['t_riccati'].sum():.0f} ms")
+    if "plan_age" in out:
+        pol = out["hold_policy"]
+        print(f"plan fallback: {np.mean(pol == 2):.4f} of the steps were failed solves that ran the last certified plan's policy; "
+              f"failed solves left with the nominal input: {np.mean((out['hold_index'] == 0) & ~out['success'] & (pol == 0)):.4f}")
     if a.solve_every > 1:
         held = out["hold_index"] > 0
         print(f"solve every {a.solve_every} steps: {held.mean():.3f} of the steps held; the tube policy ran on {out['hold_policy'][held].mean():.3f} of them "

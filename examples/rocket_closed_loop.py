@@ -49,6 +49,8 @@ def main():
     ap.add_argument("--hold-trigger", type=float, default=None, metavar="THETA",
                     help="with --persistent 1 and --solve-every M > 1: a seed's controller holds while its measured state stays inside THETA x the tube of its plan "
                     "and solves when it does not, or after M steps at the latest")
+    ap.add_argument("--plan-fallback", action="store_true",
+                    help="a step that applies no freshly certified plan (a failed solve, a hold step) runs the tube policy of the seed's last plan that succeeded")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model("rocket")
@@ -61,7 +63,7 @@ def main():
     t0 = time.perf_counter()
     r = run_monte_carlo(m, a.N, np.arange(a.seeds), a.steps, x0, solve_nominal=(a.init == "sqp"), slices=a.slices, continuation=a.continuation,
                         budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P, solve_every=a.solve_every,
-                        persistent=None if a.persistent is None else bool(a.persistent), hold_trigger=a.hold_trigger)
+                        persistent=None if a.persistent is None else bool(a.persistent), hold_trigger=a.hold_trigger, plan_fallback=a.plan_fallback)
     dt = time.perf_counter() - t0
     ok = r["success"]
     if "nlp_status" in r:
@@ -76,6 +78,10 @@ def main():
         viol = np.maximum(X - m.x_ub[None, :, None], m.x_lb[None, :, None] - X).max(axis=1)
         print(f"solve every {a.solve_every} steps: {held.mean():.3f} of the steps held, the tube policy ran on {r['hold_policy'][held].mean():.3f} of them; "
               f"measured states outside the state box: {np.mean(viol > 0):.4f} of the steps")
+    if "plan_age" in r:
+        pol = r["hold_policy"]
+        print(f"plan fallback: {np.mean(pol == 2):.4f} of the steps were failed solves that ran the last certified plan's policy (plan age there: median "
+              f"{np.median(r['plan_age'][pol == 2]) if np.any(pol == 2) else 0:g}); failed solves left with the nominal input: {np.mean((r['hold_index'] == 0) & ~ok & (pol == 0)):.4f}")
     if "solve_trigger" in r:
         by = [float(np.mean(r["solve_trigger"] == c)) for c in (1, 2, 3)]
         print(f"hold trigger {a.hold_trigger:g}: steps solved on schedule {by[0]:.3f}, because the state left {a.hold_trigger:g} x tube {by[1]:.3f}, after a failed solve {by[2]:.3f}")

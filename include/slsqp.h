@@ -312,6 +312,25 @@ double slsqp_cl_get_hold_trigger(slsqp_handle *h);
    plan (scp_success = 0).  For a step-by-step caller that decides itself (for the whole batch) when to solve.  The refusals are those of
    slsqp_cl_hold_step; the call changes nothing in the handle. */
 int slsqp_cl_tube_ratio(slsqp_handle *h, double *out, int loc);
+/* Plan fallback: what a closed-loop step does when it applies no freshly certified plan.  A property of the handle, default 0 = off: every launch and
+   every bit as without the call.  on = 1: per instance a BACKUP of its last plan that succeeded (A, Bm, the compact gains Kc, backoff_x) and plan_age,
+   the plant steps since that plan pinned its stage 0 (-1: no backup, the state after slsqp_cl_init; 0 right after a solve with scp_success = 1).
+       a solve that succeeds      applies nominal_u[0] as ever; the plan is copied into the backup, plan_age = 0
+       a solve that fails, or     k = plan_age + 1.  Backup present and k <= N - 1 (K has N rows): hold step k of the BACKUP -- the formulas of
+       a hold step                slsqp_cl_hold_step with the backup's A_{k-1}, B_{k-1}, K[k-1,j], K[k,j]; z_k, v_k are stage 0 of the live nominal (a failed
+                                  step leaves the shifted plan untouched); plan_age = k.  Otherwise the nominal input, xi as without the option,
+                                  plan_age = -1.
+   The schedule (solve_every, hold_trigger, hold_index, the solve_trigger codes) does not change; after a solve that succeeded the backup equals the live
+   arrays and plan_age the hold index, so those hold steps keep their bits.  The input is not clipped.  hold_policy / log_hold_policy: 2 on a failed
+   solve that ran the backup's policy, 1 on a hold step that ran it, 0 where the nominal input was applied.
+   Read by slsqp_cl_step and slsqp_cl_hold_step (one more launch; the hold index of slsqp_cl_hold_step's refusals stays the batch's) and by slsqp_cl_run
+   in the persistent launch, M = 1 included.  It needs rti = 1 with one fast-SLS step (the gains are then the compact ones; the full K is not kept):
+   slsqp_cl_step and slsqp_cl_run_scp with other settings and the round-based slsqp_cl_run refuse while it is on (< 0, slsqp_last_error).
+   Values other than 0 / 1 are refused and change nothing.
+   Results (slsqp_get): plan_age[int32] (1), plan_A (N,nx,nx), plan_Bm (N,nx,nu), plan_Kc (N,nu,nx), plan_backoff_x (N+1,nx); with slsqp_cl_log
+   log_plan_age[int32] (S): the age every step left behind (zeros from a handle with the option off). */
+int slsqp_cl_set_plan_fallback(slsqp_handle *h, int on);
+int slsqp_cl_get_plan_fallback(slsqp_handle *h);
 /* The whole closed loop with the instances advancing INDEPENDENTLY (rti = 1, one fast-SLS step, fp64, fuse_rti: the rocket script's setting):
    `steps` MPC steps of every instance, W (steps,B,nx) disturbance samples or NULL.  Per instance the same operations in the same order as `steps`
    calls of slsqp_cl_step (identical results), but in rounds: in a round an instance begins its next MPC step or resumes the QP solve that the

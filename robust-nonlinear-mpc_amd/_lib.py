@@ -58,6 +58,7 @@ EXPORTS = [
     "slsqp_plant_param_count", "slsqp_plant_param_name", "slsqp_plant_param_defaults", "slsqp_cl_set_plant_params", "slsqp_cl_set_bounds",
     "slsqp_cl_hold_step", "slsqp_cl_set_solve_every", "slsqp_cl_get_solve_every",
     "slsqp_cl_set_hold_trigger", "slsqp_cl_get_hold_trigger", "slsqp_cl_tube_ratio",
+    "slsqp_cl_set_plan_fallback", "slsqp_cl_get_plan_fallback",
 ]
 
 _lib = None
@@ -116,6 +117,8 @@ def load():
     lib.slsqp_cl_get_hold_trigger.argtypes = [vp]
     lib.slsqp_cl_get_hold_trigger.restype = C.c_double
     lib.slsqp_cl_tube_ratio.argtypes = [vp, dp, C.c_int]
+    lib.slsqp_cl_set_plan_fallback.argtypes = [vp, C.c_int]
+    lib.slsqp_cl_get_plan_fallback.argtypes = [vp]
     lib.slsqp_nominal_solve.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.POINTER(Opts)]
     lib.slsqp_cl_log.argtypes = [vp, C.c_int]
     lib.slsqp_cl_run.argtypes = [vp, C.c_int, dp, C.c_int, C.POINTER(Opts), C.c_double, C.c_double, C.POINTER(C.c_int)]

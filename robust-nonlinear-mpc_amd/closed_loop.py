@@ -22,7 +22,7 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
         state never fails a step on its own (slsqp_set_x0_box_tol).
@@ -34,7 +34,12 @@ class ClosedLoopMPC:
         solve_every: M of run / run_on_device / run_decoupled: the controller solves at steps 0, M, 2M, ... and holds its plan in between
         (hold_step: the tube policy of the last solve acts on the measured state); 1 <= M <= N; 1 (default): a solve at every step.
         hold_trigger: theta of run_decoupled(..., persistent_hold=True): an instance holds while its measured state stays inside theta x the tube of
-        its plan and solves when it does not, or after M steps at the latest; None or inf (default): off, the fixed period."""
+        its plan and solves when it does not, or after M steps at the latest; None or inf (default): off, the fixed period.
+        plan_fallback: True: a step that applies no freshly certified plan (a solve that failed, a hold step) runs the tube policy of the instance's
+        last plan that succeeded, from a per-instance backup, while that plan has rows left (BatchedFastSLS.set_plan_fallback; rti = 1 with one
+        fast-SLS step).  Honoured by step / hold_step, run, run_on_device and run_decoupled (the persistent launch with persistent_hold=True or M = 1,
+        else step by step); their results then hold `plan_age` (B, steps), `hold_index` and `hold_policy` (B, steps) as int32 codes: 2 a failed solve
+        that ran the backup's policy, 1 a hold step that ran it, 0 the nominal input.  False (default): every launch and every bit as before."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -50,6 +55,9 @@ class ClosedLoopMPC:
         self.steps_done = 0
         self.solve_every = self._check_solve_every(solve_every)
         self.hold_trigger = self._check_hold_trigger(hold_trigger, first=True)
+        self.plan_fallback = bool(plan_fallback)
+        if self.plan_fallback:
+            self.f.set_plan_fallback(True)
         if reference is not None:
             self.set_reference(reference)
         if plant_params is not None:
@@ -163,7 +171,21 @@ class ClosedLoopMPC:
             scp_iterations=f.get("scp_iterations", (), np.int32), primal_infeasibility=f.get("primal_infeasibility", ()),
             x0_violation=np.where(f.get("qp_stats", (2, 8), np.int32)[:, :, 6] == -1, 0.0, f.get("x0_viol", (2,))),      # (0 where the QP took no part, as in the log)
             t_qp_ms=f.timing_ms()["qp"], t_riccati_ms=f.timing_ms()["sweep"], t_jac_ms=f.timing_ms()["jac"],
+            **self._fallback_keys(solved=True),
         )
+
+    def _fallback_keys(self, solved):
+        """plan_fallback: what the step left -- `plan_age`, and on a solved step `hold_policy` (2 where a failed solve ran the backup's policy) and the
+        measured state the input was computed for is the caller's to keep; nothing without the option."""
+        if not self.plan_fallback:
+            return {}
+        f = self.f
+        out = dict(plan_age=f.get("plan_age", (), np.int32))
+        if solved:
+            out.update(hold_index=np.zeros(self.B, dtype=np.int32), hold_policy=np.where(f.get("scp_success", (), np.int32) != 0, 0, f.get("hold_policy", (), np.int32)).astype(np.int32))
+        else:
+            out.update(hold_policy=f.get("hold_policy", (), np.int32))
+        return out
 
     def hold_step(self, w=None, fetch=True):
         """One closed-loop step of the whole batch without a solve (BatchedFastSLS.hold_step): the plan of the last step() is held, its tube policy
@@ -178,7 +200,7 @@ class ClosedLoopMPC:
         self._W_log.append(wv)
         if not fetch:
             return None
-        return dict(
+        out = dict(
             u0=f.get("u0", (m.nu,)), x_next=f.get("x_meas", (m.nx,)), state=state,
             nominal_x=f.get("nominal_x", (N + 1, m.nx)), nominal_u=f.get("nominal_u", (N, m.nu)),
             backoff_x=f.get("backoff_x", (N + 1, m.nx)), backoff_u=f.get("backoff_u", (N, m.nu)),
@@ -187,6 +209,8 @@ class ClosedLoopMPC:
             x0_violation=np.zeros((self.B, 2)), hold_index=f.get("hold_index", (), np.int32), hold_policy=f.get("hold_policy", (), np.int32).astype(bool),
             t_qp_ms=0.0, t_riccati_ms=0.0, t_jac_ms=0.0,
         )
+        out.update(self._fallback_keys(solved=False))      # (plan_fallback: the policy as its code, and plan_age)
+        return out
 
     def run_on_device(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, solve_every=None, hold_trigger=None):
         """Same result as run(), but the per-step records stay in device buffers (slsqp_cl_log) and are read back once at the end: the only
@@ -205,8 +229,17 @@ class ClosedLoopMPC:
             t = f.timing_ms()
             t_qp[i], t_ric[i], t_jac[i] = t["qp"], t["sweep"], t["jac"]
         out = self._log_result(steps, t_jac, t_qp, t_ric)
-        if M > 1:
-            out.update(hold_index=f.get("log_hold", (steps,), np.int32), hold_policy=f.get("log_hold_policy", (steps,), np.int32).astype(bool))
+        if M > 1 or self.plan_fallback:
+            out.update(self._hold_log(steps))
+        return out
+
+    def _hold_log(self, steps):
+        """`hold_index` and `hold_policy` (B, steps) of a logged run; with plan_fallback the policy as its int32 code, and `plan_age`."""
+        f = self.f
+        pol = f.get("log_hold_policy", (steps,), np.int32)
+        out = dict(hold_index=f.get("log_hold", (steps,), np.int32), hold_policy=pol if self.plan_fallback else pol.astype(bool))
+        if self.plan_fallback:
+            out["plan_age"] = f.get("log_plan_age", (steps,), np.int32)
         return out
 
     def _log_result(self, steps, t_jac, t_qp, t_ric):
@@ -307,8 +340,9 @@ class ClosedLoopMPC:
             st = (C.c_double * L.CL_RUN_STATS_LEN)()
             L.check(f.lib.slsqp_cl_run_stats(f.h, st, L.CL_RUN_STATS_LEN))
             out["loop_stats"] = dict(waves=int(st[0]), busy_ms=float(st[1]), mpc_steps=int(st[2]), launch_ms=float(st[3]))
+        if hold or self.plan_fallback:
+            out.update(self._hold_log(steps))
         if hold:
-            out.update(hold_index=f.get("log_hold", (steps,), np.int32), hold_policy=f.get("log_hold_policy", (steps,), np.int32).astype(bool))
             if f.get_hold_trigger() < float("inf"):
                 out.update(tube_ratio=f.get("log_tube_ratio", (steps,)), solve_trigger=f.get("log_solve_trigger", (steps,), np.int32))
         return out
@@ -330,14 +364,20 @@ class ClosedLoopMPC:
             success=np.zeros((B, steps), dtype=bool), scp_iterations=np.zeros((B, steps), dtype=np.int32),
             primal_infeasibility=np.full((B, steps), np.nan), x0_violation=np.zeros((B, steps, 2)),
         )
-        if M > 1:
-            out.update(hold_index=np.zeros((B, steps), dtype=np.int32), hold_policy=np.zeros((B, steps), dtype=bool))
+        if M > 1 or self.plan_fallback:
+            out.update(hold_index=np.zeros((B, steps), dtype=np.int32), hold_policy=np.zeros((B, steps), dtype=np.int32 if self.plan_fallback else bool))
+        if self.plan_fallback:
+            out.update(plan_age=np.zeros((B, steps), dtype=np.int32))
         for i in range(steps):
             if i % M:
                 r = self.hold_step(None if W is None else W[i])
-                out["hold_index"][:, i], out["hold_policy"][:, i] = r["hold_index"], r["hold_policy"]
+                out["hold_index"][:, i] = r["hold_index"]
             else:
                 r = self.step(None if W is None else W[i])
+            if "hold_policy" in r and "hold_policy" in out:
+                out["hold_policy"][:, i] = r["hold_policy"]
+            if self.plan_fallback:
+                out["plan_age"][:, i] = r["plan_age"]
             out["state_trajectory"][:, :, i] = r["state"] if i % M else r["nominal_x"][:, 0, :]
             if i < steps - 1:
                 out["input_trajectory"][:, :, i] = r["u0"]

@@ -45,6 +45,22 @@ CL_HOLD_HD inline int decide(int s, int k_prev, int M, bool plan_ok, double r, d
     return TRIG_HOLD;
 }
 
+// Plan fallback (slsqp_cl_set_plan_fallback): a step that applies no freshly certified plan -- a solve that failed, or a hold
+// step -- runs the tube policy of the instance's last plan that succeeded, kept in a backup beside the live arrays.  age: plant steps since that plan
+// pinned its stage 0 (0 right after the successful solve, -1: no backup).  One definition for the host, both kernels and tests/plan_fallback_ref.py.
+CL_HOLD_HD inline bool valid_plan_fallback(int on) { return on == 0 || on == 1; }
+// the hold step of the backup such a step runs, or 0: no backup, or the backup has no row left (K has N rows: k <= N - 1)
+CL_HOLD_HD inline int fallback_index(int age, int N) { return (age >= 0 && age + 1 <= N - 1) ? age + 1 : 0; }
+// the age a step leaves behind; fresh: a solve that succeeded.  A step that found no plan marks the backup gone
+CL_HOLD_HD inline int plan_age_after(bool fresh, int age, int N) {
+    if (fresh) return 0;
+    const int k = fallback_index(age, N);
+    return k ? k : -1;
+}
+enum Policy { POLICY_NOMINAL = 0, POLICY_HOLD = 1, POLICY_FALLBACK = 2 };
+// hold_policy / log_hold_policy of a step that applied no fresh plan: k = fallback_index of the age it found; hold_step: the schedule made it a hold step
+CL_HOLD_HD inline int policy_code(bool hold_step, int k) { return k ? (hold_step ? POLICY_HOLD : POLICY_FALLBACK) : POLICY_NOMINAL; }
+
 struct State {
     int k = 0;              // index of the last hold step (1 = the first plant step after a solve)
     int at_steps = -1;      // the handle's step count right after that hold step (-1: none since slsqp_cl_init)

@@ -25,7 +25,7 @@ struct HoldArgs {
     const int *scp_success;     // (B) outcome of the last slsqp_cl_step: 0 = no valid plan, the instance applies v_k
     double *xi;                 // (B,N+1,NX) column states, row j = xi_j
     double *u;                  // (B,NU) the input the plant step applies
-    int *policy;                // (B) 1: the policy ran, 0: the nominal input was applied
+    int *policy;                // (B) 1: the policy ran, 0: the nominal input was applied (plan fallback: 2 = a failed solve ran the backup's policy)
     int S, step;                // the closed-loop log (S = 0: off) and the entry of this step
     double *lstate, *lu0, *lx0v;
     int *lit, *lhold, *lpol;
@@ -44,20 +44,22 @@ constexpr int cl_hold_lds_doubles() {      // sA | sB | sXi | sY
     return NX * NX + NX * NU + 64 * NX + (64 / NX) * NU;
 }
 // xi, u and policy of hold step k of instance b (a.k is not read); ends with u in global memory for every lane of the wave
+// plan (wave-uniform; plan fallback): 0 -- the plan is the live one, valid when the last solve succeeded, gains where stale says;
+// > 0 -- a.A / a.Bm / a.Kc are the backup, valid, its gains compact, and `plan` is the policy code to record; < 0 -- no plan (k: the schedule's index)
 template <int MODEL>
-__device__ __forceinline__ void cl_hold_wave(const HoldArgs &a, int b, int lane, int k, double *sm) {
+__device__ __forceinline__ void cl_hold_wave(const HoldArgs &a, int b, int lane, int k, double *sm, int plan = 0) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU, G = 64 / NX;
     static_assert(NU <= NX && G >= 1, "row i of y lives on lane i of a column's group");
     double *sA = sm, *sB = sA + NX * NX, *sXi = sB + NX * NU, *sY = sXi + 64 * NX;
     const int N = a.cl.N;
     double *xi = a.xi + (size_t)b * (N + 1) * NX;
     const double *Un0 = a.cl.Un + (size_t)b * N * NU;
-    const bool ok = a.scp_success[b] != 0;
+    const bool ok = plan ? plan > 0 : a.scp_success[b] != 0;
     if (!ok) {      // no valid plan: the shifted nominal input, as a failed solved step applies it; xi stays (all zero from the first hold step on)
         if (k == 1) for (int o = lane; o < (N + 1) * NX; o += 64) xi[o] = 0.0;
         if (lane < NU) a.u[(size_t)b * NU + lane] = Un0[lane];
     } else {
-        const int st = a.stale[b];
+        const int st = plan ? 32 : a.stale[b];
         const bool compact = st & 32, zeroK = !compact && (st & 2);
         const double *Kb = a.K + (size_t)b * N * (N + 1) * NU * NX, *Kcb = a.Kc + (size_t)b * N * NU * NX;
         auto gain = [&](int kk, int j) { return compact ? Kcb + (size_t)kk * NU * NX : Kb + ((size_t)kk * (N + 1) + j) * NU * NX; };
@@ -116,7 +118,7 @@ __device__ __forceinline__ void cl_hold_wave(const HoldArgs &a, int b, int lane,
             if (lane == c) a.u[(size_t)b * NU + c] = Un0[c] + s;
         }
     }
-    if (lane == 0) a.policy[b] = ok ? 1 : 0;
+    if (lane == 0) a.policy[b] = ok ? (plan > 0 ? plan : 1) : 0;
     wla::wsync_mem();      // u is in global memory for lane 0's plant step and for the log
 }
 // entry `step` of the closed-loop log as a hold step leaves it (a.S = 0: no log; a.step is not read): state and applied input of this step; no
@@ -125,11 +127,11 @@ template <int MODEL>
 __device__ __forceinline__ void cl_hold_log(const HoldArgs &a, int b, int lane, int k, int step) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     if (a.S > 0 && step < a.S) {
-        const bool ok = a.scp_success[b] != 0;
+        const int pol = a.policy[b];      // (cl_hold_wave's, behind its barrier)
         const size_t e = (size_t)b * a.S + step;
         if (lane < NX) a.lstate[e * NX + lane] = a.cl.xmeas[(size_t)b * NX + lane];
         if (lane < NU) a.lu0[e * NU + lane] = a.u[(size_t)b * NU + lane];
-        if (lane == 0) { a.lit[e] = 0; a.lhold[e] = k; a.lpol[e] = ok ? 1 : 0; a.lx0v[e * 2] = 0.0; a.lx0v[e * 2 + 1] = 0.0; }
+        if (lane == 0) { a.lit[e] = 0; a.lhold[e] = k; a.lpol[e] = pol; a.lx0v[e * 2] = 0.0; a.lx0v[e * 2 + 1] = 0.0; }
         wla::wsync_mem();      // the state is logged before lane 0 replaces it
     }
 }
@@ -166,6 +168,87 @@ __global__ __launch_bounds__(64) void k_cl_hold(HoldArgs a, PlantArgs pa) {
         c.N = 1; c.Un = a.u;      // "the first nominal input" of instance b is u[b]: the nominal itself stays the plan
         cl_plant_one<MODEL, PP>(c, b, a.cl.w, PP ? &pa : nullptr, a.step);
     }
+}
+
+// ---- plan fallback (slsqp_cl_set_plan_fallback) ---------------------------------------------------------------------------
+// The live plan of the instances, the backup of each one's last plan that succeeded (same shapes), the age of that backup (cl_hold.hpp) and its
+// per-step log.  With the option on, the HoldArgs beside this struct carry the BACKUP in A / Bm / Kc: every policy step reads the backup store.
+struct PlanArgs {
+    int on;
+    const double *A, *Bm, *Kc, *backoff_x;      // (B,N,NX,NX) (B,N,NX,NU) (B,N,NU,NX) (B,N+1,NX)
+    double *bA, *bB, *bKc, *bbo;
+    int *age;                                   // (B)
+    int *lage;                                  // (B,S) or NULL
+};
+// n doubles, coalesced; 16-byte accesses where both addresses allow them (a per-instance block is only 8-byte aligned for an odd count)
+__device__ __forceinline__ void cl_copy_wave(const double *s, double *d, int n, int lane) {
+    if (((((size_t)s) | ((size_t)d)) & 15) == 0) {
+        const double2 *s2 = (const double2 *)s;
+        double2 *d2 = (double2 *)d;
+        const int n2 = n >> 1;
+#pragma unroll 4
+        for (int o = lane; o < n2; o += 64) d2[o] = s2[o];
+        if ((n & 1) && lane == 0) d[n - 1] = s[n - 1];
+    } else {
+#pragma unroll 4
+        for (int o = lane; o < n; o += 64) d[o] = s[o];
+    }
+}
+// one wave copies the plan its instance's solve has just certified into the backup; pure streaming, no LDS
+template <int MODEL>
+__device__ __forceinline__ void cl_plan_save_wave(const PlanArgs &f, int b, int lane, int N) {
+    constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    const size_t oA = (size_t)b * N * NX * NX, oB = (size_t)b * N * NX * NU, oX = (size_t)b * (N + 1) * NX;
+    cl_copy_wave(f.A + oA, f.bA + oA, N * NX * NX, lane);
+    cl_copy_wave(f.Bm + oB, f.bB + oB, N * NX * NU, lane);
+    cl_copy_wave(f.Kc + oB, f.bKc + oB, N * NU * NX, lane);
+    cl_copy_wave(f.backoff_x + oX, f.bbo + oX, (N + 1) * NX, lane);
+}
+// What the step of instance b does under the option, sched_k its index in the schedule (0: a solve, whose outcome is a.scp_success).  A solve that
+// succeeded: the plan goes into the backup, age 0, the first nominal input goes into u verbatim.  Every other step: k = cl_hold::fallback_index of the
+// age -- the caller runs cl_hold_wave(a, b, lane, *kk, sm, *plan) when this returns true (hold step k of the backup, or today's hold step without a
+// plan), a failed solve without a plan applies the nominal input.  The age is written here; *age_out: the value, *code: the policy code of the step.
+template <int MODEL>
+__device__ __forceinline__ bool cl_fallback_begin(const HoldArgs &a, const PlanArgs &f, int b, int lane, int sched_k, int *kk, int *plan, int *age_out, int *code) {
+    constexpr int NU = dyn::Dims<MODEL>::NU;
+    const int N = a.cl.N;
+    const bool fresh = sched_k == 0 && a.scp_success[b] != 0;
+    const int age = f.age[b];
+    const int kf = fresh ? 0 : cl_hold::fallback_index(age, N);
+    *age_out = cl_hold::plan_age_after(fresh, age, N);
+    *code = cl_hold::policy_code(sched_k != 0, kf);
+    if (fresh) cl_plan_save_wave<MODEL>(f, b, lane, N);
+    if (lane == 0) f.age[b] = *age_out;
+    if (kf) { *kk = kf; *plan = *code; return true; }
+    if (sched_k) { *kk = sched_k; *plan = -1; return true; }
+    if (lane < NU) a.u[(size_t)b * NU + lane] = a.cl.Un[(size_t)b * N * NU + lane];
+    if (lane == 0 && !fresh) a.policy[b] = 0;
+    wla::wsync_mem();      // u is in global memory for the plant step and for the log
+    return false;
+}
+// entry `step` of the log under the option: the age the step left; on a solved step also the input that was applied and the policy code (a hold
+// step's are cl_hold_log's)
+template <int MODEL>
+__device__ __forceinline__ void cl_fallback_log(const HoldArgs &a, const PlanArgs &f, int b, int lane, int step, bool held, int age, int code) {
+    constexpr int NU = dyn::Dims<MODEL>::NU;
+    if (a.S > 0 && step < a.S) {
+        const size_t e = (size_t)b * a.S + step;
+        if (!held && lane < NU) a.lu0[e * NU + lane] = a.u[(size_t)b * NU + lane];
+        if (lane == 0) { if (!held) a.lpol[e] = code; f.lage[e] = age; }
+    }
+}
+// slsqp_cl_step and slsqp_cl_hold_step under the option, one wave per instance, behind the step's other launches (k_cl_scp_update / k_cl_infeas /
+// k_cl_log; the shift and k_cl_log of a hold step): u (B,NU) receives the input to apply for EVERY instance, and the plant launch that follows takes it
+// as "the first nominal input" of a one-stage plan.  sched_k: 0 for a solved step, the batch's hold index for a hold step.
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_cl_plan_fallback(HoldArgs a, PlanArgs f, int sched_k) {
+    __shared__ double sm[cl_hold_lds_doubles<MODEL>()];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= a.cl.B) return;
+    int kk = 0, plan = 0, age = -1, code = 0;
+    if (cl_fallback_begin<MODEL>(a, f, b, lane, sched_k, &kk, &plan, &age, &code)) cl_hold_wave<MODEL>(a, b, lane, kk, sm, plan);
+    if (sched_k) cl_hold_log<MODEL>(a, b, lane, sched_k, a.step);
+    cl_fallback_log<MODEL>(a, f, b, lane, a.step, sched_k != 0, age, code);
 }
 
 }  // namespace slsqp

@@ -79,7 +79,11 @@ struct slsqp_handle {
     int solve_every = 1;        // slsqp_cl_set_solve_every: M of slsqp_cl_run -- a solve at steps 0, M, 2M, ... of every instance, hold steps in between (1: a solve at every step)
     double hold_trigger = INFINITY;      // slsqp_cl_set_hold_trigger: theta of slsqp_cl_run with solve_every > 1 -- an instance holds while its tube ratio is <= theta (+inf: off, the fixed period)
     int *hold_k = nullptr, *lg_trig = nullptr; double *lg_ratio = nullptr;      // (B) per-instance hold index of an event-triggered run (ensure_hold); its per-step reason codes and ratios (slsqp_cl_log)
-    std::vector<unsigned char> hold_blk_host;      // the HoldLoopArgs the host last wrote behind the ScpLoopArgs of loop_blk (runs with solve_every > 1 only)
+    // slsqp_cl_set_plan_fallback: the backup of every instance's last plan that succeeded, one buffer
+    // [A (B,N,nx,nx) | Bm (B,N,nx,nu) | Kc (B,N,nu,nx) | backoff_x (B,N+1,nx)] allocated by the first step that needs it (ensure_plan), its age, the age's log
+    int plan_fallback = 0; double *plan_bk = nullptr; int *plan_age = nullptr, *lg_age = nullptr;
+    int plan_blk_dev = 0; std::vector<unsigned char> plan_blk_host;      // whether the PlanArgs in loop_blk (PLAN_BLK_OFFSET) say "on"; the bytes the host last wrote there
+    std::vector<unsigned char> hold_blk_host;    // the HoldLoopArgs the host last wrote behind the ScpLoopArgs of loop_blk (runs with solve_every > 1 only)
     int solve_waves = 1;        // slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = k_qp_solve_mw (one workgroup of that many waves per instance)
     double *ref_Y = nullptr; int ref_T = 0; size_t ref_stride = 0;      // slsqp_cl_set_reference: packed rows [x_ref; u_ref] (T, nz), per instance with ref_stride = T nz, shared with 0; ref_T = 0: none
     double *zero_ref = nullptr;      // (nz) zeros: the one-row reference the persistent kernels take for a handle with parameters or bounds and no reference (cl_options)
@@ -131,12 +135,15 @@ constexpr bool var_hold(int VAR) { return VAR & VAR_HOLD; }
 // What a handle has set, asked by every launch site: ref / pp / bnd are the handle's own (the flags of the batch-wide kernels: REF and BND of k_lin_vec
 // and k_nom_eval, BND of k_tighten and k_rti_chain, pp for the plant step) and own_rf the handle's own reference, empty without one (what those two
 // kernels take); var, rf, pa are what the persistent kernels take (rf: own_rf, else the zero row where var has the REF bit, else empty; pa: empty
-// without parameters).  hold: the handle's solve_every is above 1 (read by slsqp_cl_run alone: slsqp_cl_step and slsqp_cl_hold_step ignore the setting).
-struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; bool hold; };
+// without parameters).  hold: the handle's solve_every is above 1 (read by slsqp_cl_run alone: slsqp_cl_step and slsqp_cl_hold_step ignore the setting)
+// or plan fallback is on.
+// fallback: slsqp_cl_set_plan_fallback is on -- a run-time branch inside the HOLD variants, which a run with M = 1 then launches too.
+struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; bool hold; bool fallback; };
 static ClOptions cl_options(const slsqp_handle *h) {
     ClOptions o{};
     o.ref = h->ref_T > 0; o.pp = h->pp_P != nullptr; o.bnd = h->bnd_rows != nullptr;
-    o.hold = h->solve_every > 1;
+    o.fallback = h->plan_fallback != 0;
+    o.hold = h->solve_every > 1 || o.fallback;
     o.var = ((o.ref || o.pp || o.bnd || o.hold) ? VAR_REF : 0) | (o.pp ? VAR_PP : 0) | (o.bnd ? VAR_BND : 0) | (o.hold ? VAR_HOLD : 0);
     if (o.ref) o.own_rf = RefArgs{h->ref_Y, h->ref_T, h->ref_stride};
     o.rf = (o.var && !o.ref) ? RefArgs{h->zero_ref, 1, 0} : o.own_rf;
@@ -346,6 +353,7 @@ extern "C" slsqp_handle *slsqp_create(const slsqp_dims *d, int batch, int device
     reg("K", h->K, sizeof(double) * N * (N + 1) * nu * nx); reg("ubg", h->ubg, sizeof(double) * h->mb); reg("lbg", h->lbg, sizeof(double) * h->mb);
     reg("kkt", h->kkt, sizeof(double) * 8); reg("cost_tube", h->cost_tube, sizeof(double));
     reg("nominal_x", h->Xn, sizeof(double) * (N + 1) * nx); reg("nominal_u", h->Un, sizeof(double) * N * nu); reg("x_meas", h->xmeas, sizeof(double) * nx); reg("u0", h->u0, sizeof(double) * nu);
+    reg("Kc", h->Kc, sizeof(double) * N * nu * nx);      // the compact gains of the shared Riccati recursion (K[k,j] = Kc[k], j <= k, where stale has bit 32)
     reg("A", h->A, sizeof(double) * N * nx * nx); reg("Bm", h->Bm, sizeof(double) * N * nx * nu); reg("c", h->c, sizeof(double) * N * nx);
     reg("g", h->g, sizeof(double) * N * ni); reg("gN", h->gN, sizeof(double) * nif); reg("q", h->q, sizeof(double) * h->n); reg("pin_dual", h->pin_dual, sizeof(double) * nx);
     reg("chain_times", h->chain_times, sizeof(unsigned long long) * 4); reg("primal_infeasibility", h->pinf, sizeof(double)); reg("qp_stats", h->qpstat, sizeof(int) * 16); h->x0viol = x0_record(h->kkt, h->B) + 2; reg("x0_viol", h->x0viol, sizeof(double) * 2); reg("x0_arg", h->x0arg, sizeof(double) * nx);
@@ -367,6 +375,8 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     opt_clear(&h->ref_Y); opt_clear(&h->pp_P); opt_clear(&h->bnd_rows);
     if (h->hold_xi) hipFree(h->hold_xi);
     if (h->hold_policy) hipFree(h->hold_policy);
+    if (h->plan_bk) hipFree(h->plan_bk);
+    if (h->plan_age) hipFree(h->plan_age);
     if (h->qplog) hipFree(h->qplog);
     if (h->x0vlog) hipFree(h->x0vlog);
     if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
@@ -878,12 +888,18 @@ struct ScpLoopArgs {
 // every offset (bd stays its last field, tests/loop_args_check_main.cpp), and a run with M = 1 writes and reads the bytes it always did.
 // Event-triggered runs (slsqp_cl_set_hold_trigger) read the fields behind M: theta (+inf: off -- none of the others is read),
 // the last solve's backoff_x, the per-instance hold index that replaces hold_index_at(stepno, M), and the log of ratio and reason code.
+// Plan fallback (slsqp_cl_set_plan_fallback) reads a PlanArgs BEHIND this struct in the same block, at PLAN_BLK_OFFSET: this struct
+// keeps its size and every offset.  on = 0 (the default): none of its other fields is read.  With it on, a.A / a.Bm / a.Kc and backoff_x here are the
+// backup's: every policy step and the trigger's ratio read the backup store.
 struct HoldLoopArgs { HoldArgs a; int M; double theta; const double *backoff_x; int *hold_k; double *lratio; int *ltrig; };
 // the hold index of instance b at its step s: the one the wave that ran step s - 1 decided, or the fixed period's (wave-uniform)
 __device__ __forceinline__ int loop_hold_index(const HoldLoopArgs &H, int b, int s) { return cl_hold::trigger_on(H.theta, H.M) ? H.hold_k[b] : cl_hold::hold_index_at(s, H.M); }
 constexpr size_t HOLD_BLK_OFFSET = (sizeof(ScpLoopArgs) + 15) & ~(size_t)15, LOOP_BLK_BYTES = 4096;
 static_assert(HOLD_BLK_OFFSET + sizeof(HoldLoopArgs) <= LOOP_BLK_BYTES, "slsqp_handle::loop_blk is 4096 bytes");
 __device__ __forceinline__ const HoldLoopArgs *hold_blk(const ScpLoopArgs *blk) { return (const HoldLoopArgs *)((const unsigned char *)blk + HOLD_BLK_OFFSET); }
+constexpr size_t PLAN_BLK_OFFSET = (HOLD_BLK_OFFSET + sizeof(HoldLoopArgs) + 15) & ~(size_t)15;
+static_assert(PLAN_BLK_OFFSET + sizeof(PlanArgs) <= LOOP_BLK_BYTES, "slsqp_handle::loop_blk is 4096 bytes");
+__device__ __forceinline__ const PlanArgs *plan_blk_of(const HoldLoopArgs *hp) { return (const PlanArgs *)((const unsigned char *)hp + (PLAN_BLK_OFFSET - HOLD_BLK_OFFSET)); }
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
 // HOLD (k_cl_loop's hold variants): held != 0 is a hold step of the instance, which takes the shift alone -- no solver reset, so stale, itnum, q
@@ -935,25 +951,17 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
 #ifdef CL_LOOP_STAMP
     unsigned long long ts_ = wall_clock64();
 #endif
-    bool held = false;
+    bool held = false, fb = false;      // HOLD: a hold step; plan fallback is on (wave-uniform)
     int kprev = 0;      // HOLD: the hold index of this step
     if constexpr (HOLD) {
         const HoldLoopArgs &H = args_here<true>(hp);
-        const int k = loop_hold_index(H, b, s);
-        kprev = k;
-        if (k) {
-            held = true;
-            if (L.have_log) {
-                const int per = 2 * ((L.lg.N + 1) * L.lg.NX + L.lg.N * L.lg.NU);
-                for (int o = lane; o < per; o += 64) cl_log_item(L.lg, b, o);
-                wla::wsync_mem();      // (lu0 of the entry is written again below, by other lanes)
-            }
-            cl_hold_wave<MODEL>(H.a, b, lane, k, sm);
-            cl_hold_log<MODEL>(H.a, b, lane, k, s);
-            if (L.c.qplog && s < L.c.log_steps) {      // no QP took part in this step: status -1 in both slots, 0 everywhere else, no stage-0 record
-                if (lane < 16) L.c.qplog[((size_t)b * L.c.log_steps + s) * 16 + lane] = (lane & 7) == 6 ? -1 : 0;
-                if (lane >= 16 && lane < 18) L.c.x0vlog[((size_t)b * L.c.log_steps + s) * 2 + (lane - 16)] = 0.0;
-            }
+        kprev = loop_hold_index(H, b, s);
+        held = kprev != 0;
+        fb = args_here<true>(plan_blk_of(hp)).on != 0;
+        if (held && L.have_log) {
+            const int per = 2 * ((L.lg.N + 1) * L.lg.NX + L.lg.N * L.lg.NU);
+            for (int o = lane; o < per; o += 64) cl_log_item(L.lg, b, o);
+            wla::wsync_mem();      // (lu0 of the entry is written again below, by other lanes)
         }
     }
     if (!held) {
@@ -968,13 +976,33 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
         if (L.have_log) {
             const int per = 2 * ((L.lg.N + 1) * L.lg.NX + L.lg.N * L.lg.NU);
             for (int o = lane; o < per; o += 64) cl_log_item(L.lg, b, o);
+            if constexpr (HOLD) { if (fb) wla::wsync_mem(); }      // (lu0 of the entry is written again below, by other lanes)
+        }
+    }
+    if constexpr (HOLD) {
+        // the hold function, ONE call site: a hold step runs it on the plan of the last solve; under plan fallback a solved step that failed runs it too,
+        // and both on the backup, at the index the backup's age gives (after a solve that succeeded: the schedule's index and the live plan's bits)
+        if (held || fb) {
+            const HoldLoopArgs &H = args_here<true>(hp);
+            int kk = kprev, plan = 0, age = -1, code = 0;
+            bool run = held;
+            if (fb) run = cl_fallback_begin<MODEL>(H.a, args_here<true>(plan_blk_of(hp)), b, lane, kprev, &kk, &plan, &age, &code);
+            if (run) cl_hold_wave<MODEL>(H.a, b, lane, kk, sm, plan);
+            if (held) {
+                cl_hold_log<MODEL>(H.a, b, lane, kprev, s);
+                if (L.c.qplog && s < L.c.log_steps) {      // no QP took part in this step: status -1 in both slots, 0 everywhere else, no stage-0 record
+                    if (lane < 16) L.c.qplog[((size_t)b * L.c.log_steps + s) * 16 + lane] = (lane & 7) == 6 ? -1 : 0;
+                    if (lane >= 16 && lane < 18) L.c.x0vlog[((size_t)b * L.c.log_steps + s) * 2 + (lane - 16)] = 0.0;
+                }
+            }
+            if (fb) cl_fallback_log<MODEL>(H.a, args_here<true>(plan_blk_of(hp)), b, lane, s, held, age, code);
         }
     }
     CLSTAMP(9);
     if (lane == 0) {
         if constexpr (HOLD) {
             ClArgs c = L.cl;
-            if (held) { c.N = 1; c.Un = args_here<true>(hp).a.u; }      // "the first nominal input" of instance b is u[b], as in k_cl_hold: the nominal itself stays the plan
+            if (held || fb) { c.N = 1; c.Un = args_here<true>(hp).a.u; }      // "the first nominal input" of instance b is u[b], as in k_cl_hold: the nominal itself stays the plan
             cl_plant_one<MODEL, PP>(c, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
         } else cl_plant_one<MODEL, PP>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
         L.stepno[b] = s + 1;
@@ -1833,6 +1861,21 @@ extern "C" int slsqp_kernel_timing(slsqp_handle *h, double *out8, int len) {
     return 0;
 }
 
+// Plan fallback: the backup store, one buffer [A | Bm | Kc | backoff_x] with the shapes of the live arrays
+static size_t plan_doubles(const slsqp_handle *h, int part) {      // doubles per instance of part 0..3
+    const slsqp_dims &d = h->d;
+    return part == 0 ? (size_t)d.N * d.nx * d.nx : part == 3 ? (size_t)(d.N + 1) * d.nx : (size_t)d.N * d.nx * d.nu;
+}
+static double *plan_part(const slsqp_handle *h, int part) {
+    double *p = h->plan_bk;
+    for (int i = 0; i < part; i++) p += (size_t)h->B * plan_doubles(h, i);
+    return p;
+}
+static int plan_part_named(const char *name) {
+    static const char *names[] = {"plan_A", "plan_Bm", "plan_Kc", "plan_backoff_x"};
+    for (int i = 0; i < 4; i++) if (!strcmp(name, names[i])) return i;
+    return -1;
+}
 // bytes per instance of a named result (what slsqp_get copies for each instance), or -1 for an unknown name
 extern "C" long long slsqp_result_bytes(slsqp_handle *h, const char *name) {
     if (!strcmp(name, "plant_params")) return h->model_id < 0 ? -1LL : (long long)sizeof(double) * plant_params::count(h->model_id);
@@ -1841,6 +1884,8 @@ extern "C" long long slsqp_result_bytes(slsqp_handle *h, const char *name) {
     if (!strcmp(name, "bounds_gf")) return (long long)sizeof(double) * h->d.ni_f * (h->bnd_rows ? h->bnd_T : 1);
     if (!strcmp(name, "hold_index") || !strcmp(name, "hold_policy")) return (long long)sizeof(int);
     if (!strcmp(name, "hold_xi")) return (long long)sizeof(double) * (h->d.N + 1) * h->d.nx;
+    if (!strcmp(name, "plan_age")) return (long long)sizeof(int);
+    if (const int part = plan_part_named(name); part >= 0) return (long long)sizeof(double) * plan_doubles(h, part);
     auto it = h->named.find(name);
     return it == h->named.end() ? -1LL : (long long)it->second.second;
 }
@@ -2014,11 +2059,32 @@ static int get_hold_named(slsqp_handle *h, const char *name, void *out, int loc)
     return 1;
 }
 
+// slsqp_get names of plan fallback (slsqp_cl_set_plan_fallback): plan_age[int32] (1), plan_A (N,nx,nx), plan_Bm (N,nx,nu), plan_Kc (N,nu,nx),
+// plan_backoff_x (N+1,nx): every instance's backup and its age; ages -1 and zeros on a handle that never ran with the option on.  Returns as above.
+static int get_plan_named(slsqp_handle *h, const char *name, void *out, int loc) {
+    const int part = plan_part_named(name);
+    const bool is_age = !strcmp(name, "plan_age");
+    if (!is_age && part < 0) return 0;
+    HIPCHK(hipStreamSynchronize(h->st));
+    const size_t B = h->B;
+    const hipMemcpyKind from_host = loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice, from_dev = loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (is_age) {
+        if (h->plan_age) HIPCHK(hipMemcpy(out, h->plan_age, sizeof(int) * B, from_dev));
+        else { const std::vector<int> v(B, -1); HIPCHK(hipMemcpy(out, v.data(), sizeof(int) * B, from_host)); }
+    } else {
+        const size_t n = B * plan_doubles(h, part);
+        if (h->plan_bk) HIPCHK(hipMemcpy(out, plan_part(h, part), sizeof(double) * n, from_dev));
+        else { const std::vector<double> z(n, 0.0); HIPCHK(hipMemcpy(out, z.data(), sizeof(double) * n, from_host)); }
+    }
+    return 1;
+}
+
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
     if (const int r = get_plant_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_bounds_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_hold_named(h, name, out, loc)) return r < 0 ? -1 : 0;
+    if (const int r = get_plan_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (!h->pp_P && h->lg_merr && !strcmp(name, "log_model_error")) HIPCHK(hipMemsetAsync(h->lg_merr, 0, sizeof(double) * (size_t)h->B * h->log_steps * h->d.nx, h->st));      // (a handle without parameters: all zeros, whatever an earlier run with parameters left)
     auto it = h->named.find(name);
     if (it == h->named.end()) return fail(std::string("unknown result name: ") + name);
@@ -2140,6 +2206,8 @@ extern "C" int slsqp_cl_init(slsqp_handle *h, const double *x_meas, const double
     }
     h->cl_steps = 0;
     cl_hold::on_init(h->hold);      // no plan to hold yet
+    if (h->plan_age) HIPCHK(hipMemsetAsync(h->plan_age, 0xFF, sizeof(int) * B, h->st));      // (plan fallback: no backup, every age -1)
+    if (h->lg_age) HIPCHK(hipMemsetAsync(h->lg_age, 0, sizeof(int) * B * h->log_steps, h->st));      // (log_plan_age: written by the steps of a handle with the option on)
     if (h->lg_hold) HIPCHK(hipMemsetAsync(h->lg_hold, 0, sizeof(int) * B * h->log_steps * 2, h->st));      // (log_hold, log_hold_policy: solved steps never write them)
     if (h->lg_ratio) { HIPCHK(hipMemsetAsync(h->lg_ratio, 0, sizeof(double) * B * h->log_steps, h->st)); HIPCHK(hipMemsetAsync(h->lg_trig, 0, sizeof(int) * B * h->log_steps, h->st)); }      // (written by event-triggered runs only)
     HIPCHK(hipMemsetAsync(h->has_prev, 0, sizeof(int) * B, h->st));   // a fresh SCP_SLS object has no convergence history
@@ -2210,9 +2278,9 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     HIPCHK(hipStreamSynchronize(h->st));
     h->log_steps = 0;
     free_all(h->log_owned);
-    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy", "log_tube_ratio", "log_solve_trigger"};
+    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy", "log_tube_ratio", "log_solve_trigger", "log_plan_age"};
     for (const char *nm : names) h->named.erase(nm);
-    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr;
+    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_age = nullptr;
     h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr;
     const slsqp_dims &d = h->d;
     const size_t B = h->B, S = max_steps, nX = (size_t)(d.N + 1) * d.nx, nU = (size_t)d.N * d.nu;
@@ -2222,8 +2290,8 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     rc |= dalloc(ow, &h->lg_state, B * S * d.nx); rc |= dalloc(ow, &h->lg_u0, B * S * d.nu); rc |= dalloc(ow, &h->lg_succ, B * S); rc |= dalloc(ow, &h->lg_it, B * S);
     rc |= dalloc(ow, &h->lg_pinf, B * S); rc |= dalloc(ow, &h->lg_x0v, B * S * 2); rc |= dalloc(ow, &h->lg_merr, B * S * d.nx);
     rc |= dalloc(ow, &h->lg_hold, B * S * 2); h->lg_hpol = h->lg_hold ? h->lg_hold + B * S : nullptr;
-    rc |= dalloc(ow, &h->lg_ratio, B * S); rc |= dalloc(ow, &h->lg_trig, B * S);
-    if (rc) { free_all(ow); h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
+    rc |= dalloc(ow, &h->lg_ratio, B * S); rc |= dalloc(ow, &h->lg_trig, B * S); rc |= dalloc(ow, &h->lg_age, B * S);
+    if (rc) { free_all(ow); h->lg_age = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
     h->log_steps = max_steps;
     auto reg = [&](const char *nm, void *p, size_t bytes) { h->named[nm] = {p, bytes}; };
     reg("log_nominal_x", h->lg_x, sizeof(double) * S * nX); reg("log_nominal_u", h->lg_u, sizeof(double) * S * nU);
@@ -2233,6 +2301,7 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     reg("log_primal_infeasibility", h->lg_pinf, sizeof(double) * S); reg("log_x0_viol", h->lg_x0v, sizeof(double) * S * 2);
     reg("log_hold", h->lg_hold, sizeof(int) * S); reg("log_hold_policy", h->lg_hpol, sizeof(int) * S);      // slsqp_cl_hold_step: 0 for a solved step, k for hold step k; whether the policy ran
     reg("log_tube_ratio", h->lg_ratio, sizeof(double) * S); reg("log_solve_trigger", h->lg_trig, sizeof(int) * S);      // an event-triggered slsqp_cl_run (slsqp_cl_set_hold_trigger): the ratio where it was evaluated, the reason code of cl_hold::decide; zeros from every other run
+    reg("log_plan_age", h->lg_age, sizeof(int) * S);      // plan fallback (slsqp_cl_set_plan_fallback): the age every step left behind; zeros from a handle with the option off
     reg("log_model_error", h->lg_merr, sizeof(double) * S * d.nx);      // ddyn_p - ddyn of every step's plant step (slsqp_cl_set_plant_params; zeros without parameters)
     return 0;
 }
@@ -2243,6 +2312,11 @@ __global__ void k_cl_log_x0v(int B, int log_steps, int step, const double *x0vio
     if (i < 2 * B) lg[((size_t)(i / 2) * log_steps + step) * 2 + (i & 1)] = qpstat[(size_t)i * 8 + 6] == -1 ? 0.0 : x0viol[i];      // (a QP that took no part records 0)
 }
 
+static int ensure_plan(slsqp_handle *h);      // plan fallback, beside slsqp_cl_hold_step below
+static PlanArgs plan_args(const slsqp_handle *h);
+static void hold_args_on_backup(const slsqp_handle *h, HoldArgs &a);
+static ClArgs plant_args_on_u(const slsqp_handle *h, ClArgs a);
+extern const char *const FALLBACK_NEEDS;
 // One MPC step for the whole batch: [warm-start shift + solver reset] -> rti x (linearise, fast-SLS solve of x_nom0 - x_meas,
 // nominal += delta) -> u0 = first nominal input -> plant step x_meas <- ddyn(x_meas,u0) + E w.   w (B,nx) or NULL (no noise).
 extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc, const slsqp_opts *opts) {
@@ -2255,13 +2329,15 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     if (w) { if (put(h, h->wbuf, w, sizeof(double) * (size_t)h->B * d.nx, loc)) return -1; dw = h->wbuf; }
     ClArgs a = cl_args(h, dw);
     const ClOptions op = cl_options(h);
+    slsqp_opts o;
+    if (opts) o = *opts; else slsqp_default_opts(&o);
+    if (op.fallback && !(rti == 1 && o.rti_steps == 1)) return fail(std::string("slsqp_cl_step: ") + FALLBACK_NEEDS + " (the backup keeps the compact gains of the shared Riccati recursion; the full K is not snapshotted)");
+    if (op.fallback && ensure_plan(h)) return -1;
     if (h->cl_steps > 0) {
         if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 1, 0); })) return -1;
         if (slsqp_reset(h)) return -1;
         h->horizon_shifted = 1;
     }
-    slsqp_opts o;
-    if (opts) o = *opts; else slsqp_default_opts(&o);
     // SCP_SLS.solve (solver/SCP_SLS_jit.py:65-152): rti > 0 -> exactly rti iterations; rti <= 0 -> until |delta|inf < scp_eps
     // (epsilon_convergence :29) or MAX_ITER_SCP (:47).  Instances leave the loop one by one (failed step / converged); the
     // linearisation, the fast-SLS solve and the nominal update only touch the ones still iterating.
@@ -2301,9 +2377,19 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
         hipLaunchKernelGGL(k_cl_log_x0v, dim3((2 * h->B + 255) / 256), dim3(256), 0, h->st, h->B, h->log_steps, h->cl_steps, h->x0viol, h->qpstat, h->lg_x0v);
         h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};      // (a slsqp_cl_run in between points the name at its own per-run buffer)
     }
+    // plan fallback: one more launch, a wave per instance -- the plan of an instance that succeeded goes into its backup, one that
+    // failed runs the backup's policy -- which writes the input to apply for every instance; the plant launch then takes that buffer as a one-stage plan
+    const ClArgs ap = op.fallback ? plant_args_on_u(h, a) : a;
     if (with_model(h, [&](auto M) {
-            if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, op.pa, h->cl_steps, nullptr, nullptr, nullptr);      // the plant has its own parameters
-            else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 0, 1);
+            if (op.fallback) {
+                const bool log = h->log_steps > 0 && h->cl_steps < h->log_steps;
+                HoldArgs ha{a, 0, h->A, h->Bm, h->K, h->Kc, h->stale, h->scp_success, h->hold_xi, h->hold_u, h->hold_policy, log ? h->log_steps : 0, h->cl_steps,
+                            h->lg_state, h->lg_u0, h->lg_x0v, h->lg_it, h->lg_hold, h->lg_hpol};
+                hold_args_on_backup(h, ha);
+                hipLaunchKernelGGL((k_cl_plan_fallback<M()>), dim3(h->B), dim3(64), 0, h->st, ha, plan_args(h), 0);
+            }
+            if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, ap, op.pa, h->cl_steps, nullptr, nullptr, nullptr);      // the plant has its own parameters
+            else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, ap, 0, 1);
         })) return -1;
     HIPCHK(hipGetLastError());
     if (finish_enqueued(h, false)) return -1;
@@ -2327,6 +2413,15 @@ extern "C" int slsqp_cl_set_hold_trigger(slsqp_handle *h, double theta) {
     return 0;
 }
 extern "C" double slsqp_cl_get_hold_trigger(slsqp_handle *h) { return h->hold_trigger; }
+// Plan fallback: a property of the handle, default 0 = off.  1: a step that applies no freshly certified plan (a solve that
+// failed, a hold step) runs the tube policy of the instance's last plan that succeeded, read from a per-instance backup.  Read by slsqp_cl_step,
+// slsqp_cl_hold_step and slsqp_cl_run (rti = 1 with one fast-SLS step: the compact gains).  Anything but 0 / 1 is refused and changes nothing.
+extern "C" int slsqp_cl_set_plan_fallback(slsqp_handle *h, int on) {
+    if (!cl_hold::valid_plan_fallback(on)) return fail("slsqp_cl_set_plan_fallback: " + std::to_string(on) + " is neither 0 (off) nor 1 (on)");
+    h->plan_fallback = on;
+    return 0;
+}
+extern "C" int slsqp_cl_get_plan_fallback(slsqp_handle *h) { return h->plan_fallback; }
 
 // One closed-loop step WITHOUT a solve: the one-stage shift slsqp_cl_step applies at its top, then k_cl_hold -- the tube policy
 // of the last solve on the measured state, and the plant step.  No slsqp_reset (K stays valid); slsqp_cl_step is not involved and finds, at its next
@@ -2344,25 +2439,62 @@ static int ensure_hold(slsqp_handle *h) {
     h->hold_xi = buf; h->hold_u = buf + nxi; h->hold_policy = pol; h->hold_k = pol + h->B;
     return 0;
 }
+// Plan fallback: the backup store and the ages, allocated by the first step that runs with the option on, beside ensure_hold's
+// buffers (the policy's column states and input are the hold steps').  No backup yet: every age -1.
+static int ensure_plan(slsqp_handle *h) {
+    if (ensure_hold(h)) return -1;
+    if (h->plan_bk) return 0;
+    size_t per = 0;
+    for (int i = 0; i < 4; i++) per += plan_doubles(h, i);
+    double *buf = nullptr; int *age = nullptr;
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * per * h->B + 64));
+    if (hipMalloc((void **)&age, sizeof(int) * h->B + 64) != hipSuccess || hipMemset(buf, 0, sizeof(double) * per * h->B) != hipSuccess || hipMemset(age, 0xFF, sizeof(int) * h->B) != hipSuccess) {
+        hipFree(buf); if (age) hipFree(age);
+        return fail("slsqp_cl_set_plan_fallback: allocation of the backup plans failed");
+    }
+    h->plan_bk = buf; h->plan_age = age;
+    return 0;
+}
+// the option's arguments (ensure_plan first) and the HoldArgs that go with them: the policy reads the backup
+static PlanArgs plan_args(const slsqp_handle *h) {
+    PlanArgs f;
+    memset(&f, 0, sizeof f);
+    f.on = 1;
+    f.A = h->A; f.Bm = h->Bm; f.Kc = h->Kc; f.backoff_x = h->backoff_x;
+    f.bA = plan_part(h, 0); f.bB = plan_part(h, 1); f.bKc = plan_part(h, 2); f.bbo = plan_part(h, 3);
+    f.age = h->plan_age; f.lage = h->lg_age;
+    return f;
+}
+static void hold_args_on_backup(const slsqp_handle *h, HoldArgs &a) { a.A = plan_part(h, 0); a.Bm = plan_part(h, 1); a.Kc = plan_part(h, 2); }
+// the plant launch of a step under the option: "the first nominal input" of instance b is hold_u[b], the trick of k_cl_hold
+static ClArgs plant_args_on_u(const slsqp_handle *h, ClArgs a) { a.N = 1; a.Un = h->hold_u; return a; }
+const char *const FALLBACK_NEEDS = "plan fallback needs rti = 1 with one fast-SLS step";
+
 extern "C" int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc) {
     hipSetDevice(h->dev);
     std::string why;
     const int k = cl_hold::next_index(h->hold, h->model_id >= 0, h->cl_steps, h->d.N, loc, &why);
     if (!k) return fail("slsqp_cl_hold_step: " + why);
-    if (ensure_hold(h)) return -1;
+    const ClOptions op = cl_options(h);
+    if (op.fallback ? ensure_plan(h) : ensure_hold(h)) return -1;
     const slsqp_dims &d = h->d;
     const int gb = (h->B + 63) / 64;
     const double *dw = nullptr;
     if (w) { if (put(h, h->wbuf, w, sizeof(double) * (size_t)h->B * d.nx, loc)) return -1; dw = h->wbuf; }
     const ClArgs a = cl_args(h, dw);
-    const ClOptions op = cl_options(h);
     const bool log = h->log_steps > 0 && h->cl_steps < h->log_steps;
     HoldArgs ha{a, k, h->A, h->Bm, h->K, h->Kc, h->stale, h->scp_success, h->hold_xi, h->hold_u, h->hold_policy, log ? h->log_steps : 0, h->cl_steps,
                 h->lg_state, h->lg_u0, h->lg_x0v, h->lg_it, h->lg_hold, h->lg_hpol};
+    if (op.fallback) hold_args_on_backup(h, ha);      // (every instance at the index its backup's age gives; k is the batch's, for the log and for an instance without a plan)
     if (with_model(h, [&](auto M) {
             hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 1, 0);
             if (log) hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, cl_log_args(h, nullptr, nullptr, h->cl_steps));      // nominal = the shifted plan, back-offs and success of the last solve; k_cl_hold writes the rest
-            with_flag(op.pp, [&](auto PP) { hipLaunchKernelGGL((k_cl_hold<M(), PP()>), dim3(h->B), dim3(64), 0, h->st, ha, op.pa); });
+            if (op.fallback) {
+                hipLaunchKernelGGL((k_cl_plan_fallback<M()>), dim3(h->B), dim3(64), 0, h->st, ha, plan_args(h), k);
+                const ClArgs au = plant_args_on_u(h, a);
+                if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, au, op.pa, h->cl_steps, nullptr, nullptr, nullptr);
+                else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, au, 0, 1);
+            } else with_flag(op.pp, [&](auto PP) { hipLaunchKernelGGL((k_cl_hold<M(), PP()>), dim3(h->B), dim3(64), 0, h->st, ha, op.pa); });
         })) return -1;
     if (log) h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};
     HIPCHK(hipGetLastError());
@@ -2479,12 +2611,26 @@ static HoldLoopArgs make_hold_block(slsqp_handle *h) {
     a.lstate = h->lg_state; a.lu0 = h->lg_u0; a.lx0v = h->lg_x0v; a.lit = h->lg_it; a.lhold = h->lg_hold; a.lpol = h->lg_hpol;      // (lx0v: the log's own buffer; the run's log_x0_viol is the block's x0vlog)
     H.M = h->solve_every;
     H.theta = h->hold_trigger; H.backoff_x = h->backoff_x; H.hold_k = h->hold_k; H.lratio = h->lg_ratio; H.ltrig = h->lg_trig;
+    if (h->plan_fallback) { hold_args_on_backup(h, a); H.backoff_x = plan_part(h, 3); }      // (ensure_plan has run: the policy and the trigger's ratio read the backup)
     return H;
 }
 static int write_hold_block(slsqp_handle *h, const HoldLoopArgs &H) {
     h->hold_blk_host.resize(sizeof H);
     memcpy(h->hold_blk_host.data(), &H, sizeof H);
     HIPCHK(hipMemcpyAsync(h->loop_blk + HOLD_BLK_OFFSET, h->hold_blk_host.data(), sizeof H, hipMemcpyHostToDevice, h->st));
+    return 0;
+}
+// the PlanArgs behind the hold block: written when the option is on, and once more, as zero bytes, by the first HOLD launch after it was switched off
+// (the buffer starts as zeros: a handle that never had the option on writes nothing here)
+static int write_plan_block(slsqp_handle *h, bool on) {
+    if (!on && !h->plan_blk_dev) return 0;
+    PlanArgs f;
+    memset(&f, 0, sizeof f);
+    if (on) f = plan_args(h);
+    h->plan_blk_host.resize(sizeof f);
+    memcpy(h->plan_blk_host.data(), &f, sizeof f);
+    HIPCHK(hipMemcpyAsync(h->loop_blk + PLAN_BLK_OFFSET, h->plan_blk_host.data(), sizeof f, hipMemcpyHostToDevice, h->st));
+    h->plan_blk_dev = on ? 1 : 0;
     return 0;
 }
 // scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp)
@@ -2503,7 +2649,8 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     const LoopArgs &L = S.L;
     if (write_loop_block(h, S)) return -1;
     const int M = scp ? 1 : h->solve_every;      // (slsqp_cl_run_scp has refused M > 1 for its own kernel)
-    if (M > 1 && (ensure_hold(h) || write_hold_block(h, make_hold_block(h)))) return -1;
+    const bool fallback = !scp && h->plan_fallback;      // (slsqp_cl_run_scp has refused the option for its own kernel)
+    if ((M > 1 || fallback) && ((fallback ? ensure_plan(h) : ensure_hold(h)) || write_hold_block(h, make_hold_block(h)) || write_plan_block(h, fallback))) return -1;
     const bool triggered = cl_hold::trigger_on(h->hold_trigger, M);      // every instance on its own schedule: its first step is a solve
     if (triggered) HIPCHK(hipMemsetAsync(h->hold_k, 0, sizeof(int) * (size_t)B, h->st));
     hipLaunchKernelGGL(k_clq_init, dim3(64), dim3(256), 0, h->st, B, L.Q);
@@ -2615,6 +2762,8 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
     const double *dW = nullptr;
     if (h->solve_every > 1 && !o.cl_persistent)
         return fail("slsqp_cl_run: solve_every = " + std::to_string(h->solve_every) + " runs in the persistent launch only (cl_persistent = 1): the round-based loop solves at every step (use slsqp_cl_step / slsqp_cl_hold_step)");
+    if (h->plan_fallback && !o.cl_persistent)
+        return fail("slsqp_cl_run: plan fallback runs in the persistent launch only (cl_persistent = 1): the round-based loop applies the nominal input of a failed step (use slsqp_cl_step / slsqp_cl_hold_step)");
     if (cl_run_prepare(h, steps, W, loc, &dW)) return -1;
     if (o.cl_persistent) return cl_run_persistent(h, steps, dW, o, rounds_out);
     h->cl_budget = budget_ms > 0.0 ? (unsigned long long)(std::max(0.05, budget_ms) * 1e5) : (1ULL << 62);
@@ -2693,6 +2842,8 @@ extern "C" int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const doubl
     if (rti <= 0 && o.max_scp_iter < 1) return fail("slsqp_cl_run_scp: converge mode needs max_scp_iter >= 1");
     if (h->solve_every > 1 && !(rti == 1 && o.rti_steps == 1))
         return fail("slsqp_cl_run_scp: solve_every = " + std::to_string(h->solve_every) + " needs rti = 1 with one fast-SLS step (slsqp_cl_run's kernel): the general persistent loop keeps its gains per SCP iteration and solves at every step (use slsqp_cl_step / slsqp_cl_hold_step)");
+    if (h->plan_fallback && !(rti == 1 && o.rti_steps == 1))
+        return fail(std::string("slsqp_cl_run_scp: ") + FALLBACK_NEEDS + " (slsqp_cl_run's kernel): the backup keeps the compact gains, the general persistent loop keeps its gains per SCP iteration");
     const double *dW = nullptr;
     if (cl_run_prepare(h, steps, W, loc, &dW)) return -1;
     if (rti == 1 && o.rti_steps == 1) return cl_run_persistent(h, steps, dW, o, nullptr);

@@ -262,6 +262,19 @@ class BatchedFastSLS:
     def get_hold_trigger(self):
         return float(self.lib.slsqp_cl_get_hold_trigger(self.h))
 
+    def set_plan_fallback(self, on):
+        """Plan fallback (slsqp_cl_set_plan_fallback): on, a closed-loop step that applies no freshly certified plan -- a solve that failed, a hold
+        step -- runs the tube policy of the instance's last plan that succeeded, kept in a per-instance backup, for as long as that plan has rows
+        (plan_age + 1 <= N - 1); off (default): the nominal input.  slsqp_cl_step, hold_step and the persistent slsqp_cl_run read it; it needs rti = 1
+        with one fast-SLS step.  Anything but a bool / 0 / 1 is refused with the handle unchanged.  get("plan_age", (), np.int32) and
+        get("plan_A" / "plan_Bm" / "plan_Kc" / "plan_backoff_x", shape) read the backup."""
+        if not (isinstance(on, (bool, np.bool_)) or (isinstance(on, (int, np.integer)))):
+            raise ValueError(f"set_plan_fallback: expected a bool or 0 / 1, got {on!r}")
+        L.check(self.lib.slsqp_cl_set_plan_fallback(self.h, int(on)))
+
+    def get_plan_fallback(self):
+        return bool(self.lib.slsqp_cl_get_plan_fallback(self.h))
+
     def tube_ratio(self):
         """(B,) max_i |x_meas_i - z_i| / backoff_x[k, i] of every instance for the hold step k that hold_step would run next (slsqp_cl_tube_ratio), z
         stage k of the plan; inf for an instance without a valid plan.  Refused where hold_step is; changes nothing."""

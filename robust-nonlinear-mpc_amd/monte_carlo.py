@@ -46,10 +46,10 @@ PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
 
 
 def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1,
-               reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None):
+               reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
-    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every, hold_trigger=hold_trigger)
+    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every, hold_trigger=hold_trigger, plan_fallback=plan_fallback)
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
     rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
     want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
@@ -70,7 +70,7 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
                     budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None,
-                    solve_every=1, hold_trigger=None):
+                    solve_every=1, hold_trigger=None, plan_fallback=False):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
@@ -95,6 +95,9 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     hold_trigger: theta < inf = event-triggered solves (ClosedLoopMPC.run_decoupled's hold_trigger): with solve_every = M > 1 and persistent=True a seed's
     controller holds while its state stays inside theta x its tube and solves when it does not, or after M steps at the latest; the result then holds
     `tube_ratio` and `solve_trigger` (seeds, steps).  Without persistent=True it raises.  None (default): off.
+    plan_fallback: True = a step of a seed that applies no freshly certified plan (a solve that failed, a hold step) runs the tube policy of the seed's
+    last plan that succeeded (ClosedLoopMPC's plan_fallback; rti = 1 with one fast-SLS step); the result then holds `plan_age`, `hold_index` and
+    `hold_policy` (seeds, steps), the policy as its code 0 / 1 / 2.  False (default): today's loops, unchanged.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -148,6 +151,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["solve_every"] = solve_every
             if hold_trigger is not None:
                 kw["hold_trigger"] = hold_trigger
+            if plan_fallback:
+                kw["plan_fallback"] = True
             kw.update(options(k))
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:

@@ -42,6 +42,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--persistent", action="store_true", help="one persistent launch per run instead of one launch sequence per step")
     ap.add_argument("--trigger", type=float, default=None, help="theta of the event-triggered schedule (with --persistent and M > 1; inf or absent: the fixed period)")
+    ap.add_argument("--fallback", action="store_true", help="plan fallback on (DESIGN.md section 22): a failed solve and every hold step run the policy of the last plan that succeeded")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose package is measured")
     a = ap.parse_args()
     triggered = a.trigger is not None and a.trigger < float("inf")
@@ -59,7 +60,8 @@ def main():
     nlp_ok = float(np.mean(cl.nlp_status == 0))
     cl.close()
     for M in a.M:
-        cl = ClosedLoopMPC(m, N, B) if M == 1 else ClosedLoopMPC(m, N, B, solve_every=M)
+        kw = dict(plan_fallback=True) if a.fallback else {}      # (off: the option is not named at all, as solve_every for M = 1)
+        cl = ClosedLoopMPC(m, N, B, **kw) if M == 1 else ClosedLoopMPC(m, N, B, solve_every=M, **kw)
         mark = {}
         reset, log_result = cl.reset, cl._log_result
 
@@ -101,6 +103,12 @@ def main():
                        tube_nonfinite=int(np.sum(~np.isfinite(per))))
             per = per[np.isfinite(per)]
             rec.update(tube_ratio_max=float(per.max()), tube_ratio_p50=float(np.median(per)), tube_ratio_p99=float(np.quantile(per, 0.99)), tube_exceeded=float(np.mean(per > 1.0)))
+        if "plan_age" in out:      # plan fallback: what the steps without a fresh plan did, and the tube of the backup on the failed solves that ran its policy
+            pol, age = out["hold_policy"], out["plan_age"]
+            fell = pol == 2
+            rec.update(fallback=True, success_share=float(out["success"][out["hold_index"] == 0].mean()), policy2_share=float(fell.mean()),
+                       policy0_share_unsolved=float(np.mean((pol == 0) & ~((out["hold_index"] == 0) & out["success"]))),
+                       plan_age_at_fallback={str(k): int(np.sum(age[fell] == k)) for k in np.unique(age[fell])})
         if a.persistent:
             ls = out["loop_stats"]
             rec.update(persistent=True, loop_stats=ls, waves_busy=float(ls["busy_ms"] / max(1e-9, ls["waves"] * runs[-1] * steps)))
