@@ -12,6 +12,7 @@ fast_sls_rti_steps, step counts and (rocket) seed-s disturbance streams; B indep
     ... --model quadrotor --bound 5=-1.2:inf@3                             # a box that changes during the run: descent rate >= -1.2 from step 3 on
     ... --solve-every 3                                                    # solve at steps 0, 3, 6, ...; the tube policy of the last solve acts in between
     ... --model rocket --persistent 1 --solve-every 5 --hold-trigger 0.75  # solve when the state leaves 0.75 x the plan's tube, or after 5 steps
+    ... --persistent 1 --fast-sls-steps 0                                  # fast-SLS converge mode, every run iterating at its own pace in the one launch
 
 The first nominal comes from the GPU initialiser (slsqp_nominal_solve) in place of IPOPT."""
 import argparse
@@ -57,6 +58,9 @@ def main():
                     "inside THETA x the tube of its plan and solves when it does not, or after M steps at the latest")
     ap.add_argument("--plan-fallback", action="store_true",
                     help="a step that applies no freshly certified plan (a failed solve, a hold step) runs the tube policy of the run's last plan that succeeded")
+    ap.add_argument("--fast-sls-steps", type=int, default=None, metavar="K",
+                    help="fast-SLS steps per solve instead of the script's value; 0: converge mode, every solve iterates until its step is below the tolerance "
+                    "(fast_SLS.solve's default) -- with --persistent 1 inside the one launch, every run at its own pace")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -112,15 +116,23 @@ def main():
             ap.error(str(e))
     cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P, bounds=bounds,
                        solve_every=a.solve_every, plan_fallback=a.plan_fallback)
+    if a.fast_sls_steps is not None:
+        cl.f.set_rti_steps(a.fast_sls_steps)      # (0: converge mode)
     t0 = time.perf_counter()
     run = cl.run_decoupled if a.persistent else cl.run_on_device
     kw = {} if a.hold_trigger is None else dict(hold_trigger=a.hold_trigger, **(dict(persistent_hold=True) if a.persistent else {}))
+    if a.persistent and cl.f.opts.rti_steps <= 0:
+        kw["persistent_converge"] = True
     out = run(x0, steps, W, solve_nominal=True, continuation=2 if a.model == "rocket" else 1, **kw)
     dt = time.perf_counter() - t0
     dist0 = np.linalg.norm(out["state_trajectory"][:, :, 0] - m.x_ref, axis=1).mean()
     dist1 = np.linalg.norm(out["state_trajectory"][:, :, -1] - m.x_ref, axis=1).mean()
     print(f"{a.model}: {B} runs x {steps} MPC steps (N={N}, rti={cl.rti}) in {dt:.2f} s; nominal NLP solved for {np.mean(cl.nlp_status == 0):.3f}; "
           f"MPC steps solved {out['success'].mean():.3f}; mean |x - x_ref| {dist0:.3f} -> {dist1:.3f}; QP {out['t_qp'].sum():.0f} ms, sweeps {out['t_riccati'].sum():.0f} ms")
+    if "sls_iterations" in out:
+        it = out["sls_iterations"]
+        print(f"fast-SLS converge mode in the persistent launch: sweeps per MPC step min {it.min()} / median {int(np.median(it))} / max {it.max()}; "
+              f"waves busy {out['loop_stats']['busy_ms'] / max(out['loop_stats']['waves'] * out['loop_stats']['launch_ms'], 1e-9):.2f} of the launch")
     if "plan_age" in out:
         pol = out["hold_policy"]
         print(f"plan fallback: {np.mean(pol == 2):.4f} of the steps were failed solves that ran the last certified plan's policy; "

@@ -356,6 +356,20 @@ int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc, const sls
    (steps,2,8), which holds per MPC step what `qp_stats` holds after the corresponding slsqp_cl_step (converge mode: an instance that left the SCP
    loop before the last instance of the batch did has its slots marked "took no part", status -1, as the batch-wide launches leave them). */
 int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const double *W, int loc, const slsqp_opts *opts);
+/* Fast-SLS converge mode inside slsqp_cl_run_scp's persistent launch.  A property of the handle, default 0 = off: the call refuses opts.rti_steps <= 0
+   as above and launches what it always did.  on = 1: slsqp_cl_run_scp accepts opts.rti_steps <= 0, for every rti, with opts.max_sls_iter >= 1 (a
+   smaller value is refused), and runs the steps as ONE launch in which every instance iterates fast_SLS.solve's default loop
+   (fast_SLS_jit.py:298-312) on its own: QP, eta and the convergence test, then either it leaves (converged: success; its QP failed: not) or it sweeps
+   and tightens and goes on, up to max_sls_iter times; an instance that hits the cap solves the last QP and fails, and its solver state is reset at
+   the top of its next solve (_finish_failure), as slsqp_cl_step does.  Same operations per instance in the same order as `steps` calls of
+   slsqp_cl_step(h, rti, ...) with the same options: same bits, `log_qp_stats` and `log_x0_viol` included (slot 0 of an instance that left a step's
+   last solve while another instance of the batch iterated on says "took no part", as the batch-wide launches leave it).  The other refusals of
+   slsqp_cl_run_scp stand (precision = 1, general G, solve_waves > 1, the fused chain switched off, solve_every > 1, plan fallback).  With the option
+   on and opts.rti_steps >= 1 the call launches exactly what it launches with the option off.  Values other than 0 / 1 are refused and change nothing.
+   Result (slsqp_get): log_sls_iterations[int32] (steps), iteration_number as each MPC step of the run left it (the sweeps the step ran); registered
+   by every slsqp_cl_run / slsqp_cl_run_scp, zeros from every run but these. */
+int slsqp_cl_set_sls_converge(slsqp_handle *h, int on);
+int slsqp_cl_get_sls_converge(slsqp_handle *h);
 /* wave statistics of the last persistent slsqp_cl_run / slsqp_cl_run_scp: [0] wavefronts launched, [1] sum over the MPC steps of the time a wavefront spent on them (ms),
    [2] MPC steps run, [3] duration of the launch (ms, HIP events; 0 without opts.time_kernels).  [1] / ([0] x [3]) = how busy the queue kept the waves. */
 #define SLSQP_CL_RUN_STATS_LEN 4

@@ -59,6 +59,7 @@ EXPORTS = [
     "slsqp_cl_hold_step", "slsqp_cl_set_solve_every", "slsqp_cl_get_solve_every",
     "slsqp_cl_set_hold_trigger", "slsqp_cl_get_hold_trigger", "slsqp_cl_tube_ratio",
     "slsqp_cl_set_plan_fallback", "slsqp_cl_get_plan_fallback",
+    "slsqp_cl_set_sls_converge", "slsqp_cl_get_sls_converge",
 ]
 
 _lib = None
@@ -119,6 +120,8 @@ def load():
     lib.slsqp_cl_tube_ratio.argtypes = [vp, dp, C.c_int]
     lib.slsqp_cl_set_plan_fallback.argtypes = [vp, C.c_int]
     lib.slsqp_cl_get_plan_fallback.argtypes = [vp]
+    lib.slsqp_cl_set_sls_converge.argtypes = [vp, C.c_int]
+    lib.slsqp_cl_get_sls_converge.argtypes = [vp]
     lib.slsqp_nominal_solve.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.POINTER(Opts)]
     lib.slsqp_cl_log.argtypes = [vp, C.c_int]
     lib.slsqp_cl_run.argtypes = [vp, C.c_int, dp, C.c_int, C.POINTER(Opts), C.c_double, C.c_double, C.POINTER(C.c_int)]

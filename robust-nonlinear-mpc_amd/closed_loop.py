@@ -277,7 +277,7 @@ class ClosedLoopMPC:
                 wm[:, i] += w
         return np.max(np.abs(wm), axis=2).T.copy()
 
-    def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0, solve_every=None, persistent_hold=False, hold_trigger=None):
+    def run_decoupled(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, budget_ms=8.0, cut_frac=0.0, solve_every=None, persistent_hold=False, hold_trigger=None, persistent_converge=False):
         """Same results as run_on_device() -- bit for bit -- with the instances advancing through their MPC steps independently, so nobody waits for
         the slowest instance of a step.
         rti = 1 with one fast-SLS step (the rocket script's setting): slsqp_cl_run.  With opts.cl_persistent (the default) the whole loop is ONE launch:
@@ -285,7 +285,7 @@ class ClosedLoopMPC:
         solves that is not done budget_ms after its launch started suspends itself and resumes in the next round; cut_frac: see slsqp_cl_run).
         Every other setting slsqp_cl_step takes with a fixed number of fast-SLS steps (rti > 1, SCP converge mode rti <= 0, rti_steps > 1: the
         pendulum and quadrotor scripts, SCP_SLS's default): slsqp_cl_run_scp, always one persistent launch (budget_ms / cut_frac ignored).  Fast-SLS
-        converge mode (fast_sls_rti_steps None), precision = 1 and SLSQP_FUSE_RTI=0 are refused with the library's message.
+        converge mode (fast_sls_rti_steps None; but see persistent_converge), precision = 1 and SLSQP_FUSE_RTI=0 are refused with the library's message.
         solve_every = M > 1 (None: the constructor's): by default the run takes the step-by-step loop (run_on_device), as it does for solve_waves > 1.
         persistent_hold=True runs it as the persistent launch instead, the hold steps of an instance inside the loop of the wave that solved for it
         (BatchedFastSLS.set_solve_every; rti = 1 with one fast-SLS step and opts.cl_persistent only, every other setting raises with the library's
@@ -293,6 +293,10 @@ class ClosedLoopMPC:
         hold_trigger = theta < inf (None: the constructor's; with persistent_hold and M > 1 only, anything else raises): event-triggered solves -- an
         instance holds while its tube ratio is <= theta and solves when it is not, or after M steps at the latest (slsqp_cl_set_hold_trigger); the result
         then also holds `tube_ratio` (B, steps) and `solve_trigger` (B, steps) (0 hold, 1 scheduled, 2 left theta x tube, 3 the last solve had failed).
+        persistent_converge=True with fast-SLS converge mode (fast_sls_rti_steps None): the run is taken as one persistent launch in which every
+        instance iterates its fast-SLS solves to convergence on its own (BatchedFastSLS.set_sls_converge, set for this call and cleared afterwards;
+        at most opts.max_sls_iter iterations per solve); the result then also holds `sls_iterations` (B, steps), iteration_number as each step left
+        it.  With a fixed number of fast-SLS steps it changes nothing.  False (default): that mode raises with the library's message, as before.
         Adds `qp_stats` (B, steps, 2, 8) (next to `x0_violation` (B, steps, 2), which every logged run has), `rounds` and (persistent) `loop_stats`; the t_* arrays hold the run's totals in their first entry."""
         f, m, N, B = self.f, self.m, self.N, self.B
         M = self._check_solve_every(solve_every)
@@ -307,15 +311,18 @@ class ClosedLoopMPC:
         if hold and not (self.rti == 1 and f.opts.rti_steps == 1):      # (asked here, before anything is reset: the library's words)
             raise RuntimeError(f"slsqp: slsqp_cl_run_scp: solve_every = {M} needs rti = 1 with one fast-SLS step (slsqp_cl_run's kernel): the general "
                                "persistent loop keeps its gains per SCP iteration and solves at every step (use slsqp_cl_step / slsqp_cl_hold_step)")
+        conv = bool(persistent_converge) and f.opts.rti_steps <= 0
         f.set_solve_every(M if hold else 1)
         f.set_hold_trigger(theta if hold else None)
+        f.set_sls_converge(conv)
         try:
-            return self._run_persistent(x0, steps, W, X_nom, U_nom, solve_nominal, continuation, budget_ms, cut_frac, hold)
+            return self._run_persistent(x0, steps, W, X_nom, U_nom, solve_nominal, continuation, budget_ms, cut_frac, hold, conv)
         finally:
-            f.set_solve_every(1)      # (the handle's M and theta are this call's: the next run says what it wants)
+            f.set_solve_every(1)      # (the handle's M, theta and converge option are this call's: the next run says what it wants)
             f.set_hold_trigger(None)
+            f.set_sls_converge(False)
 
-    def _run_persistent(self, x0, steps, W, X_nom, U_nom, solve_nominal, continuation, budget_ms, cut_frac, hold):
+    def _run_persistent(self, x0, steps, W, X_nom, U_nom, solve_nominal, continuation, budget_ms, cut_frac, hold, conv=False):
         f, m, N, B = self.f, self.m, self.N, self.B
         L.check(f.lib.slsqp_cl_log(f.h, int(steps)))
         self.reset(x0, X_nom, U_nom, solve_nominal=solve_nominal, continuation=continuation)
@@ -340,6 +347,8 @@ class ClosedLoopMPC:
             st = (C.c_double * L.CL_RUN_STATS_LEN)()
             L.check(f.lib.slsqp_cl_run_stats(f.h, st, L.CL_RUN_STATS_LEN))
             out["loop_stats"] = dict(waves=int(st[0]), busy_ms=float(st[1]), mpc_steps=int(st[2]), launch_ms=float(st[3]))
+        if conv:
+            out["sls_iterations"] = f.get("log_sls_iterations", (steps,), np.int32)
         if hold or self.plan_fallback:
             out.update(self._hold_log(steps))
         if hold:

@@ -21,6 +21,7 @@
 #include "cl_bounds.hpp"
 #include "cl_hold.hpp"
 #include "cl_hold_kernel.hpp"
+#include "cl_sls_conv.hpp"
 
 using namespace slsqp;
 
@@ -82,6 +83,9 @@ struct slsqp_handle {
     // slsqp_cl_set_plan_fallback: the backup of every instance's last plan that succeeded, one buffer
     // [A (B,N,nx,nx) | Bm (B,N,nx,nu) | Kc (B,N,nu,nx) | backoff_x (B,N+1,nx)] allocated by the first step that needs it (ensure_plan), its age, the age's log
     int plan_fallback = 0; double *plan_bk = nullptr; int *plan_age = nullptr, *lg_age = nullptr;
+    // slsqp_cl_set_sls_converge: slsqp_cl_run_scp takes fast-SLS converge mode (opts.rti_steps <= 0).  sls_itlog: one allocation
+    // [log_sls_iterations (B, qplog_cap) | the sweeps of each step's last solve (B, qplog_cap)], made with qplog
+    int sls_converge = 0, *sls_itlog = nullptr; std::vector<unsigned char> conv_blk_host;
     int plan_blk_dev = 0; std::vector<unsigned char> plan_blk_host;      // whether the PlanArgs in loop_blk (PLAN_BLK_OFFSET) say "on"; the bytes the host last wrote there
     std::vector<unsigned char> hold_blk_host;    // the HoldLoopArgs the host last wrote behind the ScpLoopArgs of loop_blk (runs with solve_every > 1 only)
     int solve_waves = 1;        // slsqp_set_solve_waves: 1 = the single-wave QP kernels, 2 / 4 / 8 = k_qp_solve_mw (one workgroup of that many waves per instance)
@@ -380,6 +384,7 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     if (h->qplog) hipFree(h->qplog);
     if (h->x0vlog) hipFree(h->x0vlog);
     if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
+    if (h->sls_itlog) hipFree(h->sls_itlog);
     if (h->chain_times_host) hipHostFree(h->chain_times_host);
     for (auto &e : h->ev) hipEventDestroy(e);
     for (auto &e : h->tl) hipEventDestroy(e);
@@ -900,6 +905,13 @@ __device__ __forceinline__ const HoldLoopArgs *hold_blk(const ScpLoopArgs *blk) 
 constexpr size_t PLAN_BLK_OFFSET = (HOLD_BLK_OFFSET + sizeof(HoldLoopArgs) + 15) & ~(size_t)15;
 static_assert(PLAN_BLK_OFFSET + sizeof(PlanArgs) <= LOOP_BLK_BYTES, "slsqp_handle::loop_blk is 4096 bytes");
 __device__ __forceinline__ const PlanArgs *plan_blk_of(const HoldLoopArgs *hp) { return (const PlanArgs *)((const unsigned char *)hp + (PLAN_BLK_OFFSET - HOLD_BLK_OFFSET)); }
+// What the CONV variants of k_cl_loop_scp read besides (slsqp_cl_set_sls_converge): per (instance, step) of the run's log the
+// sweeps of the step's last fast-SLS solve (from which k_cl_qplog_sls_conv reproduces the batch-wide launches' "took no part") and iteration_number
+// as the step leaves it (log_sls_iterations).  BEHIND the plan block in the same device block: nothing in front of it moves, no other kernel reads it.
+struct SlsConvArgs { int *lastit, *itlog; int log_steps; };
+constexpr size_t CONV_BLK_OFFSET = (PLAN_BLK_OFFSET + sizeof(PlanArgs) + 15) & ~(size_t)15;
+static_assert(CONV_BLK_OFFSET + sizeof(SlsConvArgs) <= LOOP_BLK_BYTES, "slsqp_handle::loop_blk is 4096 bytes");
+__device__ __forceinline__ const SlsConvArgs *conv_blk(const ScpLoopArgs *blk) { return (const SlsConvArgs *)((const unsigned char *)blk + CONV_BLK_OFFSET); }
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
 // HOLD (k_cl_loop's hold variants): held != 0 is a hold step of the instance, which takes the shift alone -- no solver reset, so stale, itnum, q
@@ -1191,9 +1203,16 @@ __device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S_, int b, int lane, in
 // one fast-SLS solve of rti_steps steps of one instance by one wave: what solve_impl launches (fast_SLS_jit.py:278-296).  QP i of the call gets the
 // arguments launch_qp builds for it: the first one q1's (warm per opts.warm_start, slot 0, no iterate copy to restart from), the middle ones warm,
 // slot 0, restart allowed, the last one q2's; the horizon shift only reaches the first and the last QP of the first solve after the shift
-template <int NX, int NU, bool BND = false>
-__device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int lane, double *sm, int rti_steps, int shifted, const BndArgs *bdp = nullptr) {
+// CONV (the CONV variants of k_cl_loop_scp): fast-SLS converge mode (fast_SLS_jit.py:298-312), what solve_impl launches with
+// rti_steps <= 0.  rti_steps is the cap max_sls_iter here; QP i = 0 .. cap - 1 with the first call's arguments (warm and restart past the first),
+// after_qp_wave with rti = 0 (it clears `alive` on convergence); the instance leaves at the first iteration that returns no mask -- converged, or its
+// QP failed -- else sweep and tightening; then the last QP, which solves for an instance still alive (it hit the cap, :311) and writes "took no part"
+// for every other, as the batch-wide launch on `alive` does; then k_finish's converge branch (pending: the solver reset of the instance's next solve,
+// applied by solve_begin_wave).  *nsweeps: the sweeps of this solve.  No exit depends on another instance; every bound is wave-uniform.
+template <int NX, int NU, bool BND = false, bool CONV = false>
+__device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int lane, double *sm, int rti_steps, int shifted, const BndArgs *bdp = nullptr, int *pending = nullptr, int *nsweeps = nullptr) {
     const ChainArgs *cp = &c_;
+    [[maybe_unused]] int left = 0, swept = 0;      // CONV: the instance has left the loop (the pass that follows is its last QP); sweeps so far
 #pragma unroll 1
     for (int i = 0; i <= rti_steps; i++) {
         asm volatile("" : "+v"(lane));
@@ -1204,16 +1223,20 @@ __device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int la
             q.stat_slot = i == rti_steps ? 1 : 0;
             q.snap_use = i > 0 ? c.q2.snap_use : 0;
             q.warm_shift = (shifted && (i == 0 || i == rti_steps)) ? c.q.warm_shift : 0;
+            if constexpr (CONV) { if (left) { q.stat_slot = 1; q.warm_shift = shifted ? c.q.warm_shift : 0; } }
             qp_solve_dev<NX, NU, false>(q, b, lane, sm, c.max_ticks);
         }
         wla::wsync_mem();
         if (i == rti_steps) break;
+        if constexpr (CONV) { if (left) break; }
         asm volatile("" : "+v"(lane));
         const ChainArgs &c = args_here<true>(cp);
         AfterQpArgs aq = c.aq;
         aq.first_iter = i == 0 ? 1 : 0; aq.ea.first_iter = aq.first_iter;
+        if constexpr (CONV) aq.rti = 0;
         const int m = __builtin_amdgcn_readfirstlane(after_qp_wave(aq, b, lane));
         wla::wsync_mem();
+        if constexpr (CONV) { if (!m) { left = 1; continue; } swept++; }
         if (!m) continue;
         if (i == 0) {      // beta = eps in every column: one Riccati recursion for all of them
             sweep_ric1_dev<NX, NU>(c.sw, b, lane, sm);
@@ -1239,13 +1262,18 @@ __device__ __forceinline__ void sls_solve_dev(const ChainArgs &c_, int b, int la
     const ChainArgs &c = args_here<true>(cp);
     if (lane == 0) {
         if (c.active && !c.active[b]) c.success[b] = 0;
+        else if constexpr (CONV) { if (c.aq.alive[b] || c.infeas[b]) { c.success[b] = 0; pending[b] = 1; } }      // hit the cap or infeasible (k_finish, converge mode: :304, :312)
         else c.success[b] = (!c.infeas[b]) || c.success[b];           // fast_SLS_jit.py:295 (k_finish, RTI)
     }
+    if constexpr (CONV) *nsweeps = swept;
     wla::wsync_mem();
 }
 // one body for the five variants, as k_cl_loop above: var_ref reads the tracked linear cost in cl_scp_iter_begin, var_pp the plant parameters in
 // cl_scp_step_end, var_bnd the bounds in cl_scp_iter_begin and sls_solve_dev
-template <int MODEL, int VAR>
+// CONV (slsqp_cl_set_sls_converge): every fast-SLS solve of the step runs in converge mode (sls_solve_dev's CONV, S.rti_steps the
+// cap max_sls_iter), and the step's entry of the two per-step arrays behind the block is written.  A flag of its own, not a VAR bit: the five
+// variants exist with and without it, and every statement it adds is under if constexpr (CONV).
+template <int MODEL, int VAR, bool CONV = false>
 __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(const ScpLoopArgs *blk, RefArgs rf, PlantArgs pa) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     int lane = threadIdx.x;
@@ -1264,18 +1292,28 @@ __global__ __launch_bounds__(64, QP_PERSIST_WAVES_PER_SIMD) void k_cl_loop_scp(c
         cl_scp_step_begin<MODEL>(L, b, lane);
         b = __builtin_amdgcn_readfirstlane(b);
         int nsolves = 0;
+        [[maybe_unused]] int nsweeps = 0;      // CONV: the sweeps of the step's last solve
 #pragma unroll 1
         for (int ii = 0; ii < S.max_it; ii++) {
             asm volatile("" : "+v"(lane));
             cl_scp_iter_begin<MODEL, var_ref(VAR), var_bnd(VAR)>(L, b, lane, ii, var_ref(VAR) ? &rf : nullptr, var_bnd(VAR) ? &blk->bd : nullptr);
             b = __builtin_amdgcn_readfirstlane(b);
             asm volatile("" : "+v"(lane));
-            sls_solve_dev<NX, NU, var_bnd(VAR)>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0, var_bnd(VAR) ? &blk->bd : nullptr);
+            if constexpr (CONV) {
+                sls_solve_dev<NX, NU, var_bnd(VAR), true>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0, var_bnd(VAR) ? &blk->bd : nullptr, L.pending, &nsweeps);
+                nsweeps = __builtin_amdgcn_readfirstlane(nsweeps);
+            } else sls_solve_dev<NX, NU, var_bnd(VAR)>(L.c, b, lane, sm, S.rti_steps, ii == 0 ? 1 : 0, var_bnd(VAR) ? &blk->bd : nullptr);
             asm volatile("" : "+v"(lane));
             const int act = __builtin_amdgcn_readfirstlane(cl_scp_iter_end<MODEL>(L, b, lane, ii, S.converge));
             b = __builtin_amdgcn_readfirstlane(b);
             nsolves = ii + 1;
             if (S.converge && !act) break;
+        }
+        if constexpr (CONV) {
+            const SlsConvArgs &V = args_here<true>(conv_blk(blk));
+            const LoopArgs &Lc = args_here<true>(blk).L;
+            const int s = Lc.stepno[b];
+            if (lane == 0 && s < V.log_steps) { V.lastit[(size_t)b * V.log_steps + s] = nsweeps; V.itlog[(size_t)b * V.log_steps + s] = Lc.itnum[b]; }
         }
         asm volatile("" : "+v"(lane));
         const int next = __builtin_amdgcn_readfirstlane(cl_scp_step_end<MODEL, var_pp(VAR)>(S, b, lane, nsolves, var_pp(VAR) ? &pa : nullptr));
@@ -1307,6 +1345,32 @@ __global__ void k_cl_qplog_masked(int B, int steps, int log_steps, const int *ns
             int *qs = qplog + ((size_t)b * log_steps + s) * 16;
             for (int i = 0; i < 16; i++) qs[i] = (i % 8 == 6) ? -1 : 0;
             x0vlog[((size_t)b * log_steps + s) * 2] = 0.0; x0vlog[((size_t)b * log_steps + s) * 2 + 1] = 0.0;      // (a QP that took no part records 0)
+        }
+}
+// fast-SLS converge mode (the CONV variants; cl_sls_conv.hpp): among the instances that took part in the last solve the batch-wide launches of step s
+// run -- the ones with the step's largest number of solves -- an instance that left the fast-SLS loop before the last loop QP was launched has its
+// slot 0 rewritten as "took no part" by the launches that follow.  lastit (B, log_steps): the sweeps of each instance's last solve of the step.
+// One block per step, behind k_cl_qplog_masked (which has dealt with the instances that ran fewer solves).
+__global__ void k_cl_qplog_sls_conv(int B, int steps, int log_steps, int cap, const int *nsolves, const int *lastit, int *qplog, double *x0vlog) {
+    const int s = blockIdx.x;
+    __shared__ int smax, nmax;
+    if (threadIdx.x == 0) { smax = 0; nmax = 0; }
+    __syncthreads();
+    int mx = 0;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) mx = max(mx, nsolves[(size_t)b * log_steps + s]);
+    atomicMax(&smax, mx);
+    __syncthreads();
+    mx = smax;
+    int nm = 0;
+    for (int b = threadIdx.x; b < B; b += blockDim.x) if (nsolves[(size_t)b * log_steps + s] == mx) nm = max(nm, lastit[(size_t)b * log_steps + s]);
+    atomicMax(&nmax, nm);
+    __syncthreads();
+    nm = nmax;
+    for (int b = threadIdx.x; b < B; b += blockDim.x)
+        if (nsolves[(size_t)b * log_steps + s] == mx && cl_sls_conv::slot0_took_no_part(lastit[(size_t)b * log_steps + s], nm, cap)) {
+            int *qs = qplog + ((size_t)b * log_steps + s) * 16;
+            for (int i = 0; i < 8; i++) qs[i] = (i == 6) ? -1 : 0;
+            x0vlog[((size_t)b * log_steps + s) * 2] = 0.0;      // (a QP that took no part records 0)
         }
 }
 
@@ -2422,6 +2486,15 @@ extern "C" int slsqp_cl_set_plan_fallback(slsqp_handle *h, int on) {
     return 0;
 }
 extern "C" int slsqp_cl_get_plan_fallback(slsqp_handle *h) { return h->plan_fallback; }
+// Fast-SLS converge mode inside the persistent launch: a property of the handle, default 0 = off.  1: slsqp_cl_run_scp takes
+// opts.rti_steps <= 0 and runs it on the CONV variants of its kernel; with opts.rti_steps >= 1 it launches what it launches with the option off.
+// Read by slsqp_cl_run_scp alone.  Anything but 0 / 1 is refused and changes nothing.
+extern "C" int slsqp_cl_set_sls_converge(slsqp_handle *h, int on) {
+    if (!cl_sls_conv::valid_option(on)) return fail("slsqp_cl_set_sls_converge: " + std::to_string(on) + " is neither 0 (off) nor 1 (on)");
+    h->sls_converge = on;
+    return 0;
+}
+extern "C" int slsqp_cl_get_sls_converge(slsqp_handle *h) { return h->sls_converge; }
 
 // One closed-loop step WITHOUT a solve: the one-stage shift slsqp_cl_step applies at its top, then k_cl_hold -- the tube policy
 // of the last solve on the measured state, and the plant step.  No slsqp_reset (K stays valid); slsqp_cl_step is not involved and finds, at its next
@@ -2528,8 +2601,9 @@ __global__ void k_cl_begin_flags(int B, const int *begin, int *scp_success, int 
     if (b < B && begin[b]) { scp_success[b] = 0; scp_iters[b] = 0; }
 }
 // the persistent closed-loop launch (k_cl_loop): as many waves as the GPU holds at the kernel's occupancy (or as there are instances)
+// conv: the CONV variant of k_cl_loop_scp (fast-SLS converge mode; S only)
 template <int MODEL>
-static int launch_loop_t(slsqp_handle *h, bool S) {
+static int launch_loop_t(slsqp_handle *h, bool S, bool conv = false) {
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
     const ClOptions op = cl_options(h);      // (the bounds themselves are in the block: make_loop_block)
     // (HOLD: the hold function works in the same dynamic LDS -- the larger of the two sizes; which one binds per model: DESIGN.md section 20)
@@ -2547,6 +2621,7 @@ static int launch_loop_t(slsqp_handle *h, bool S) {
         hipEventRecord(h->ev[8], h->st);
         found = with_loop_var(op.var, [&](auto V) {
             if constexpr (var_hold(V())) hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);      // (k_cl_loop only: refused above for S)
+            else if (S && conv) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V(), true>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);
             else if (S) hipLaunchKernelGGL((k_cl_loop_scp<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);      // (the general sweep's LDS, sweep_lds_doubles, is part of chain_lds_bytes)
             else hipLaunchKernelGGL((k_cl_loop<MODEL, V()>), dim3(grid), dim3(64), lds, h->st, blk, op.rf, op.pa);
         }, /* hold_sets */ !S);
@@ -2558,7 +2633,8 @@ static int launch_loop_t(slsqp_handle *h, bool S) {
 }
 // the argument block of one persistent launch, composed of the builders' results (memset first: the block is copied and compared as bytes); no HIP call in
 // here -- the x0 tolerance its QPs ask for is cl_run_persistent's to write
-static ScpLoopArgs make_loop_block(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, bool scp, int scp_rti) {
+// sls_conv (the CONV variants of k_cl_loop_scp): rti_steps carries the cap opts.max_sls_iter of the fast-SLS loop
+static ScpLoopArgs make_loop_block(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, bool scp, int scp_rti, bool sls_conv = false) {
     const int max_it = !scp ? 1 : (scp_rti > 0 ? scp_rti : o.max_scp_iter);
     ScpLoopArgs S;
     memset(&S, 0, sizeof S);
@@ -2581,7 +2657,7 @@ static ScpLoopArgs make_loop_block(slsqp_handle *h, int steps, const double *dW,
     L.W_all = dW; L.pinf = h->pinf;
     L.Q = ClQueue{h->clq_slots, h->clq_cap - 1u, (unsigned *)h->clq_ctl, (unsigned *)h->clq_ctl + 1, h->clq_ctl + 2, h->clq_ctl + 3};
     L.busy = h->cl_busy; L.t_begin = h->cl_tbegin;
-    S.max_it = max_it; S.converge = scp_rti <= 0 ? 1 : 0; S.rti_steps = o.rti_steps; S.nsolves = h->qplog_nsolves;
+    S.max_it = max_it; S.converge = scp_rti <= 0 ? 1 : 0; S.rti_steps = sls_conv ? o.max_sls_iter : o.rti_steps; S.nsolves = h->qplog_nsolves;
     if (cl_options(h).bnd) { S.bd.rows = h->bnd_rows; S.bd.T = h->bnd_T; S.bd.stride = h->bnd_stride; S.bd.stepno = h->cl_stepno; S.bd.step = 0; }      // (field by field: the padding stays zero; all zero bytes without bounds, and never read)
     return S;
 }
@@ -2633,8 +2709,23 @@ static int write_plan_block(slsqp_handle *h, bool on) {
     h->plan_blk_dev = on ? 1 : 0;
     return 0;
 }
-// scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp)
-static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out, bool scp = false, int scp_rti = 1) {
+// what the CONV variants of k_cl_loop_scp read behind the plan block (no HIP call in make_conv_block; the buffer is cl_run_prepare's): the run's two
+// per-step arrays, indexed with the run's own step count as log_qp_stats is
+static SlsConvArgs make_conv_block(const slsqp_handle *h) {
+    SlsConvArgs V;
+    memset(&V, 0, sizeof V);
+    V.itlog = h->sls_itlog; V.lastit = h->sls_itlog + (size_t)h->B * h->qplog_cap; V.log_steps = h->qplog_steps;
+    return V;
+}
+static int write_conv_block(slsqp_handle *h, const SlsConvArgs &V) {
+    h->conv_blk_host.resize(sizeof V);
+    memcpy(h->conv_blk_host.data(), &V, sizeof V);
+    HIPCHK(hipMemcpyAsync(h->loop_blk + CONV_BLK_OFFSET, h->conv_blk_host.data(), sizeof V, hipMemcpyHostToDevice, h->st));
+    return 0;
+}
+// scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp), sls_conv: its CONV
+// variant (fast-SLS converge mode, opts.max_sls_iter the cap; slsqp_cl_set_sls_converge)
+static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out, bool scp = false, int scp_rti = 1, bool sls_conv = false) {
     const int max_it = !scp ? 1 : (scp_rti > 0 ? scp_rti : o.max_scp_iter);
     const slsqp_dims &d = h->d;
     const int B = h->B;
@@ -2645,9 +2736,10 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     }
     h->time_kernels = o.time_kernels != 0;
     set_x0_tol(h, h->x0_box_tol);
-    const ScpLoopArgs S = make_loop_block(h, steps, dW, o, scp, scp_rti);
+    const ScpLoopArgs S = make_loop_block(h, steps, dW, o, scp, scp_rti, sls_conv);
     const LoopArgs &L = S.L;
     if (write_loop_block(h, S)) return -1;
+    if (sls_conv && write_conv_block(h, make_conv_block(h))) return -1;
     const int M = scp ? 1 : h->solve_every;      // (slsqp_cl_run_scp has refused M > 1 for its own kernel)
     const bool fallback = !scp && h->plan_fallback;      // (slsqp_cl_run_scp has refused the option for its own kernel)
     if ((M > 1 || fallback) && ((fallback ? ensure_plan(h) : ensure_hold(h)) || write_hold_block(h, make_hold_block(h)) || write_plan_block(h, fallback))) return -1;
@@ -2659,8 +2751,9 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     HIPCHK(hipMemsetAsync(h->counter + 2, 0, sizeof(int), h->st));
     const int tl_tot = tl_begin(h, 2), tl_c = tl_begin(h, 4);
     int rc = -1;
-    if (with_model(h, [&](auto M) { rc = launch_loop_t<M()>(h, scp); }) || rc) return -1;
+    if (with_model(h, [&](auto M) { rc = launch_loop_t<M()>(h, scp, sls_conv); }) || rc) return -1;
     if (scp && S.converge) hipLaunchKernelGGL(k_cl_qplog_masked, dim3(steps), dim3(256), 0, h->st, B, steps, h->qplog_steps, h->qplog_nsolves, h->qplog, h->x0vlog);
+    if (sls_conv) hipLaunchKernelGGL(k_cl_qplog_sls_conv, dim3(steps), dim3(256), 0, h->st, B, steps, h->qplog_steps, S.rti_steps, h->qplog_nsolves, h->sls_itlog + (size_t)B * h->qplog_cap, h->qplog, h->x0vlog);
     tl_end(h, tl_c); tl_end(h, tl_tot);
     int ctl[4] = {0, 0, 0, 0};
     std::vector<int> sn((size_t)B);
@@ -2717,18 +2810,22 @@ static int cl_run_prepare(slsqp_handle *h, int steps, const double *W, int loc, 
         if (h->qplog) hipFree(h->qplog);
         if (h->x0vlog) hipFree(h->x0vlog);
         if (h->qplog_nsolves) hipFree(h->qplog_nsolves);
-        h->qplog = nullptr; h->x0vlog = nullptr; h->qplog_nsolves = nullptr; h->qplog_cap = 0; h->qplog_steps = 0;
+        if (h->sls_itlog) hipFree(h->sls_itlog);
+        h->qplog = nullptr; h->x0vlog = nullptr; h->qplog_nsolves = nullptr; h->sls_itlog = nullptr; h->qplog_cap = 0; h->qplog_steps = 0;
         HIPCHK(hipMalloc((void **)&h->qplog, (size_t)B * steps * 16 * sizeof(int) + 64));
         HIPCHK(hipMalloc((void **)&h->x0vlog, (size_t)B * steps * 2 * sizeof(double) + 64));
         HIPCHK(hipMalloc((void **)&h->qplog_nsolves, (size_t)B * steps * sizeof(int) + 64));
+        HIPCHK(hipMalloc((void **)&h->sls_itlog, (size_t)B * steps * 2 * sizeof(int) + 64));
         h->qplog_cap = steps;
     }
     h->qplog_steps = steps;
     HIPCHK(hipMemsetAsync(h->qplog, 0, (size_t)B * steps * 16 * sizeof(int), h->st));
     HIPCHK(hipMemsetAsync(h->qplog_nsolves, 0, (size_t)B * steps * sizeof(int), h->st));
+    HIPCHK(hipMemsetAsync(h->sls_itlog, 0, (size_t)B * h->qplog_cap * 2 * sizeof(int), h->st));
     HIPCHK(hipMemsetAsync(h->x0vlog, 0, (size_t)B * steps * 2 * sizeof(double), h->st));
     h->named["log_qp_stats"] = {h->qplog, sizeof(int) * 16 * (size_t)steps};
     h->named["log_x0_viol"] = {h->x0vlog, sizeof(double) * 2 * (size_t)steps};
+    h->named["log_sls_iterations"] = {h->sls_itlog, sizeof(int) * (size_t)steps};      // written by the CONV variants of k_cl_loop_scp alone (slsqp_cl_set_sls_converge): zeros from every other run
     HIPCHK(hipMemsetAsync(h->cl_stepno, 0, sizeof(int) * B, h->st));
     HIPCHK(hipMemsetAsync(h->cl_lag, 0, sizeof(int) * B, h->st));
     hipLaunchKernelGGL(k_fill_doubles, dim3(64), dim3(256), 0, h->st, h->call_ids, h->call_id, (size_t)B);
@@ -2835,7 +2932,8 @@ extern "C" int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const doubl
     if (opts) o = *opts; else slsqp_default_opts(&o);
     if (h->solve_waves > 1) return fail("slsqp_cl_run_scp: the persistent loop is one wave per instance: solve_waves must be 1 (use slsqp_cl_step with solve_waves > 1)");
     h->ne_waves = 0;      // (slsqp_ne_solve's factors do not survive a QP solve)
-    if (o.rti_steps <= 0) return fail("slsqp_cl_run_scp: fast-SLS converge mode (rti_steps <= 0) does not run inside the persistent loop (use slsqp_cl_step)");
+    const bool sls_conv = o.rti_steps <= 0 && h->sls_converge;      // (slsqp_cl_set_sls_converge: the CONV variants of k_cl_loop_scp)
+    if (const char *why = cl_sls_conv::run_scp_refusal(o.rti_steps, h->sls_converge, o.max_sls_iter)) return fail(why);
     if (o.precision != 0) return fail("slsqp_cl_run_scp: mixed precision (precision = 1) does not run inside the persistent loop: fp64 only (use slsqp_cl_step)");
     if (h->general_G) return fail("slsqp_cl_run_scp: box constraints only (general G: use the sweep-level boundary)");
     if (!(o.fuse_rti && chain_allowed() && sweep_shared_allowed())) return fail("slsqp_cl_run_scp needs the fused chain: fuse_rti = 1, SLSQP_FUSE_RTI and SLSQP_SWEEP_SHARED not 0 (use slsqp_cl_step otherwise)");
@@ -2847,7 +2945,7 @@ extern "C" int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const doubl
     const double *dW = nullptr;
     if (cl_run_prepare(h, steps, W, loc, &dW)) return -1;
     if (rti == 1 && o.rti_steps == 1) return cl_run_persistent(h, steps, dW, o, nullptr);
-    return cl_run_persistent(h, steps, dW, o, nullptr, true, rti);
+    return cl_run_persistent(h, steps, dW, o, nullptr, true, rti, sls_conv);
 }
 
 // ---- QP-level boundary (osqp_generated look-alike, batched) -------------------------------------------------

@@ -275,6 +275,20 @@ class BatchedFastSLS:
     def get_plan_fallback(self):
         return bool(self.lib.slsqp_cl_get_plan_fallback(self.h))
 
+    def set_sls_converge(self, on):
+        """Fast-SLS converge mode inside the persistent launch (slsqp_cl_set_sls_converge): on, slsqp_cl_run_scp takes opts.rti_steps <= 0
+        (set_rti_steps(None)) and every instance iterates its fast-SLS solves to convergence on its own, at most opts.max_sls_iter times; off
+        (default): that setting is refused there.  With a fixed number of fast-SLS steps the option changes nothing.  Anything but a bool / 0 / 1 is
+        refused with the handle unchanged.  get("log_sls_iterations", (steps,), np.int32) reads the sweeps of every MPC step of such a run."""
+        if isinstance(on, (bool, np.bool_)):
+            on = int(on)
+        if not isinstance(on, (int, np.integer)):
+            raise ValueError(f"set_sls_converge: expected a bool or 0 / 1, got {on!r}")
+        L.check(self.lib.slsqp_cl_set_sls_converge(self.h, int(on)))
+
+    def get_sls_converge(self):
+        return bool(self.lib.slsqp_cl_get_sls_converge(self.h))
+
     def tube_ratio(self):
         """(B,) max_i |x_meas_i - z_i| / backoff_x[k, i] of every instance for the hold step k that hold_step would run next (slsqp_cl_tube_ratio), z
         stage k of the plan; inf for an instance without a valid plan.  Refused where hold_step is; changes nothing."""

@@ -17,13 +17,15 @@ def disturbance_stream(seed, steps, nx):
     return np.stack([2.0 * rs.rand(nx) - 1.0 for _ in range(steps)])
 
 
-def can_run_persistent(rti, rti_steps, opts=None, environ=os.environ):
+def can_run_persistent(rti, rti_steps, opts=None, environ=os.environ, sls_converge=False):
     """Whether ClosedLoopMPC.run_decoupled takes this setting (slsqp_cl_run / slsqp_cl_run_scp): any number of SCP iterations `rti` (<= 0: SCP
-    converge mode), a fixed number of fast-SLS steps `rti_steps` >= 1 (None / <= 0 is fast-SLS converge mode: not inside the loop), fp64, and the
-    fused chain with the shared first sweep allowed (opts.fuse_rti, SLSQP_FUSE_RTI, SLSQP_SWEEP_SHARED).  `opts`: a _lib.Opts (or anything with
-    precision / fuse_rti attributes), None = the library's defaults.  Plain Python: needs no handle and no GPU."""
+    converge mode), a fixed number of fast-SLS steps `rti_steps` >= 1 (None / <= 0 is fast-SLS converge mode: inside the loop only with
+    sls_converge=True, run_decoupled's persistent_converge, and then with opts.max_sls_iter >= 1), fp64, and the fused chain with the shared first
+    sweep allowed (opts.fuse_rti, SLSQP_FUSE_RTI, SLSQP_SWEEP_SHARED).  `opts`: a _lib.Opts (or anything with precision / fuse_rti attributes),
+    None = the library's defaults.  Plain Python: needs no handle and no GPU."""
     if rti_steps is None or int(rti_steps) < 1:
-        return False
+        if not sls_converge or (opts is not None and int(getattr(opts, "max_sls_iter", 30)) < 1):
+            return False
     if opts is not None and (int(getattr(opts, "precision", 0)) != 0 or int(getattr(opts, "fuse_rti", 1)) == 0):
         return False
     if opts is None and int(environ.get("SLSQP_PRECISION", "0") or 0) != 0:      # (BatchedFastSLS takes its precision from there)
@@ -46,7 +48,7 @@ PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
 
 
 def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1,
-               reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False):
+               reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False, persistent_converge=False):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
     cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every, hold_trigger=hold_trigger, plan_fallback=plan_fallback)
@@ -58,8 +60,10 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
     if cl.hold_trigger < float("inf") and not hold:
         cl.close()
         raise ValueError("run_monte_carlo: hold_trigger runs in the persistent launch only: pass solve_every = M > 1 and persistent=True (rti = 1 with one fast-SLS step, opts.cl_persistent, solve_waves = 1)")
-    if (solve_every == 1 or hold) and budget_ms != 0 and want and can_run_persistent(cl.rti, rti_steps, cl.f.opts):      # instances advance independently (slsqp_cl_run / slsqp_cl_run_scp): same bits
-        out = cl.run_decoupled(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation, budget_ms=8.0 if budget_ms is None else budget_ms, persistent_hold=hold)
+    # fast-SLS converge mode inside the persistent launch: only when asked for twice (persistent=True and persistent_converge=True)
+    conv = bool(persistent_converge) and persistent is True and rti_steps is None and solve_every == 1 and solve_waves == 1
+    if (solve_every == 1 or hold) and budget_ms != 0 and want and can_run_persistent(cl.rti, rti_steps, cl.f.opts, sls_converge=conv):      # instances advance independently (slsqp_cl_run / slsqp_cl_run_scp): same bits
+        out = cl.run_decoupled(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation, budget_ms=8.0 if budget_ms is None else budget_ms, persistent_hold=hold, persistent_converge=conv)
     else:
         out = cl.run_on_device(X0, steps, W, solve_nominal=solve_nominal, continuation=continuation)
     if cl.nlp_status is not None:
@@ -70,7 +74,7 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
                     budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None,
-                    solve_every=1, hold_trigger=None, plan_fallback=False):
+                    solve_every=1, hold_trigger=None, plan_fallback=False, persistent_converge=False):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
@@ -98,6 +102,10 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     plan_fallback: True = a step of a seed that applies no freshly certified plan (a solve that failed, a hold step) runs the tube policy of the seed's
     last plan that succeeded (ClosedLoopMPC's plan_fallback; rti = 1 with one fast-SLS step); the result then holds `plan_age`, `hold_index` and
     `hold_policy` (seeds, steps), the policy as its code 0 / 1 / 2.  False (default): today's loops, unchanged.
+    persistent_converge: True with persistent=True = a model in fast-SLS converge mode (model.fast_sls_rti_steps None, fast_SLS.solve's default) runs
+    every slice as one persistent launch in which each seed iterates its solves to convergence on its own (run_decoupled's persistent_converge): the
+    bits of the step-by-step loop, plus `qp_stats`, `rounds`, `loop_stats` and `sls_iterations` (seeds, steps).  persistent=None keeps stepping for
+    this mode whatever the flag says.  False (default): today's loops, unchanged.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -153,6 +161,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["hold_trigger"] = hold_trigger
             if plan_fallback:
                 kw["plan_fallback"] = True
+            if persistent_converge:
+                kw["persistent_converge"] = True
             kw.update(options(k))
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:

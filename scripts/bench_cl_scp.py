@@ -10,6 +10,7 @@ times; (c)'s outputs must equal (a)'s bit for bit.  One JSON line: median and mi
     python scripts/bench_cl_scp.py --model pendulum  --batch 1024 --steps 60            # script settings (rti 3, 2 fast-SLS steps)
     python scripts/bench_cl_scp.py --model quadrotor --batch 2048 --steps 30
     python scripts/bench_cl_scp.py --model rocket    --batch 4096 --steps 10 --rti -1 --rti-steps 1      # SCP converge mode (BASELINE config 4)
+    python scripts/bench_cl_scp.py --model rocket    --batch 4096 --steps 10 --rti 1 --sls-converge      # fast-SLS converge mode (fast_SLS.solve's default)
 """
 import argparse
 import dataclasses
@@ -40,9 +41,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--warm-batch", type=int, default=64)
     ap.add_argument("--paths", default="abc")
+    ap.add_argument("--sls-converge", action="store_true",
+                    help="fast-SLS converge mode (fast_sls_rti_steps None: every solve iterates to convergence, --rti-steps is ignored); (c) then is the "
+                    "persistent launch with every instance iterating on its own (run_decoupled's persistent_converge)")
     a = ap.parse_args()
     m = get_model(a.model)
     m = dataclasses.replace(m, rti=m.rti if a.rti is None else a.rti, fast_sls_rti_steps=m.fast_sls_rti_steps if a.rti_steps is None else a.rti_steps)
+    if a.sls_converge:
+        m = dataclasses.replace(m, fast_sls_rti_steps=None)
     N = a.N or (10 if a.model == "pendulum" else 20)
     steps = a.steps or m.extra.get("sim_steps", 30)
     B = a.batch
@@ -52,7 +58,7 @@ def main():
     paths = {
         "a": lambda s: _run_slice(m, N, s, steps, x0, 0, True, True, cont, budget_ms=0),
         "b": lambda s: run_monte_carlo(m, N, s, steps, x0, solve_nominal=True, continuation=cont, budget_ms=0, slices=3),
-        "c": lambda s: _run_slice(m, N, s, steps, x0, 0, True, True, cont, persistent=True),
+        "c": lambda s: _run_slice(m, N, s, steps, x0, 0, True, True, cont, persistent=True, persistent_converge=a.sls_converge),
     }
     res, outs = {}, {}
     for p in a.paths:
@@ -73,6 +79,10 @@ def main():
         line["persistent_launch_ms_per_mpc_step"] = ls["launch_ms"] / steps
         line["solved"] = float(outs["c"]["success"].mean())
         line["scp_iterations_mean"] = float(outs["c"]["scp_iterations"].mean())
+        if "sls_iterations" in outs["c"]:      # --sls-converge: the sweeps per MPC step, the spread the launch exploits
+            it = outs["c"]["sls_iterations"]
+            line["sls_iterations"] = dict(mean=float(it.mean()), max=int(it.max()), quantiles_0_50_90_99=[int(v) for v in np.quantile(it, [0.0, 0.5, 0.9, 0.99])],
+                                          histogram={str(k): int(v) for k, v in zip(*np.unique(it, return_counts=True))})
     if "a" in outs and "c" in outs:
         same = all(np.array_equal(outs["a"][k], outs["c"][k], equal_nan=True) for k in KEYS)
         line["persistent_equals_run_on_device"] = bool(same)
