@@ -61,6 +61,11 @@ def main():
     ap.add_argument("--fast-sls-steps", type=int, default=None, metavar="K",
                     help="fast-SLS steps per solve instead of the script's value; 0: converge mode, every solve iterates until its step is below the tolerance "
                     "(fast_SLS.solve's default) -- with --persistent 1 inside the one launch, every run at its own pace")
+    ap.add_argument("--adversary", default="off", choices=["off", "nearest_bound", "away_from_target"],
+                    help="the disturbance of every plant step is decided on the device from the measured state: every state pushed towards the nearer side of "
+                    "its box, or away from the reference (origin); off: the run's own samples")
+    ap.add_argument("--adversary-amp", type=float, default=1.0, metavar="AMP",
+                    help="size of the adversary's samples (1: the vertices of the box the tubes are computed for; above 1: outside it)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -115,7 +120,7 @@ def main():
         except ValueError as e:
             ap.error(str(e))
     cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P, bounds=bounds,
-                       solve_every=a.solve_every, plan_fallback=a.plan_fallback)
+                       solve_every=a.solve_every, plan_fallback=a.plan_fallback, adversary=None if a.adversary == "off" else a.adversary, adversary_amp=a.adversary_amp)
     if a.fast_sls_steps is not None:
         cl.f.set_rti_steps(a.fast_sls_steps)      # (0: converge mode)
     t0 = time.perf_counter()
@@ -148,6 +153,11 @@ def main():
         du = out["disturbance_used"]
         print(f"plant mismatch: steps with disturbance_used > 1 (model error + noise outside the box the tubes assume): {np.mean(du > 1.0):.3f}; "
               f"largest {np.nanmax(du):.2f}; largest |model error| {np.abs(out['model_error']).max():.3e}")
+    if "w_applied" in out:
+        X = out["state_trajectory"]
+        inside = np.all((X <= m.x_ub[None, :, None]) & (X >= m.x_lb[None, :, None]), axis=1)
+        print(f"adversary {a.adversary} (amp {a.adversary_amp:g}): MPC steps solved {out['success'].mean():.3f}; measured states inside the model's state box "
+              f"{inside.mean():.4f} of the steps; largest disturbance_used {np.nanmax(out['disturbance_used']):.2f}")
     if bounds is not None:
         print(f"bounds {' '.join(a.bound)}: MPC steps solved {out['success'].mean():.3f}; smallest constraint_margin {out['constraint_margin'].min():.3e} "
               f"(negative: the measured state or applied input left the box in force at that step)")

@@ -51,6 +51,11 @@ def main():
                     "and solves when it does not, or after M steps at the latest")
     ap.add_argument("--plan-fallback", action="store_true",
                     help="a step that applies no freshly certified plan (a failed solve, a hold step) runs the tube policy of the seed's last plan that succeeded")
+    ap.add_argument("--adversary", default="off", choices=["off", "nearest_bound", "away_from_target"],
+                    help="the disturbance of every plant step is decided on the device from the seed's measured state: every state pushed towards the nearer "
+                    "side of its box, or away from the origin; off: the seed's uniform stream")
+    ap.add_argument("--adversary-amp", type=float, default=1.0, metavar="AMP",
+                    help="size of the adversary's samples (1: the vertices of the box the tubes are computed for; above 1: outside it)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model("rocket")
@@ -63,7 +68,8 @@ def main():
     t0 = time.perf_counter()
     r = run_monte_carlo(m, a.N, np.arange(a.seeds), a.steps, x0, solve_nominal=(a.init == "sqp"), slices=a.slices, continuation=a.continuation,
                         budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P, solve_every=a.solve_every,
-                        persistent=None if a.persistent is None else bool(a.persistent), hold_trigger=a.hold_trigger, plan_fallback=a.plan_fallback)
+                        persistent=None if a.persistent is None else bool(a.persistent), hold_trigger=a.hold_trigger, plan_fallback=a.plan_fallback,
+                        adversary=None if a.adversary == "off" else a.adversary, adversary_amp=a.adversary_amp)
     dt = time.perf_counter() - t0
     ok = r["success"]
     if "nlp_status" in r:
@@ -85,6 +91,11 @@ def main():
     if "solve_trigger" in r:
         by = [float(np.mean(r["solve_trigger"] == c)) for c in (1, 2, 3)]
         print(f"hold trigger {a.hold_trigger:g}: steps solved on schedule {by[0]:.3f}, because the state left {a.hold_trigger:g} x tube {by[1]:.3f}, after a failed solve {by[2]:.3f}")
+    if "w_applied" in r:
+        X = r["state_trajectory"]
+        inside = np.all((X <= m.x_ub[None, :, None]) & (X >= m.x_lb[None, :, None]), axis=1)
+        print(f"adversary {a.adversary} (amp {a.adversary_amp:g}): measured states inside the state box {inside.mean():.4f} of the steps; "
+              f"largest disturbance_used {np.nanmax(r['disturbance_used']):.2f}")
     if P is not None:
         X = r["state_trajectory"]      # (seeds, nx, steps): the measured states
         viol = np.maximum(X - m.x_ub[None, :, None], m.x_lb[None, :, None] - X).max(axis=1)

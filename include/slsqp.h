@@ -370,6 +370,27 @@ int slsqp_cl_run_scp(slsqp_handle *h, int steps, int rti, const double *W, int l
    by every slsqp_cl_run / slsqp_cl_run_scp, zeros from every run but these. */
 int slsqp_cl_set_sls_converge(slsqp_handle *h, int on);
 int slsqp_cl_get_sls_converge(slsqp_handle *h);
+/* State-feedback disturbance adversary of the closed loops.  A property of the handle, default off: every call launches what it always did.  With a
+   policy on, the sample w of every plant step x+ = ddyn(x, u0) + E w of slsqp_cl_step, slsqp_cl_hold_step, slsqp_cl_run and slsqp_cl_run_scp is decided
+   on the device from the measured state x of the instance at that step (its entry of log_state), per state component i a direction d_i:
+     SLSQP_ADV_NEAREST_BOUND     towards the nearer side of the state's box in force at the step -- row min(s, T - 1) of slsqp_cl_set_bounds' table, else
+                                 the model's g; d_i = +1 when hi_i - x_i <= x_i - lo_i, else -1; a side that is +inf or >= 1e20 is absent: the other one
+                                 pulls, and without either d_i = 0;
+     SLSQP_ADV_AWAY_FROM_TARGET  away from what the loop tracks: d_i = +1 if x_i >= xref_i, else -1, xref the state part of row min(s, T - 1) of
+                                 slsqp_cl_set_reference's table, or zero.
+   A NaN x_i gives d_i = 0.  Channel j gets s_j = sum_i d_i E_ij and w_j = amp sign(s_j) where mask[j] != 0 and s_j != 0; every other channel keeps the
+   caller's W_j (0 where the caller passed none).  For a diagonal E: w_j = amp d_j sign(E_jj).  mask (nx) bytes on the host, NULL = every channel.
+   amp > 1 is accepted: it is outside the box the tubes were designed for.  policy = SLSQP_ADV_OFF clears the option (amp and mask are not read).
+   Refused, with a message that names the argument and the previous setting left in force: an unknown policy; amp NaN, infinite or <= 0; a handle
+   without slsqp_set_model; a general G.  The option changes nothing but the sample the plant step reads: a run with the option off and W = the
+   applied samples gives the same bits.
+   Results (slsqp_get): w_applied (nx), the sample the last plant step used; with slsqp_cl_log, log_w_applied (S,nx), one entry per MPC step (zeros
+   while the option is off). */
+#define SLSQP_ADV_OFF 0
+#define SLSQP_ADV_NEAREST_BOUND 1
+#define SLSQP_ADV_AWAY_FROM_TARGET 2
+int slsqp_cl_set_adversary(slsqp_handle *h, int policy, double amp, const unsigned char *mask /* (nx) host, NULL = every channel */);
+int slsqp_cl_get_adversary(slsqp_handle *h, int *policy, double *amp);
 /* wave statistics of the last persistent slsqp_cl_run / slsqp_cl_run_scp: [0] wavefronts launched, [1] sum over the MPC steps of the time a wavefront spent on them (ms),
    [2] MPC steps run, [3] duration of the launch (ms, HIP events; 0 without opts.time_kernels).  [1] / ([0] x [3]) = how busy the queue kept the waves. */
 #define SLSQP_CL_RUN_STATS_LEN 4

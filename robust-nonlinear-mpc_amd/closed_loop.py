@@ -22,7 +22,8 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 
 class ClosedLoopMPC:
-    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False):
+    def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False,
+                 adversary=None, adversary_amp=1.0, adversary_mask=None):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
         state never fails a step on its own (slsqp_set_x0_box_tol).
@@ -39,7 +40,8 @@ class ClosedLoopMPC:
         last plan that succeeded, from a per-instance backup, while that plan has rows left (BatchedFastSLS.set_plan_fallback; rti = 1 with one
         fast-SLS step).  Honoured by step / hold_step, run, run_on_device and run_decoupled (the persistent launch with persistent_hold=True or M = 1,
         else step by step); their results then hold `plan_age` (B, steps), `hold_index` and `hold_policy` (B, steps) as int32 codes: 2 a failed solve
-        that ran the backup's policy, 1 a hold step that ran it, 0 the nominal input.  False (default): every launch and every bit as before."""
+        that ran the backup's policy, 1 a hold step that ran it, 0 the nominal input.  False (default): every launch and every bit as before.
+        adversary, adversary_amp, adversary_mask: see set_adversary (None: the disturbance is the caller's W, as before)."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -64,6 +66,20 @@ class ClosedLoopMPC:
             self.set_plant_params(plant_params)
         if bounds is not None:
             self.set_bounds(bounds)
+        if adversary is not None:
+            self.set_adversary(adversary, adversary_amp, adversary_mask)
+
+    def set_adversary(self, policy, amp=1.0, mask=None):
+        """State-feedback disturbance adversary from the next plant step on (BatchedFastSLS.set_adversary): "nearest_bound" pushes every state towards
+        the nearer side of its box in force (set_bounds, else the model's), "away_from_target" away from the reference (set_reference, else the
+        origin), as w_j = amp sign(sum_i d_i E_ij) on the channels of `mask` ((nx,), None: all); the other channels keep the W the run was given.
+        None / "off" / 0 clears it.  step, hold_step and every run method then return `w_applied` -- (B,nx) per step, (steps,B,nx) per run -- and
+        the runs `disturbance_used` (steps,B), computed from it; amp > 1 shows there as values above 1."""
+        self.f.set_adversary(policy, amp, mask)
+
+    def _adversary_keys(self):
+        """What a step under the adversary adds: the sample its plant step used; nothing without the option."""
+        return {} if self.f.adversary is None else dict(w_applied=self.f.get("w_applied", (self.m.nx,)))
 
     def _check_solve_every(self, M):
         M = self.solve_every if M is None else int(M)
@@ -171,7 +187,7 @@ class ClosedLoopMPC:
             scp_iterations=f.get("scp_iterations", (), np.int32), primal_infeasibility=f.get("primal_infeasibility", ()),
             x0_violation=np.where(f.get("qp_stats", (2, 8), np.int32)[:, :, 6] == -1, 0.0, f.get("x0_viol", (2,))),      # (0 where the QP took no part, as in the log)
             t_qp_ms=f.timing_ms()["qp"], t_riccati_ms=f.timing_ms()["sweep"], t_jac_ms=f.timing_ms()["jac"],
-            **self._fallback_keys(solved=True),
+            **self._fallback_keys(solved=True), **self._adversary_keys(),
         )
 
     def _fallback_keys(self, solved):
@@ -210,6 +226,7 @@ class ClosedLoopMPC:
             t_qp_ms=0.0, t_riccati_ms=0.0, t_jac_ms=0.0,
         )
         out.update(self._fallback_keys(solved=False))      # (plan_fallback: the policy as its code, and plan_age)
+        out.update(self._adversary_keys())
         return out
 
     def run_on_device(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, solve_every=None, hold_trigger=None):
@@ -258,13 +275,18 @@ class ClosedLoopMPC:
             primal_infeasibility=f.get("log_primal_infeasibility", (steps,)),
             x0_violation=f.get("log_x0_viol", (steps, 2)),
         )
+        wa = None if f.adversary is None else f.get("log_w_applied", (steps, m.nx)).transpose(1, 0, 2).copy()      # (steps, B, nx)
         if f.plant_params is not None:
             me = f.get("log_model_error", (steps, m.nx))
-            out.update(model_error=me.transpose(0, 2, 1).copy(), disturbance_used=self._disturbance_used(me), plant_params=np.array(f.plant_params))
+            out.update(model_error=me.transpose(0, 2, 1).copy(), disturbance_used=self._disturbance_used(me, wa), plant_params=np.array(f.plant_params))
+        if wa is not None:
+            out["w_applied"] = wa
+            out.setdefault("disturbance_used", self._disturbance_used(np.zeros((self.B, steps, m.nx)), wa))
         return self._add_margin(out)
 
-    def _disturbance_used(self, me):
-        """me (B,steps,nx): ddyn_p - ddyn of every plant step.  (steps,B): max_i |(E^-1 me)_i + w_i|, how much of the unit box the tubes assume the
+    def _disturbance_used(self, me, w_applied=None):
+        """me (B,steps,nx): ddyn_p - ddyn of every plant step; w_applied (steps,B,nx): the samples the plant steps used where an adversary chose
+        them (None: the W the run was given).  (steps,B): max_i |(E^-1 me)_i + w_i|, how much of the unit box the tubes assume the
         mismatch and the noise sample of the step used together (> 1: outside what the tubes were designed for); NaN when E is not square and
         nonsingular."""
         m, B, steps = self.m, me.shape[0], me.shape[1]
@@ -272,7 +294,7 @@ class ClosedLoopMPC:
         if E.ndim != 2 or E.shape[0] != E.shape[1] or np.linalg.matrix_rank(E) < E.shape[0]:
             return np.full((steps, B), np.nan)
         wm = np.linalg.solve(E, me.reshape(-1, m.nx).T).T.reshape(B, steps, m.nx)
-        for i, w in enumerate(self._W_log[:steps]):
+        for i, w in enumerate(self._W_log[:steps] if w_applied is None else w_applied[:steps]):
             if w is not None:
                 wm[:, i] += w
         return np.max(np.abs(wm), axis=2).T.copy()
@@ -401,8 +423,13 @@ class ClosedLoopMPC:
             out["x0_violation"][:, i] = r["x0_violation"]
             if self.f.plant_params is not None:
                 out.setdefault("model_error", np.zeros((B, m.nx, steps)))[:, :, i] = self.f.get("model_err", (m.nx,))
+            if "w_applied" in r:
+                out.setdefault("w_applied", np.zeros((steps, B, m.nx)))[i] = r["w_applied"]
+        wa = out.get("w_applied")
         if "model_error" in out:
-            out.update(disturbance_used=self._disturbance_used(out["model_error"].transpose(0, 2, 1)), plant_params=np.array(self.f.plant_params))
+            out.update(disturbance_used=self._disturbance_used(out["model_error"].transpose(0, 2, 1), wa), plant_params=np.array(self.f.plant_params))
+        elif wa is not None:
+            out["disturbance_used"] = self._disturbance_used(np.zeros((B, steps, m.nx)), wa)
         return self._add_margin(out)
 
     def save_npz(self, path, out, b=0):

@@ -156,8 +156,12 @@ __global__ __launch_bounds__(64) void k_cl_tube_ratio(ClArgs cl, const double *b
     const double r = scp_success[b] != 0 ? cl_tube_ratio_wave<MODEL>(cl, backoff_x, b, lane, k) : INFINITY;
     if (lane == 0) out[b] = r;
 }
+// PP: the waves per SIMD the instantiation had before the plant step took a third inlined model step (the model's row, cl_plant_one) are asked for, so
+// that step costs registers of the allocation, not occupancy; 0 without parameters: no request, the code object as it was
 template <int MODEL, bool PP>
-__global__ __launch_bounds__(64) void k_cl_hold(HoldArgs a, PlantArgs pa) {
+constexpr int cl_hold_waves() { return !PP ? 0 : MODEL == 0 ? 5 : MODEL == 1 ? 3 : 2; }
+template <int MODEL, bool PP>
+__global__ __launch_bounds__(64, (cl_hold_waves<MODEL, PP>())) void k_cl_hold(HoldArgs a, PlantArgs pa) {
     __shared__ double sm[cl_hold_lds_doubles<MODEL>()];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= a.cl.B) return;

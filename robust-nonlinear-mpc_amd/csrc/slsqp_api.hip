@@ -97,6 +97,12 @@ struct slsqp_handle {
     // slsqp_cl_set_bounds: the packed rows (sets, T, ni + ni_f) (bnd_stride = T (ni + ni_f) per instance, 0 shared; bnd_rows NULL: none).  bnd_host: the packed
     // rows on the host (slsqp_get "bounds_g" / "bounds_gf"); g_raw_host / gf_raw_host: the model's box, served where no bounds are set.
     double *bnd_rows = nullptr; int bnd_T = 0; size_t bnd_stride = 0; std::vector<double> bnd_host, g_raw_host, gf_raw_host;
+    // slsqp_cl_set_adversary (cl_adversary.hpp): policy (0 = off), amp, the channel mask as a bit set; one allocation made by the
+    // first call that switches it on, [the model's plant parameters (np) | model_err (B, nx) | adv_w (B, nx)]: the row of defaults and the model error
+    // the persistent kernels' PP variants take for a handle without parameters of its own, and the sample every instance's last plant step used.
+    // lg_wadv: its per-step log (part of the slsqp_cl_log buffers).  adv_blk_*: as plan_blk_* for the AdvArgs in loop_blk (ADV_BLK_OFFSET).
+    int adv_policy = 0; double adv_amp = 1.0; unsigned adv_mask = 0u; double *adv_buf = nullptr, *adv_merr = nullptr, *adv_w = nullptr, *lg_wadv = nullptr;
+    int adv_blk_dev = 0; std::vector<unsigned char> adv_blk_host;
     // slsqp_cl_hold_step: which hold step comes next (cl_hold.hpp) and, allocated by the first hold step, one buffer [xi (B,N+1,nx) | u (B,nu)] of the
     // column states and the applied input, and the per-instance flag "the policy ran"; lg_hold / lg_hpol: their per-step log (part of the slsqp_cl_log buffers)
     cl_hold::State hold; double *hold_xi = nullptr, *hold_u = nullptr; int *hold_policy = nullptr, *lg_hold = nullptr, *lg_hpol = nullptr;
@@ -142,16 +148,36 @@ constexpr bool var_hold(int VAR) { return VAR & VAR_HOLD; }
 // without parameters).  hold: the handle's solve_every is above 1 (read by slsqp_cl_run alone: slsqp_cl_step and slsqp_cl_hold_step ignore the setting)
 // or plan fallback is on.
 // fallback: slsqp_cl_set_plan_fallback is on -- a run-time branch inside the HOLD variants, which a run with M = 1 then launches too.
-struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; bool hold; bool fallback; };
+// adv: slsqp_cl_set_adversary is on -- the stepped paths launch k_cl_adversary with aa in front of their plant launch; the persistent
+// kernels branch on the AdvArgs of their block inside the instantiations with the PP bit, so var carries that bit, and a handle without parameters of its
+// own passes the model's row of defaults as pa (cl_plant_one's is_model rule: the model's step, a model error of exactly zero).  pp stays the handle's own.
+struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; bool hold; bool fallback; bool adv; cl_adversary::Args aa; };
+// what the adversary reads at the plant step (no HIP call in here): the bounds in force -- the handle's table, or the model's g as one shared row --
+// and the reference, or one shared row of zeros
+static cl_adversary::Args adv_args(const slsqp_handle *h) {
+    cl_adversary::Args A;
+    memset(&A, 0, sizeof A);
+    A.policy = h->adv_policy; A.nz = h->d.nx + h->d.nu; A.mask = h->adv_mask; A.amp = h->adv_amp;
+    A.adv_w = h->adv_w; A.lg = h->log_steps > 0 ? h->lg_wadv : nullptr; A.S = h->log_steps;
+    if (h->bnd_rows) { A.bd.rows = h->bnd_rows; A.bd.T = h->bnd_T; A.bd.stride = h->bnd_stride; A.bdW = h->d.ni + h->d.ni_f; }
+    else { A.bd.rows = h->g_raw; A.bd.T = 1; A.bd.stride = 0; A.bdW = h->d.ni; }
+    if (h->ref_T > 0) { A.rf.rows = h->ref_Y; A.rf.T = h->ref_T; A.rf.stride = h->ref_stride; }
+    else { A.rf.rows = h->zero_ref; A.rf.T = 1; A.rf.stride = 0; }
+    return A;
+}
 static ClOptions cl_options(const slsqp_handle *h) {
     ClOptions o{};
     o.ref = h->ref_T > 0; o.pp = h->pp_P != nullptr; o.bnd = h->bnd_rows != nullptr;
     o.fallback = h->plan_fallback != 0;
     o.hold = h->solve_every > 1 || o.fallback;
-    o.var = ((o.ref || o.pp || o.bnd || o.hold) ? VAR_REF : 0) | (o.pp ? VAR_PP : 0) | (o.bnd ? VAR_BND : 0) | (o.hold ? VAR_HOLD : 0);
+    o.adv = h->adv_policy != cl_adversary::OFF;
+    const bool ppk = o.pp || o.adv;      // the PP bit of the persistent kernels
+    o.var = ((o.ref || ppk || o.bnd || o.hold) ? VAR_REF : 0) | (ppk ? VAR_PP : 0) | (o.bnd ? VAR_BND : 0) | (o.hold ? VAR_HOLD : 0);
     if (o.ref) o.own_rf = RefArgs{h->ref_Y, h->ref_T, h->ref_stride};
     o.rf = (o.var && !o.ref) ? RefArgs{h->zero_ref, 1, 0} : o.own_rf;
     if (o.pp) o.pa = PlantArgs{h->pp_P, h->pp_stride, h->pp_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps};
+    else if (o.adv) o.pa = PlantArgs{h->adv_buf, 0, h->adv_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps};
+    if (o.adv) o.aa = adv_args(h);
     return o;
 }
 // the bounds' table (empty without bounds) and the MPC step whose window a batch-wide launch reads, of the reference too: `step`, or stepno[b]
@@ -376,7 +402,7 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     free_all(h->owned);
     if (h->stage) hipFree(h->stage);
     if (h->cl_W) hipFree(h->cl_W);
-    opt_clear(&h->ref_Y); opt_clear(&h->pp_P); opt_clear(&h->bnd_rows);
+    opt_clear(&h->ref_Y); opt_clear(&h->pp_P); opt_clear(&h->bnd_rows); opt_clear(&h->adv_buf);
     if (h->hold_xi) hipFree(h->hold_xi);
     if (h->hold_policy) hipFree(h->hold_policy);
     if (h->plan_bk) hipFree(h->plan_bk);
@@ -912,6 +938,14 @@ struct SlsConvArgs { int *lastit, *itlog; int log_steps; };
 constexpr size_t CONV_BLK_OFFSET = (PLAN_BLK_OFFSET + sizeof(PlanArgs) + 15) & ~(size_t)15;
 static_assert(CONV_BLK_OFFSET + sizeof(SlsConvArgs) <= LOOP_BLK_BYTES, "slsqp_handle::loop_blk is 4096 bytes");
 __device__ __forceinline__ const SlsConvArgs *conv_blk(const ScpLoopArgs *blk) { return (const SlsConvArgs *)((const unsigned char *)blk + CONV_BLK_OFFSET); }
+// What the instantiations with the PP bit read at their plant step besides (slsqp_cl_set_adversary): the adversary's arguments
+// (cl_adversary.hpp), BEHIND the CONV block in the same device block -- nothing in front of it moves.  policy = 0 (the zero bytes of a handle that never
+// set the option): none of its other fields is read.  The block starts with the LoopArgs (L is ScpLoopArgs' first member), so both step-end functions
+// reach it from the pointer they hold.
+using AdvArgs = cl_adversary::Args;
+constexpr size_t ADV_BLK_OFFSET = (CONV_BLK_OFFSET + sizeof(SlsConvArgs) + 15) & ~(size_t)15;
+static_assert(ADV_BLK_OFFSET + sizeof(AdvArgs) <= LOOP_BLK_BYTES && sizeof(AdvArgs) % 8 == 0, "slsqp_handle::loop_blk is 4096 bytes");
+__device__ __forceinline__ const AdvArgs *adv_blk(const LoopArgs *blk) { return (const AdvArgs *)((const unsigned char *)blk + ADV_BLK_OFFSET); }
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
 // HOLD (k_cl_loop's hold variants): held != 0 is a hold step of the instance, which takes the shift alone -- no solver reset, so stale, itnum, q
@@ -1012,11 +1046,13 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
     }
     CLSTAMP(9);
     if (lane == 0) {
+        const double *w = L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr;
+        if constexpr (PP) w = cl_adversary_lane<NX>(adv_blk(Lp), L.cl, b, s, w);      // slsqp_cl_set_adversary: the sample is decided here, from x_meas as the plant step reads it
         if constexpr (HOLD) {
             ClArgs c = L.cl;
             if (held || fb) { c.N = 1; c.Un = args_here<true>(hp).a.u; }      // "the first nominal input" of instance b is u[b], as in k_cl_hold: the nominal itself stays the plan
-            cl_plant_one<MODEL, PP>(c, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
-        } else cl_plant_one<MODEL, PP>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
+            cl_plant_one<MODEL, PP>(c, b, w, pa, s);
+        } else cl_plant_one<MODEL, PP>(L.cl, b, w, pa, s);
         L.stepno[b] = s + 1;
         if (L.busy) { atomicAdd(L.busy, wall_clock64() - L.t_begin[b]); atomicAdd(L.busy + 2, 1ULL); }
     }
@@ -1193,7 +1229,9 @@ __device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S_, int b, int lane, in
         if (lane == 0) S.nsolves[(size_t)b * L.c.log_steps + s] = nsolves;
     }
     if (lane == 0) {
-        cl_plant_one<MODEL, PP>(L.cl, b, L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr, pa, s);
+        const double *w = L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr;
+        if constexpr (PP) w = cl_adversary_lane<NX>(adv_blk(&Sp->L), L.cl, b, s, w);      // slsqp_cl_set_adversary, as in cl_step_end
+        cl_plant_one<MODEL, PP>(L.cl, b, w, pa, s);
         L.stepno[b] = s + 1;
         if (L.busy) { atomicAdd(L.busy, wall_clock64() - L.t_begin[b]); atomicAdd(L.busy + 2, 1ULL); }
     }
@@ -1944,6 +1982,7 @@ static int plan_part_named(const char *name) {
 extern "C" long long slsqp_result_bytes(slsqp_handle *h, const char *name) {
     if (!strcmp(name, "plant_params")) return h->model_id < 0 ? -1LL : (long long)sizeof(double) * plant_params::count(h->model_id);
     if (!strcmp(name, "model_err")) return (long long)sizeof(double) * h->d.nx;
+    if (!strcmp(name, "w_applied")) return (long long)sizeof(double) * h->d.nx;
     if (!strcmp(name, "bounds_g")) return (long long)sizeof(double) * h->d.ni * (h->bnd_rows ? h->bnd_T : 1);
     if (!strcmp(name, "bounds_gf")) return (long long)sizeof(double) * h->d.ni_f * (h->bnd_rows ? h->bnd_T : 1);
     if (!strcmp(name, "hold_index") || !strcmp(name, "hold_policy")) return (long long)sizeof(int);
@@ -2054,7 +2093,7 @@ static int get_plant_named(slsqp_handle *h, const char *name, void *out, int loc
     HIPCHK(hipStreamSynchronize(h->st));
     if (is_e) {
         const size_t n = (size_t)h->B * h->d.nx;
-        if (h->pp_P) HIPCHK(hipMemcpy(out, h->pp_merr, sizeof(double) * n, loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+        if (h->pp_P || h->adv_policy != cl_adversary::OFF) HIPCHK(hipMemcpy(out, h->pp_P ? h->pp_merr : h->adv_merr, sizeof(double) * n, loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));      // (under an adversary without parameters: what the persistent kernels' PP variants wrote for the model's row -- zeros)
         else { std::vector<double> z(n, 0.0); HIPCHK(hipMemcpy(out, z.data(), sizeof(double) * n, kind)); }
         return 1;
     }
@@ -2143,13 +2182,16 @@ static int get_plan_named(slsqp_handle *h, const char *name, void *out, int loc)
     return 1;
 }
 
+static int get_adversary_named(slsqp_handle *h, const char *name, void *out, int loc);      // slsqp_cl_set_adversary, below
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
+    if (const int r = get_adversary_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_plant_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_bounds_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_hold_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_plan_named(h, name, out, loc)) return r < 0 ? -1 : 0;
-    if (!h->pp_P && h->lg_merr && !strcmp(name, "log_model_error")) HIPCHK(hipMemsetAsync(h->lg_merr, 0, sizeof(double) * (size_t)h->B * h->log_steps * h->d.nx, h->st));      // (a handle without parameters: all zeros, whatever an earlier run with parameters left)
+    if (h->adv_policy == cl_adversary::OFF && h->lg_wadv && !strcmp(name, "log_w_applied")) HIPCHK(hipMemsetAsync(h->lg_wadv, 0, sizeof(double) * (size_t)h->B * h->log_steps * h->d.nx, h->st));      // (the option is off: all zeros, whatever an earlier run left)
+    if (!h->pp_P && h->adv_policy == cl_adversary::OFF && h->lg_merr && !strcmp(name, "log_model_error")) HIPCHK(hipMemsetAsync(h->lg_merr, 0, sizeof(double) * (size_t)h->B * h->log_steps * h->d.nx, h->st));      // (a handle without parameters: all zeros, whatever an earlier run with parameters left)
     auto it = h->named.find(name);
     if (it == h->named.end()) return fail(std::string("unknown result name: ") + name);
     const size_t bytes = it->second.second * (size_t)h->B;
@@ -2273,6 +2315,10 @@ extern "C" int slsqp_cl_init(slsqp_handle *h, const double *x_meas, const double
     if (h->plan_age) HIPCHK(hipMemsetAsync(h->plan_age, 0xFF, sizeof(int) * B, h->st));      // (plan fallback: no backup, every age -1)
     if (h->lg_age) HIPCHK(hipMemsetAsync(h->lg_age, 0, sizeof(int) * B * h->log_steps, h->st));      // (log_plan_age: written by the steps of a handle with the option on)
     if (h->lg_hold) HIPCHK(hipMemsetAsync(h->lg_hold, 0, sizeof(int) * B * h->log_steps * 2, h->st));      // (log_hold, log_hold_policy: solved steps never write them)
+    if (h->adv_buf) {      // (slsqp_cl_set_adversary: no plant step yet; without parameters of its own the handle's model error and its log are the PP variants' to write, zeros until then)
+        HIPCHK(hipMemsetAsync(h->adv_merr, 0, sizeof(double) * 2 * B * d.nx, h->st));
+        if (!h->pp_P && h->lg_merr) HIPCHK(hipMemsetAsync(h->lg_merr, 0, sizeof(double) * B * h->log_steps * d.nx, h->st));
+    }
     if (h->lg_ratio) { HIPCHK(hipMemsetAsync(h->lg_ratio, 0, sizeof(double) * B * h->log_steps, h->st)); HIPCHK(hipMemsetAsync(h->lg_trig, 0, sizeof(int) * B * h->log_steps, h->st)); }      // (written by event-triggered runs only)
     HIPCHK(hipMemsetAsync(h->has_prev, 0, sizeof(int) * B, h->st));   // a fresh SCP_SLS object has no convergence history
     HIPCHK(hipStreamSynchronize(h->st));
@@ -2342,9 +2388,9 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     HIPCHK(hipStreamSynchronize(h->st));
     h->log_steps = 0;
     free_all(h->log_owned);
-    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy", "log_tube_ratio", "log_solve_trigger", "log_plan_age"};
+    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy", "log_tube_ratio", "log_solve_trigger", "log_plan_age", "log_w_applied"};
     for (const char *nm : names) h->named.erase(nm);
-    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_age = nullptr;
+    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_age = nullptr; h->lg_wadv = nullptr;
     h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr;
     const slsqp_dims &d = h->d;
     const size_t B = h->B, S = max_steps, nX = (size_t)(d.N + 1) * d.nx, nU = (size_t)d.N * d.nu;
@@ -2354,8 +2400,8 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     rc |= dalloc(ow, &h->lg_state, B * S * d.nx); rc |= dalloc(ow, &h->lg_u0, B * S * d.nu); rc |= dalloc(ow, &h->lg_succ, B * S); rc |= dalloc(ow, &h->lg_it, B * S);
     rc |= dalloc(ow, &h->lg_pinf, B * S); rc |= dalloc(ow, &h->lg_x0v, B * S * 2); rc |= dalloc(ow, &h->lg_merr, B * S * d.nx);
     rc |= dalloc(ow, &h->lg_hold, B * S * 2); h->lg_hpol = h->lg_hold ? h->lg_hold + B * S : nullptr;
-    rc |= dalloc(ow, &h->lg_ratio, B * S); rc |= dalloc(ow, &h->lg_trig, B * S); rc |= dalloc(ow, &h->lg_age, B * S);
-    if (rc) { free_all(ow); h->lg_age = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
+    rc |= dalloc(ow, &h->lg_ratio, B * S); rc |= dalloc(ow, &h->lg_trig, B * S); rc |= dalloc(ow, &h->lg_age, B * S); rc |= dalloc(ow, &h->lg_wadv, B * S * d.nx);
+    if (rc) { free_all(ow); h->lg_wadv = nullptr; h->lg_age = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
     h->log_steps = max_steps;
     auto reg = [&](const char *nm, void *p, size_t bytes) { h->named[nm] = {p, bytes}; };
     reg("log_nominal_x", h->lg_x, sizeof(double) * S * nX); reg("log_nominal_u", h->lg_u, sizeof(double) * S * nU);
@@ -2366,6 +2412,7 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     reg("log_hold", h->lg_hold, sizeof(int) * S); reg("log_hold_policy", h->lg_hpol, sizeof(int) * S);      // slsqp_cl_hold_step: 0 for a solved step, k for hold step k; whether the policy ran
     reg("log_tube_ratio", h->lg_ratio, sizeof(double) * S); reg("log_solve_trigger", h->lg_trig, sizeof(int) * S);      // an event-triggered slsqp_cl_run (slsqp_cl_set_hold_trigger): the ratio where it was evaluated, the reason code of cl_hold::decide; zeros from every other run
     reg("log_plan_age", h->lg_age, sizeof(int) * S);      // plan fallback (slsqp_cl_set_plan_fallback): the age every step left behind; zeros from a handle with the option off
+    reg("log_w_applied", h->lg_wadv, sizeof(double) * S * d.nx);      // the sample every step's plant step used under slsqp_cl_set_adversary; zeros from a handle with the option off
     reg("log_model_error", h->lg_merr, sizeof(double) * S * d.nx);      // ddyn_p - ddyn of every step's plant step (slsqp_cl_set_plant_params; zeros without parameters)
     return 0;
 }
@@ -2381,6 +2428,12 @@ static PlanArgs plan_args(const slsqp_handle *h);
 static void hold_args_on_backup(const slsqp_handle *h, HoldArgs &a);
 static ClArgs plant_args_on_u(const slsqp_handle *h, ClArgs a);
 extern const char *const FALLBACK_NEEDS;
+// slsqp_cl_set_adversary on the stepped paths: k_cl_adversary directly in front of a plant launch, which then takes adv_w as its
+// samples.  w (B,nx) or NULL: the caller's sample of this step; step, or mask / stepno / W_all as the plant launch of a round takes them.
+static int launch_adversary(slsqp_handle *h, const ClOptions &op, const double *w, int step, const int *mask, const int *stepno, const double *W_all) {
+    const int gb = (h->B + 63) / 64;
+    return with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_adversary<dyn::Dims<M()>::NX>), dim3(gb), dim3(64), 0, h->st, op.aa, h->B, h->xmeas, h->E, w, step, mask, stepno, W_all); });
+}
 // One MPC step for the whole batch: [warm-start shift + solver reset] -> rti x (linearise, fast-SLS solve of x_nom0 - x_meas,
 // nominal += delta) -> u0 = first nominal input -> plant step x_meas <- ddyn(x_meas,u0) + E w.   w (B,nx) or NULL (no noise).
 extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc, const slsqp_opts *opts) {
@@ -2443,7 +2496,8 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     }
     // plan fallback: one more launch, a wave per instance -- the plan of an instance that succeeded goes into its backup, one that
     // failed runs the backup's policy -- which writes the input to apply for every instance; the plant launch then takes that buffer as a one-stage plan
-    const ClArgs ap = op.fallback ? plant_args_on_u(h, a) : a;
+    ClArgs ap = op.fallback ? plant_args_on_u(h, a) : a;
+    if (op.adv) { if (launch_adversary(h, op, dw, h->cl_steps, nullptr, nullptr, nullptr)) return -1; ap.w = h->adv_w; }      // (x_meas stays as it is until the plant launch)
     if (with_model(h, [&](auto M) {
             if (op.fallback) {
                 const bool log = h->log_steps > 0 && h->cl_steps < h->log_steps;
@@ -2495,6 +2549,42 @@ extern "C" int slsqp_cl_set_sls_converge(slsqp_handle *h, int on) {
     return 0;
 }
 extern "C" int slsqp_cl_get_sls_converge(slsqp_handle *h) { return h->sls_converge; }
+// State-feedback disturbance adversary (cl_adversary.hpp): a property of the handle, default off.  With a policy on, every plant
+// step of slsqp_cl_step, slsqp_cl_hold_step, slsqp_cl_run and slsqp_cl_run_scp reads the sample the rule decides from the measured state, on the
+// channels of `mask` (NULL: every channel); the caller's W stays the sample of every other channel.  policy = 0 clears it.  A refused call -- the
+// message names the argument -- leaves the previous setting in force.
+extern "C" int slsqp_cl_set_adversary(slsqp_handle *h, int policy, double amp, const unsigned char *mask) {
+    std::string why;
+    if (!cl_adversary::check(policy, amp, h->model_id >= 0, h->general_G, h->d.nx, &why)) return fail("slsqp_cl_set_adversary: " + why);
+    hipSetDevice(h->dev);
+    HIPCHK(hipStreamSynchronize(h->st));
+    if (policy == cl_adversary::OFF) { h->adv_policy = cl_adversary::OFF; return 0; }
+    if (!h->adv_buf) {
+        const int np = plant_params::count(h->model_id);
+        const size_t nE = (size_t)h->B * h->d.nx;
+        std::vector<double> dflt((size_t)np);
+        for (int i = 0; i < np; i++) dflt[i] = plant_params::default_value(h->model_id, i);
+        if (opt_install("slsqp_cl_set_adversary", &h->adv_buf, dflt, 2 * nE)) return -1;      // (model_err and adv_w behind the row, zeroed)
+        h->adv_merr = h->adv_buf + np; h->adv_w = h->adv_merr + nE;
+    }
+    h->adv_policy = policy; h->adv_amp = amp; h->adv_mask = cl_adversary::mask_bits(mask, h->d.nx);
+    return 0;
+}
+extern "C" int slsqp_cl_get_adversary(slsqp_handle *h, int *policy, double *amp) {
+    if (policy) *policy = h->adv_policy;
+    if (amp) *amp = h->adv_amp;
+    return 0;
+}
+// slsqp_get name of the adversary: w_applied (B,nx), the sample the last plant step under the option used (zeros on a handle that never had it on).
+// Returns 1 when `name` was it and has been served, 0 when not, -1 on error.
+static int get_adversary_named(slsqp_handle *h, const char *name, void *out, int loc) {
+    if (strcmp(name, "w_applied")) return 0;
+    HIPCHK(hipStreamSynchronize(h->st));
+    const size_t n = (size_t)h->B * h->d.nx;
+    if (h->adv_w) HIPCHK(hipMemcpy(out, h->adv_w, sizeof(double) * n, loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
+    else { const std::vector<double> z(n, 0.0); HIPCHK(hipMemcpy(out, z.data(), sizeof(double) * n, loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice)); }
+    return 1;
+}
 
 // One closed-loop step WITHOUT a solve: the one-stage shift slsqp_cl_step applies at its top, then k_cl_hold -- the tube policy
 // of the last solve on the measured state, and the plant step.  No slsqp_reset (K stays valid); slsqp_cl_step is not involved and finds, at its next
@@ -2554,7 +2644,9 @@ extern "C" int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc) {
     const int gb = (h->B + 63) / 64;
     const double *dw = nullptr;
     if (w) { if (put(h, h->wbuf, w, sizeof(double) * (size_t)h->B * d.nx, loc)) return -1; dw = h->wbuf; }
-    const ClArgs a = cl_args(h, dw);
+    // slsqp_cl_set_adversary: k_cl_adversary goes first (neither the shift nor the policy touches x_meas), and every plant step below reads adv_w
+    if (op.adv && launch_adversary(h, op, dw, h->cl_steps, nullptr, nullptr, nullptr)) return -1;
+    const ClArgs a = cl_args(h, op.adv ? h->adv_w : dw);
     const bool log = h->log_steps > 0 && h->cl_steps < h->log_steps;
     HoldArgs ha{a, k, h->A, h->Bm, h->K, h->Kc, h->stale, h->scp_success, h->hold_xi, h->hold_u, h->hold_policy, log ? h->log_steps : 0, h->cl_steps,
                 h->lg_state, h->lg_u0, h->lg_x0v, h->lg_it, h->lg_hold, h->lg_hpol};
@@ -2723,6 +2815,19 @@ static int write_conv_block(slsqp_handle *h, const SlsConvArgs &V) {
     HIPCHK(hipMemcpyAsync(h->loop_blk + CONV_BLK_OFFSET, h->conv_blk_host.data(), sizeof V, hipMemcpyHostToDevice, h->st));
     return 0;
 }
+// the AdvArgs behind the CONV block (slsqp_cl_set_adversary): written by the runs with the option on, and once more, as zero bytes, by the first
+// persistent launch after it was switched off (the buffer starts as zeros: a handle that never had the option on writes nothing here)
+static int write_adv_block(slsqp_handle *h, bool on) {
+    if (!on && !h->adv_blk_dev) return 0;
+    AdvArgs A;
+    memset(&A, 0, sizeof A);
+    if (on) A = adv_args(h);
+    h->adv_blk_host.resize(sizeof A);
+    memcpy(h->adv_blk_host.data(), &A, sizeof A);
+    HIPCHK(hipMemcpyAsync(h->loop_blk + ADV_BLK_OFFSET, h->adv_blk_host.data(), sizeof A, hipMemcpyHostToDevice, h->st));
+    h->adv_blk_dev = on ? 1 : 0;
+    return 0;
+}
 // scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp), sls_conv: its CONV
 // variant (fast-SLS converge mode, opts.max_sls_iter the cap; slsqp_cl_set_sls_converge)
 static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out, bool scp = false, int scp_rti = 1, bool sls_conv = false) {
@@ -2740,6 +2845,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     const LoopArgs &L = S.L;
     if (write_loop_block(h, S)) return -1;
     if (sls_conv && write_conv_block(h, make_conv_block(h))) return -1;
+    if (write_adv_block(h, h->adv_policy != cl_adversary::OFF)) return -1;
     const int M = scp ? 1 : h->solve_every;      // (slsqp_cl_run_scp has refused M > 1 for its own kernel)
     const bool fallback = !scp && h->plan_fallback;      // (slsqp_cl_run_scp has refused the option for its own kernel)
     if ((M > 1 || fallback) && ((fallback ? ensure_plan(h) : ensure_hold(h)) || write_hold_block(h, make_hold_block(h)) || write_plan_block(h, fallback))) return -1;
@@ -2903,9 +3009,13 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         hipLaunchKernelGGL(k_cl_scp_update, dim3(B), dim3(64), 0, h->st, a, scp_args(h, o, 0, 0));
         if (with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_infeas<M()>), dim3(B), dim3(64), 0, h->st, a, h->scp_upd, h->pinf); })) return -1;
         if (h->log_steps > 0) hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, cl_log_args(h, h->cl_stepno, h->cl_done, 0));
+        // slsqp_cl_set_adversary: every instance of the round's mask gets the sample of ITS step decided from its x_meas, and the plant launch reads adv_w
+        ClArgs aw = a;
+        if (op.adv) { if (launch_adversary(h, op, nullptr, 0, h->cl_done, h->cl_stepno, dW)) return -1; aw.w = h->adv_w; }
+        const double *pW = op.adv ? nullptr : dW;
         if (with_model(h, [&](auto M) {
-                if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, a, op.pa, 0, h->cl_done, h->cl_stepno, dW);
-                else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 0, 1, h->cl_done, h->cl_stepno, dW);
+                if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, aw, op.pa, 0, h->cl_done, h->cl_stepno, pW);
+                else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, aw, 0, 1, h->cl_done, h->cl_stepno, pW);
             })) return -1;
         hipLaunchKernelGGL(k_cl_advance, dim3(gbi), dim3(256), 0, h->st, B, h->cl_done, h->cl_stepno, h->call_ids, h->cl_begin);
         HIPCHK(hipGetLastError());

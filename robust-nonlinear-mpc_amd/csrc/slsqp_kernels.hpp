@@ -20,6 +20,7 @@
 
 #include "dynamics.hpp"
 #include "wave_la.hpp"
+#include "cl_adversary.hpp"
 
 namespace slsqp {
 
@@ -2380,6 +2381,23 @@ struct PlantArgs { const double *P; int stride; double *model_err; double *lg; i
 template <int MODEL, bool PP = false>
 __device__ __forceinline__ void cl_plant_one(const ClArgs &a, int b, const double *w /* (B,NX) sample or NULL */, const PlantArgs *pa = nullptr, int step = 0) {      // one thread
     constexpr int NX = dyn::Dims<MODEL>::NX, NU = dyn::Dims<MODEL>::NU;
+    if constexpr (PP) {
+        // A row that holds the model's constants bit for bit IS the model, and it takes the very statements of the instantiation without parameters, in
+        // a block of their own: the model's RK4 step inlined beside a second evaluation was contracted into multiply-adds differently from the same source
+        // in the kernels without parameters (a few products of the rocket's step), so that "explicit defaults" and "nothing set" differed in the last
+        // bit at some states.  The model error of such a row is exactly zero.
+        constexpr int NP = dyn::Dims<MODEL>::NP;
+        bool row_is_model = true;
+        for (int i = 0; i < NP; i++) row_is_model = row_is_model && pa->P[(size_t)b * pa->stride + i] == dyn::param_default<MODEL>(i);
+        if (row_is_model) {
+            cl_plant_one<MODEL, false>(a, b, w);
+            for (int i = 0; i < NX; i++) {
+                pa->model_err[(size_t)b * NX + i] = 0.0;
+                if (pa->lg && step < pa->S) pa->lg[((size_t)b * pa->S + step) * NX + i] = 0.0;
+            }
+            return;
+        }
+    }
     const double *U = a.Un + (size_t)b * a.N * NU;
     double xm[NX], u[NU], xp[NX];
     for (int i = 0; i < NX; i++) xm[i] = a.xmeas[(size_t)b * NX + i];
@@ -2397,12 +2415,8 @@ __device__ __forceinline__ void cl_plant_one(const ClArgs &a, int b, const doubl
         for (int i = 0; i < NX; i++) asm volatile("" : "+v"(xm[i]));
 #pragma unroll
         for (int i = 0; i < NU; i++) asm volatile("" : "+v"(u[i]));
-        bool is_model = true;
-        for (int i = 0; i < NP; i++) { pr[i] = pa->P[(size_t)b * pa->stride + i]; is_model = is_model && pr[i] == dyn::param_default<MODEL>(i); }
-        // A row that holds the model's constants bit for bit IS the model: it takes the model's step, so that explicit defaults give a model error of
-        // exactly zero (the pointer instantiation does not promise the folded constants' rounding on the device).
-        if (is_model) { for (int i = 0; i < NX; i++) xp[i] = xc[i]; }
-        else dyn::ddyn<MODEL, double, dyn::ParamPtr>(xm, u, xp, dyn::ParamPtr(pr));
+        for (int i = 0; i < NP; i++) pr[i] = pa->P[(size_t)b * pa->stride + i];      // (a row that is the model has left above: the pointer instantiation does not promise the folded constants' rounding)
+        dyn::ddyn<MODEL, double, dyn::ParamPtr>(xm, u, xp, dyn::ParamPtr(pr));
         for (int i = 0; i < NX; i++) {
             const double e = xp[i] - xc[i];
             pa->model_err[(size_t)b * NX + i] = e;
@@ -2446,8 +2460,12 @@ __global__ void k_cl_shift_plant(ClArgs a, int do_shift, int do_plant, const int
 // the plant step of a handle with plant parameters (slsqp_cl_step, the rounds of slsqp_cl_run); the shift stays k_cl_shift_plant's: it is the
 // controller's prediction.  step: the MPC step the instances are at, or stepno[b].  Launched with 64 threads a block: two RK4 steps of the rocket
 // fit the registers of a 64-thread block without scratch
+// (the waves per SIMD the instantiations had before cl_plant_one took the model's row through a third inlined step are asked for: that step costs
+// registers of the allocation, not occupancy)
 template <int MODEL>
-__global__ __launch_bounds__(64) void k_cl_shift_plant_pp(ClArgs a, PlantArgs pa, int step, const int *mask, const int *stepno, const double *W_all) {
+constexpr int cl_plant_pp_waves() { return MODEL == 0 ? 4 : MODEL == 1 ? 3 : 2; }
+template <int MODEL>
+__global__ __launch_bounds__(64, (cl_plant_pp_waves<MODEL>())) void k_cl_shift_plant_pp(ClArgs a, PlantArgs pa, int step, const int *mask, const int *stepno, const double *W_all) {
     constexpr int NX = dyn::Dims<MODEL>::NX;
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.B) return;
@@ -2455,6 +2473,31 @@ __global__ __launch_bounds__(64) void k_cl_shift_plant_pp(ClArgs a, PlantArgs pa
     if (stepno) step = stepno[b];
     if (W_all) a.w = W_all + (size_t)step * a.B * NX;      // (mask[b] implies stepno[b] < steps, as in k_cl_shift_plant)
     cl_plant_one<MODEL, true>(a, b, a.w, &pa, step);
+}
+// The state-feedback adversary of a handle with slsqp_cl_set_adversary (cl_adversary.hpp), launched directly before the plant
+// launch of slsqp_cl_step, slsqp_cl_hold_step and the rounds of slsqp_cl_run: one thread per instance decides the sample from x_meas as the plant step
+// will read it and writes row b of A.adv_w (and the log), which the plant launch then takes as its w.  step / mask / stepno / W_all: as
+// k_cl_shift_plant_pp's (the caller's sample of the instance is row b of w, or of W_all's block of the instance's own step).
+template <int NX>
+__global__ __launch_bounds__(64) void k_cl_adversary(cl_adversary::Args A, int B, const double *xmeas, const double *E, const double *w, int step, const int *mask, const int *stepno, const double *W_all) {
+    static_assert(NX <= cl_adversary::MAX_NX, "the directions travel as a bit set");
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (mask && !mask[b]) return;
+    if (stepno) step = stepno[b];
+    if (W_all) w = W_all + (size_t)step * B * NX;      // (mask[b] implies stepno[b] < steps, as in k_cl_shift_plant)
+    cl_adversary::decide(A, NX, b, step, xmeas + (size_t)b * NX, E, w ? w + (size_t)b * NX : nullptr);
+}
+// The same decision by the lane that runs the plant step of instance b inside a persistent closed-loop kernel (the instantiations with the PP bit):
+// Ap lies in the kernel's argument block.  A run-time branch on the block's policy, uniform over the wave; off (the zero bytes of a handle that never
+// set the option included) returns the caller's samples untouched and reads nothing else.  Returns the (B, NX) array the plant step indexes.
+template <int NX>
+__device__ __forceinline__ const double *cl_adversary_lane(const cl_adversary::Args *Ap, const ClArgs &cl, int b, int s, const double *w) {
+    static_assert(NX <= cl_adversary::MAX_NX, "the directions travel as a bit set");
+    const cl_adversary::Args &A = args_here<true>(Ap);
+    if (A.policy == cl_adversary::OFF) return w;
+    cl_adversary::decide(A, NX, b, s, cl.xmeas + (size_t)b * NX, cl.E, w ? w + (size_t)b * NX : nullptr);
+    return A.adv_w;
 }
 // the same shift of ONE instance by one wave (k_cl_loop): the tail by lane 0, the copies by all lanes (read everything, then write)
 template <int MODEL>

@@ -88,6 +88,34 @@ class _SolverForward:
         L.check(o.lib.slsqp_set(o.h, b"ubg", _ptr(u), L.HOST))
 
 
+ADVERSARY_POLICIES = {"off": 0, "nearest_bound": 1, "away_from_target": 2}      # SLSQP_ADV_* of include/slsqp.h
+
+
+def adversary_arguments(policy, amp=1.0, mask=None, nx=None):
+    """What set_adversary passes to the library, checked without a handle: (code, amp, mask) with code one of ADVERSARY_POLICIES' values (policy None /
+    a name / the code itself), amp a finite float > 0 and mask None (every channel) or (nx,) uint8.  Anything else raises ValueError."""
+    if policy is None:
+        code = 0
+    elif isinstance(policy, str):
+        if policy not in ADVERSARY_POLICIES:
+            raise ValueError(f"adversary: unknown policy {policy!r} (one of {sorted(ADVERSARY_POLICIES)}, or None)")
+        code = ADVERSARY_POLICIES[policy]
+    elif isinstance(policy, (int, np.integer)) and not isinstance(policy, (bool, np.bool_)) and int(policy) in ADVERSARY_POLICIES.values():
+        code = int(policy)
+    else:
+        raise ValueError(f"adversary: unknown policy {policy!r} (one of {sorted(ADVERSARY_POLICIES)}, their codes 0 / 1 / 2, or None)")
+    amp = float(amp)
+    if code and not (np.isfinite(amp) and amp > 0.0):
+        raise ValueError(f"adversary: amp must be finite and > 0 (1 = the vertices of the unit box), got {amp}")
+    mk = None
+    if mask is not None:
+        mk = np.asarray(mask).astype(bool).astype(np.uint8)
+        if mk.ndim != 1 or (nx is not None and mk.shape[0] != nx):
+            raise ValueError(f"adversary: mask must be ({nx},), one entry per disturbance channel, got {mk.shape}")
+        mk = np.ascontiguousarray(mk)
+    return code, amp, mk
+
+
 class BatchedFastSLS:
     def __init__(self, N, Q, R, model, Qf, Q_reg=None, R_reg=None, Q_reg_f=None, batch=1, device=0):
         self.lib = L.load()
@@ -103,6 +131,7 @@ class BatchedFastSLS:
         self.solver_forward = _SolverForward(self)
         self.plant_params = None
         self.bounds = None
+        self.adversary = None
         self.dims = L.Dims(nx, nu, model.nw, self.N, model.ni, model.ni_f)
         self.n = model.nz * self.N + nx
         self.mb = self.N * (nx + model.ni) + model.ni_f
@@ -288,6 +317,23 @@ class BatchedFastSLS:
 
     def get_sls_converge(self):
         return bool(self.lib.slsqp_cl_get_sls_converge(self.h))
+
+    def set_adversary(self, policy, amp=1.0, mask=None):
+        """State-feedback disturbance adversary of the closed-loop entry points (slsqp_cl_set_adversary): with a policy on, the sample of every plant
+        step is decided on the device from the measured state -- "nearest_bound": every state is pushed towards the nearer side of its box in force,
+        "away_from_target": away from the reference (or the origin) -- as w_j = amp sign(sum_i d_i E_ij) on the channels of `mask` ((nx,) truthy =
+        the adversary's; None: every channel); the other channels keep the caller's W.  policy None, "off" or 0 clears it (the default).  amp > 1
+        is accepted: outside the box the tubes were designed for.  An unknown policy and an amp that is NaN, infinite or <= 0 raise and leave the
+        setting as it was.  get("w_applied", (nx,)) reads the sample the last plant step used; self.adversary holds (code, amp) or None."""
+        code, amp, mk = adversary_arguments(policy, amp, mask, self.m.nx)
+        L.check(self.lib.slsqp_cl_set_adversary(self.h, code, amp, None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        self.adversary = None if code == 0 else (code, amp)
+
+    def get_adversary(self):
+        """(policy code, amp) as the handle holds them (slsqp_cl_get_adversary)."""
+        code, amp = C.c_int(0), C.c_double(0.0)
+        L.check(self.lib.slsqp_cl_get_adversary(self.h, C.byref(code), C.byref(amp)))
+        return int(code.value), float(amp.value)
 
     def tube_ratio(self):
         """(B,) max_i |x_meas_i - z_i| / backoff_x[k, i] of every instance for the hold step k that hold_step would run next (slsqp_cl_tube_ratio), z

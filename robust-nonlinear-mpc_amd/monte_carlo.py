@@ -48,10 +48,12 @@ PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
 
 
 def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1,
-               reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False, persistent_converge=False):
+               reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False, persistent_converge=False,
+               adversary=None, adversary_amp=1.0, adversary_mask=None):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
-    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every, hold_trigger=hold_trigger, plan_fallback=plan_fallback)
+    cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every, hold_trigger=hold_trigger, plan_fallback=plan_fallback,
+                       adversary=adversary, adversary_amp=adversary_amp, adversary_mask=adversary_mask)
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
     rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
     want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
@@ -74,7 +76,8 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
                     budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None,
-                    solve_every=1, hold_trigger=None, plan_fallback=False, persistent_converge=False):
+                    solve_every=1, hold_trigger=None, plan_fallback=False, persistent_converge=False,
+                    adversary=None, adversary_amp=1.0, adversary_mask=None):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
@@ -106,6 +109,10 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     every slice as one persistent launch in which each seed iterates its solves to convergence on its own (run_decoupled's persistent_converge): the
     bits of the step-by-step loop, plus `qp_stats`, `rounds`, `loop_stats` and `sls_iterations` (seeds, steps).  persistent=None keeps stepping for
     this mode whatever the flag says.  False (default): today's loops, unchanged.
+    adversary: "nearest_bound" / "away_from_target" = every seed's disturbance is decided on the device from its measured state
+    (ClosedLoopMPC's adversary, adversary_amp, adversary_mask: the same for every seed); the seed's own stream stays the sample of the channels outside
+    the mask.  The result then holds `w_applied` (steps, seeds, nx) and `disturbance_used` (steps, seeds), computed from it.  None / "off" (default):
+    today's loops, unchanged.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -163,6 +170,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["plan_fallback"] = True
             if persistent_converge:
                 kw["persistent_converge"] = True
+            if adversary not in (None, "off", 0):
+                kw.update(adversary=adversary, adversary_amp=adversary_amp, adversary_mask=adversary_mask)
             kw.update(options(k))
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:
@@ -182,7 +191,7 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     for key, v in parts[0].items():
         if key in ("rounds", "loop_stats"):
             out[key] = [p[key] for p in parts]
-        elif key in ("disturbance_used", "constraint_margin"):      # (steps, seeds)
+        elif key in ("disturbance_used", "constraint_margin", "w_applied"):      # (steps, seeds[, nx])
             out[key] = np.concatenate([p[key] for p in parts], axis=1)
         elif key == "plant_params":      # as given: one vector, or a row per seed
             out[key] = v if v.ndim == 1 else np.concatenate([p[key] for p in parts], axis=0)

@@ -2,7 +2,7 @@
 """What holding an MPC solution costs and keeps: the rocket closed loop of bench.py (N = 20, the script's x0, seed-s noise streams) through
 ClosedLoopMPC.run_on_device with a solve every M steps and the tube's feedback policy in between (slsqp_cl_hold_step).
 
-    python scripts/bench_hold.py [--batch 4096] [--steps 30] [--M 1 2 3 5] [--reps 5] [--root DIR] [--persistent [--trigger THETA]]
+    python scripts/bench_hold.py [--batch 4096] [--steps 30] [--M 1 2 3 5] [--reps 5] [--root DIR] [--persistent [--trigger THETA]] [--plant-spread PCT]
 
 --persistent: the same loop as ONE persistent launch (ClosedLoopMPC.run_decoupled, for M > 1 with persistent_hold=True: the hold steps run inside the
 launch); the timed span is then reset's return to the launch's end (the upload of the noise samples included), and the line also
@@ -43,6 +43,9 @@ def main():
     ap.add_argument("--persistent", action="store_true", help="one persistent launch per run instead of one launch sequence per step")
     ap.add_argument("--trigger", type=float, default=None, help="theta of the event-triggered schedule (with --persistent and M > 1; inf or absent: the fixed period)")
     ap.add_argument("--fallback", action="store_true", help="plan fallback on (DESIGN.md section 22): a failed solve and every hold step run the policy of the last plan that succeeded")
+    ap.add_argument("--plant-spread", type=float, default=None, metavar="PCT",
+                    help="every instance's true plant with its parameters within +-PCT %% of their defaults (ClosedLoopMPC's plant_params): the stepped loop then "
+                    "launches the plant-parameter kernels, k_cl_shift_plant_pp and k_cl_hold<., true>")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="the checkout whose package is measured")
     a = ap.parse_args()
     triggered = a.trigger is not None and a.trigger < float("inf")
@@ -61,6 +64,9 @@ def main():
     cl.close()
     for M in a.M:
         kw = dict(plan_fallback=True) if a.fallback else {}      # (off: the option is not named at all, as solve_every for M = 1)
+        if a.plant_spread is not None:
+            from robust_nonlinear_mpc_amd._plant_cli import sample_plant_params
+            kw["plant_params"] = sample_plant_params(m, np.arange(B), a.plant_spread)
         cl = ClosedLoopMPC(m, N, B, **kw) if M == 1 else ClosedLoopMPC(m, N, B, solve_every=M, **kw)
         mark = {}
         reset, log_result = cl.reset, cl._log_result
@@ -89,7 +95,7 @@ def main():
         X = out["state_trajectory"]                                     # (B, nx, steps): the measured state every step started from
         inside = np.all((X <= m.x_ub[None, :, None]) & (X >= m.x_lb[None, :, None]), axis=1)
         solved = np.arange(steps) % M == 0
-        rec = dict(M=M, batch=B, N=N, steps=steps, nlp_ok=nlp_ok, ms_per_step=float(np.median(runs)), ms_per_step_runs=[round(r, 4) for r in runs],
+        rec = dict(M=M, plant_spread=a.plant_spread, batch=B, N=N, steps=steps, nlp_ok=nlp_ok, ms_per_step=float(np.median(runs)), ms_per_step_runs=[round(r, 4) for r in runs],
                    solved_ok=float(out["success"][:, solved].mean()), inside_box=float(inside.mean()))
         if "solve_trigger" in out:      # every instance on its own schedule
             did = out["hold_index"] == 0
