@@ -23,7 +23,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from robust_nonlinear_mpc_amd import ClosedLoopMPC, box_bounds, disturbance_stream, get_model, plant_param_names  # noqa: E402
+from robust_nonlinear_mpc_amd import ClosedLoopMPC, box_bounds, disturbance_stream, get_model, meas_noise_table, measurement_stream, plant_param_names  # noqa: E402
 from robust_nonlinear_mpc_amd._plant_cli import parse_plant_scale, sample_plant_params  # noqa: E402
 
 
@@ -66,6 +66,9 @@ def main():
                     "its box, or away from the reference (origin); off: the run's own samples")
     ap.add_argument("--adversary-amp", type=float, default=1.0, metavar="AMP",
                     help="size of the adversary's samples (1: the vertices of the box the tubes are computed for; above 1: outside it)")
+    ap.add_argument("--meas-noise", type=float, default=None, metavar="AMP",
+                    help="the controller is given x_plant + AMP E[0] v, v a uniform unit sample per run and step, while the plant steps from x_plant "
+                    "(1: the set the tubes' stage-0 column assumes); the printed states are then the true ones")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model(a.model)
@@ -120,7 +123,8 @@ def main():
         except ValueError as e:
             ap.error(str(e))
     cl = ClosedLoopMPC(m, N, B, x0_box_tol=a.x0_box_tol, solve_waves=a.solve_waves, reference=None if Xref is None else (Xref, Uref), plant_params=P, bounds=bounds,
-                       solve_every=a.solve_every, plan_fallback=a.plan_fallback, adversary=None if a.adversary == "off" else a.adversary, adversary_amp=a.adversary_amp)
+                       solve_every=a.solve_every, plan_fallback=a.plan_fallback, adversary=None if a.adversary == "off" else a.adversary, adversary_amp=a.adversary_amp,
+                       meas_noise=None if a.meas_noise is None else meas_noise_table(m, np.stack([measurement_stream(s, steps + 1, m.nw) for s in range(B)]), a.meas_noise))
     if a.fast_sls_steps is not None:
         cl.f.set_rti_steps(a.fast_sls_steps)      # (0: converge mode)
     t0 = time.perf_counter()
@@ -153,6 +157,9 @@ def main():
         du = out["disturbance_used"]
         print(f"plant mismatch: steps with disturbance_used > 1 (model error + noise outside the box the tubes assume): {np.mean(du > 1.0):.3f}; "
               f"largest {np.nanmax(du):.2f}; largest |model error| {np.abs(out['model_error']).max():.3e}")
+    if "measured_trajectory" in out:
+        print(f"measurement noise amp {a.meas_noise:g}: MPC steps solved {out['success'].mean():.3f}; largest |x_meas - x_plant| "
+              f"{np.abs(out['measured_trajectory'] - out['state_trajectory']).max():.3e}; largest stage-0 violation of the measurement {out['x0_violation'].max():.2e}")
     if "w_applied" in out:
         X = out["state_trajectory"]
         inside = np.all((X <= m.x_ub[None, :, None]) & (X >= m.x_lb[None, :, None]), axis=1)

@@ -56,6 +56,9 @@ def main():
                     "side of its box, or away from the origin; off: the seed's uniform stream")
     ap.add_argument("--adversary-amp", type=float, default=1.0, metavar="AMP",
                     help="size of the adversary's samples (1: the vertices of the box the tubes are computed for; above 1: outside it)")
+    ap.add_argument("--meas-noise", type=float, default=None, metavar="AMP",
+                    help="every seed's controller is given x_plant + AMP E[0] v, v a uniform unit sample per step, while the plant steps from x_plant "
+                    "(1: the set the tubes' stage-0 column assumes); the printed states are then the true ones")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     m = get_model("rocket")
@@ -69,7 +72,7 @@ def main():
     r = run_monte_carlo(m, a.N, np.arange(a.seeds), a.steps, x0, solve_nominal=(a.init == "sqp"), slices=a.slices, continuation=a.continuation,
                         budget_ms=a.round_budget_ms, x0_box_tol=a.x0_box_tol, plant_params=P, solve_every=a.solve_every,
                         persistent=None if a.persistent is None else bool(a.persistent), hold_trigger=a.hold_trigger, plan_fallback=a.plan_fallback,
-                        adversary=None if a.adversary == "off" else a.adversary, adversary_amp=a.adversary_amp)
+                        adversary=None if a.adversary == "off" else a.adversary, adversary_amp=a.adversary_amp, meas_noise=a.meas_noise)
     dt = time.perf_counter() - t0
     ok = r["success"]
     if "nlp_status" in r:
@@ -91,6 +94,11 @@ def main():
     if "solve_trigger" in r:
         by = [float(np.mean(r["solve_trigger"] == c)) for c in (1, 2, 3)]
         print(f"hold trigger {a.hold_trigger:g}: steps solved on schedule {by[0]:.3f}, because the state left {a.hold_trigger:g} x tube {by[1]:.3f}, after a failed solve {by[2]:.3f}")
+    if "measured_trajectory" in r:
+        X = r["state_trajectory"]      # (the true states)
+        viol = np.maximum(X - m.x_ub[None, :, None], m.x_lb[None, :, None] - X).max(axis=1)
+        print(f"measurement noise amp {a.meas_noise:g}: largest |x_meas - x_plant| {np.abs(r['measured_trajectory'] - X).max():.3e}; true states outside the "
+              f"state box {np.mean(viol > 0):.4f} of the steps; first QPs refused at x0 {np.mean(r['x0_violation'][:, :, 0] > max(1e-9, a.x0_box_tol)):.4f}")
     if "w_applied" in r:
         X = r["state_trajectory"]
         inside = np.all((X <= m.x_ub[None, :, None]) & (X >= m.x_lb[None, :, None]), axis=1)

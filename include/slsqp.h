@@ -391,6 +391,26 @@ int slsqp_cl_get_sls_converge(slsqp_handle *h);
 #define SLSQP_ADV_AWAY_FROM_TARGET 2
 int slsqp_cl_set_adversary(slsqp_handle *h, int policy, double amp, const unsigned char *mask /* (nx) host, NULL = every channel */);
 int slsqp_cl_get_adversary(slsqp_handle *h, int *policy, double *amp);
+/* Measurement noise of the closed loops.  A property of the handle, default off: every call launches what it always did.  With a table on, the handle
+   keeps two states per instance: x_plant (B,nx), the true state -- the plant step x_plant <- ddyn_p(x_plant, u) + E w reads and writes it, the adversary
+   reads it (its "entry of log_state" becomes "entry of log_plant_state"), model_err / log_model_error are computed from it -- and x_meas = x_plant + n_s,
+   what the controller sees: the pin x_nom0 - x_meas of every solve of the step, the stage-0 gate and x0_viol, the hold policy's e = x_meas - z_k,
+   slsqp_cl_tube_ratio and the event trigger, slsqp_nominal_solve's pin and the roll-out of slsqp_cl_init.  One fp64 addition per component.
+   n_s is row min(s, T - 1) of Nm, s the MPC step counted from slsqp_cl_init (the instance's own count in slsqp_cl_run / slsqp_cl_run_scp); the last row
+   is held, T = 1 is a constant bias.  Nm (T,nx) shared by the batch (per_instance = 0) or (B,T,nx) (per_instance = 1), host or device (`loc`), copied by
+   the call: the error itself, in state coordinates.  The measurement of step s + 1 is formed directly behind the plant step of step s (in the
+   persistent launches before the event-trigger decision that follows it).  slsqp_cl_init(h, x, ...) takes x as the TRUE state: x_plant <- x,
+   x_meas <- x + n_0.
+   slsqp_cl_init LATCHES the table in force: a call of this setter between two slsqp_cl_init calls takes effect at the next slsqp_cl_init and changes
+   nothing in the loop in progress.  The option survives slsqp_cl_init.  T = 0 with Nm = NULL clears it.
+   Refused, with a message that names the argument and the previous table left in force: T < 0; T = 0 with a table; T > 0 without one; a NaN or
+   infinite entry; per_instance outside {0,1}; loc outside {SLSQP_HOST, SLSQP_DEVICE}; a handle without slsqp_set_model.
+   Results (slsqp_get, slsqp_result_bytes): x_plant (nx), equal to x_meas on a handle with the option off; meas_noise (T,nx) per instance, the latched
+   table (a shared one repeated; 0 bytes while off); with slsqp_cl_log: log_plant_state (S,nx), the true state at the top of every step, and
+   log_measured_state (S,nx), x_meas at the top of every step, both in the layout of log_state and, with the option off, copies of it.  log_state
+   keeps its meaning: the state the step's solve was pinned to (stage 0 of the nominal after the step).  slsqp_set takes "x_plant"; with the option on
+   slsqp_set "x_meas" writes the measurement only (with it off both names are the one state). */
+int slsqp_cl_set_meas_noise(slsqp_handle *h, const double *Nm, int T, int per_instance, int loc);
 /* wave statistics of the last persistent slsqp_cl_run / slsqp_cl_run_scp: [0] wavefronts launched, [1] sum over the MPC steps of the time a wavefront spent on them (ms),
    [2] MPC steps run, [3] duration of the launch (ms, HIP events; 0 without opts.time_kernels).  [1] / ([0] x [3]) = how busy the queue kept the waves. */
 #define SLSQP_CL_RUN_STATS_LEN 4

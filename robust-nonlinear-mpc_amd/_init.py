@@ -5,4 +5,4 @@ from ._lib import X0_BOX_TOL_OSQP_DEFAULT  # noqa: F401,E402
 from .fast_sls import BatchedFastSLS, fast_SLS  # noqa: F401,E402
 from .synthetic import make_batch  # noqa: F401,E402
 from .closed_loop import ClosedLoopMPC  # noqa: F401,E402
-from .monte_carlo import run_monte_carlo, disturbance_stream, can_run_persistent  # noqa: F401,E402
+from .monte_carlo import run_monte_carlo, disturbance_stream, can_run_persistent, measurement_stream, meas_noise_table  # noqa: F401,E402

@@ -61,6 +61,7 @@ EXPORTS = [
     "slsqp_cl_set_plan_fallback", "slsqp_cl_get_plan_fallback",
     "slsqp_cl_set_sls_converge", "slsqp_cl_get_sls_converge",
     "slsqp_cl_set_adversary", "slsqp_cl_get_adversary",
+    "slsqp_cl_set_meas_noise",
 ]
 
 _lib = None
@@ -125,6 +126,7 @@ def load():
     lib.slsqp_cl_get_sls_converge.argtypes = [vp]
     lib.slsqp_cl_set_adversary.argtypes = [vp, C.c_int, C.c_double, C.POINTER(C.c_ubyte)]
     lib.slsqp_cl_get_adversary.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    lib.slsqp_cl_set_meas_noise.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
     lib.slsqp_nominal_solve.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.POINTER(Opts)]
     lib.slsqp_cl_log.argtypes = [vp, C.c_int]
     lib.slsqp_cl_run.argtypes = [vp, C.c_int, dp, C.c_int, C.POINTER(Opts), C.c_double, C.c_double, C.POINTER(C.c_int)]

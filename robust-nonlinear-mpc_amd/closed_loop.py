@@ -23,7 +23,7 @@ from .fast_sls import BatchedFastSLS, _c, _ptr
 
 class ClosedLoopMPC:
     def __init__(self, model, N, batch, rti=None, fast_sls_rti_steps=None, device=0, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False,
-                 adversary=None, adversary_amp=1.0, adversary_mask=None):
+                 adversary=None, adversary_amp=1.0, adversary_mask=None, meas_noise=None):
         """x0_box_tol: how far the measured state may lie outside its own stage-0 box (the tightened QP's included) before an MPC step is
         refused as infeasible; 0 = strict (1e-9), X0_BOX_TOL_OSQP_DEFAULT = what the reference's OSQP settings let through, inf = a measured
         state never fails a step on its own (slsqp_set_x0_box_tol).
@@ -41,7 +41,8 @@ class ClosedLoopMPC:
         fast-SLS step).  Honoured by step / hold_step, run, run_on_device and run_decoupled (the persistent launch with persistent_hold=True or M = 1,
         else step by step); their results then hold `plan_age` (B, steps), `hold_index` and `hold_policy` (B, steps) as int32 codes: 2 a failed solve
         that ran the backup's policy, 1 a hold step that ran it, 0 the nominal input.  False (default): every launch and every bit as before.
-        adversary, adversary_amp, adversary_mask: see set_adversary (None: the disturbance is the caller's W, as before)."""
+        adversary, adversary_amp, adversary_mask: see set_adversary (None: the disturbance is the caller's W, as before).
+        meas_noise: see set_meas_noise (None: the controller is given the true plant state, as before)."""
         m = model
         self.m, self.N, self.B = m, int(N), int(batch)
         self.rti = int(m.rti if rti is None else rti)
@@ -68,6 +69,27 @@ class ClosedLoopMPC:
             self.set_bounds(bounds)
         if adversary is not None:
             self.set_adversary(adversary, adversary_amp, adversary_mask)
+        self._mn = None      # the measurement-noise table the loop in progress runs under (latched by reset)
+        if meas_noise is not None:
+            self.set_meas_noise(meas_noise)
+
+    def set_meas_noise(self, Nm):
+        """Measurement noise from the next reset() on (BatchedFastSLS.set_meas_noise): Nm (T,nx) or (B,T,nx), the error of the measurement in state
+        coordinates, row min(s, T - 1) for MPC step s, last row held; None clears it.  The controller is then pinned to x_meas = x_plant + n_s while
+        the plant (and the adversary) run on x_plant.  Honoured by run, run_on_device, run_decoupled, step and hold_step.  Their results change only
+        while the option is on: `state_trajectory` is the TRUE plant trajectory (so `constraint_margin`, `disturbance_used` and `model_error` audit the
+        real system), `measured_trajectory` (B,nx,steps) what the controller saw, `meas_noise` the table; `x0_violation`, `tube_ratio` and
+        `solve_trigger` stay what the controller computed from its measurement.  step / hold_step return `x_plant` (the true state after the plant
+        step) beside `x_next` (the next measurement)."""
+        self.f.set_meas_noise(Nm)
+
+    def _meas_row(self, s):
+        """(B,nx) or (nx,): the latched table's row for MPC step s."""
+        return self._mn[..., min(int(s), self._mn.shape[-2] - 1), :]
+
+    def _meas_keys(self):
+        """What a step under measurement noise adds: the true state its plant step left; nothing without the option."""
+        return {} if self._mn is None else dict(x_plant=self.f.get("x_plant", (self.m.nx,)))
 
     def set_adversary(self, policy, amp=1.0, mask=None):
         """State-feedback disturbance adversary from the next plant step on (BatchedFastSLS.set_adversary): "nearest_bound" pushes every state towards
@@ -156,6 +178,7 @@ class ClosedLoopMPC:
         K = max(1, int(continuation)) if solve_nominal and Xn is None else 1
         x_first = x_meas if K == 1 else _c(m.x_ref + (x_meas - m.x_ref) / K)
         L.check(f.lib.slsqp_cl_init(f.h, _ptr(x_first), _ptr(Xn), _ptr(Un), _ptr(ui), L.HOST))
+        self._mn = f.meas_noise      # (slsqp_cl_init has latched it: x_plant <- x_first, x_meas <- x_first + n_0)
         self.steps_done = 0
         self._W_log = []      # the disturbance samples of the run's steps (disturbance_used)
         self.nlp_status = None
@@ -163,6 +186,9 @@ class ClosedLoopMPC:
             L.check(f.lib.slsqp_nominal_solve(f.h, int(max_qp), float(tol), float(rho), C.byref(f.opts)))
             for k in range(2, K + 1):
                 xs = _c(m.x_ref + (x_meas - m.x_ref) * (k / K))
+                if self._mn is not None:      # (the stages are the controller's: each is pinned to what it would measure there; the truth ends at x_meas)
+                    L.check(f.lib.slsqp_set(f.h, b"x_plant", _ptr(xs), L.HOST))
+                    xs = _c(xs + self._meas_row(0))
                 L.check(f.lib.slsqp_set(f.h, b"x_meas", _ptr(xs), L.HOST))
                 L.check(f.lib.slsqp_nominal_solve(f.h, int(max_qp), float(tol), float(rho), C.byref(f.opts)))
             self.nlp_status = f.get("nlp_status", (), np.int32)
@@ -187,7 +213,7 @@ class ClosedLoopMPC:
             scp_iterations=f.get("scp_iterations", (), np.int32), primal_infeasibility=f.get("primal_infeasibility", ()),
             x0_violation=np.where(f.get("qp_stats", (2, 8), np.int32)[:, :, 6] == -1, 0.0, f.get("x0_viol", (2,))),      # (0 where the QP took no part, as in the log)
             t_qp_ms=f.timing_ms()["qp"], t_riccati_ms=f.timing_ms()["sweep"], t_jac_ms=f.timing_ms()["jac"],
-            **self._fallback_keys(solved=True), **self._adversary_keys(),
+            **self._fallback_keys(solved=True), **self._adversary_keys(), **self._meas_keys(),
         )
 
     def _fallback_keys(self, solved):
@@ -227,6 +253,7 @@ class ClosedLoopMPC:
         )
         out.update(self._fallback_keys(solved=False))      # (plan_fallback: the policy as its code, and plan_age)
         out.update(self._adversary_keys())
+        out.update(self._meas_keys())
         return out
 
     def run_on_device(self, x0, steps, W=None, X_nom=None, U_nom=None, solve_nominal=False, continuation=1, solve_every=None, hold_trigger=None):
@@ -275,6 +302,9 @@ class ClosedLoopMPC:
             primal_infeasibility=f.get("log_primal_infeasibility", (steps,)),
             x0_violation=f.get("log_x0_viol", (steps, 2)),
         )
+        if self._mn is not None:      # measurement noise: the audit keys below are computed from the TRUE trajectory
+            out.update(state_trajectory=f.get("log_plant_state", (steps, m.nx)).transpose(0, 2, 1).copy(),
+                       measured_trajectory=f.get("log_measured_state", (steps, m.nx)).transpose(0, 2, 1).copy(), meas_noise=np.array(self._mn))
         wa = None if f.adversary is None else f.get("log_w_applied", (steps, m.nx)).transpose(1, 0, 2).copy()      # (steps, B, nx)
         if f.plant_params is not None:
             me = f.get("log_model_error", (steps, m.nx))
@@ -399,7 +429,11 @@ class ClosedLoopMPC:
             out.update(hold_index=np.zeros((B, steps), dtype=np.int32), hold_policy=np.zeros((B, steps), dtype=np.int32 if self.plan_fallback else bool))
         if self.plan_fallback:
             out.update(plan_age=np.zeros((B, steps), dtype=np.int32))
+        if self._mn is not None:
+            out.update(measured_trajectory=np.zeros((B, m.nx, steps)), meas_noise=np.array(self._mn))
         for i in range(steps):
+            if self._mn is not None:
+                xp_i, xm_i = self.f.get("x_plant", (m.nx,)), self.f.get("x_meas", (m.nx,))
             if i % M:
                 r = self.hold_step(None if W is None else W[i])
                 out["hold_index"][:, i] = r["hold_index"]
@@ -410,6 +444,8 @@ class ClosedLoopMPC:
             if self.plan_fallback:
                 out["plan_age"][:, i] = r["plan_age"]
             out["state_trajectory"][:, :, i] = r["state"] if i % M else r["nominal_x"][:, 0, :]
+            if self._mn is not None:      # (the true state and the measurement at the top of the step)
+                out["state_trajectory"][:, :, i], out["measured_trajectory"][:, :, i] = xp_i, xm_i
             if i < steps - 1:
                 out["input_trajectory"][:, :, i] = r["u0"]
             out["nominal_trajectory_x"][:, :, :, i] = r["nominal_x"].transpose(0, 2, 1)
@@ -447,4 +483,6 @@ class ClosedLoopMPC:
                      disturbance_used=out["disturbance_used"][:, b])),
                  **({} if "constraint_margin" not in out else dict(      # (only a run with bounds, likewise)
                      constraint_margin=out["constraint_margin"][:, b], bounds_g=out["bounds_g"] if out["bounds_g"].ndim == 2 else out["bounds_g"][b],
-                     bounds_gf=out["bounds_gf"] if out["bounds_gf"].ndim == 2 else out["bounds_gf"][b])))
+                     bounds_gf=out["bounds_gf"] if out["bounds_gf"].ndim == 2 else out["bounds_gf"][b])),
+                 **({} if "measured_trajectory" not in out else dict(      # (only a run with measurement noise, likewise: state_trajectory is the truth there)
+                     measured_trajectory=out["measured_trajectory"][b], meas_noise=out["meas_noise"] if out["meas_noise"].ndim == 2 else out["meas_noise"][b])))

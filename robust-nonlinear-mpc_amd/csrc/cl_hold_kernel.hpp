@@ -173,6 +173,17 @@ __global__ __launch_bounds__(64, (cl_hold_waves<MODEL, PP>())) void k_cl_hold(Ho
         cl_plant_one<MODEL, PP>(c, b, a.cl.w, PP ? &pa : nullptr, a.step);
     }
 }
+// The hold step of a handle with measurement noise (slsqp_cl_set_meas_noise): the policy and the log of k_cl_hold WITHOUT its
+// plant step -- the policy reads the measurement in x_meas, the plant launch that follows (behind k_cl_meas, which puts the truth there) takes u as
+// "the first nominal input" of a one-stage plan, as under plan fallback.
+template <int MODEL>
+__global__ __launch_bounds__(64) void k_cl_hold_policy(HoldArgs a) {
+    __shared__ double sm[cl_hold_lds_doubles<MODEL>()];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= a.cl.B) return;
+    cl_hold_wave<MODEL>(a, b, lane, a.k, sm);
+    cl_hold_log<MODEL>(a, b, lane, a.k, a.step);
+}
 
 // ---- plan fallback (slsqp_cl_set_plan_fallback) ---------------------------------------------------------------------------
 // The live plan of the instances, the backup of each one's last plan that succeeded (same shapes), the age of that backup (cl_hold.hpp) and its

@@ -103,6 +103,13 @@ struct slsqp_handle {
     // lg_wadv: its per-step log (part of the slsqp_cl_log buffers).  adv_blk_*: as plan_blk_* for the AdvArgs in loop_blk (ADV_BLK_OFFSET).
     int adv_policy = 0; double adv_amp = 1.0; unsigned adv_mask = 0u; double *adv_buf = nullptr, *adv_merr = nullptr, *adv_w = nullptr, *lg_wadv = nullptr;
     int adv_blk_dev = 0; std::vector<unsigned char> adv_blk_host;
+    // slsqp_cl_set_meas_noise (cl_meas.hpp): the table the setter last accepted (mn_next: rows on the device, T = 0: none,
+    // stride = T nx per instance or 0 shared, its host copy) and the one slsqp_cl_init latched for the loop in progress (mn); both may name the same
+    // buffer.  x_plant (B, nx): the true state, allocated by the first call that sets a table.  lg_plant / lg_meas: the per-step logs of the truth and of
+    // the measurement (part of the slsqp_cl_log buffers).  mn_blk_*: as adv_blk_* for the cl_meas::Args in loop_blk (MEAS_BLK_OFFSET).
+    struct MeasTab { double *rows = nullptr; int T = 0; size_t stride = 0; std::vector<double> host; } mn, mn_next;
+    double *x_plant = nullptr, *lg_plant = nullptr, *lg_meas = nullptr;
+    int mn_blk_dev = 0; std::vector<unsigned char> mn_blk_host;
     // slsqp_cl_hold_step: which hold step comes next (cl_hold.hpp) and, allocated by the first hold step, one buffer [xi (B,N+1,nx) | u (B,nu)] of the
     // column states and the applied input, and the per-instance flag "the policy ran"; lg_hold / lg_hpol: their per-step log (part of the slsqp_cl_log buffers)
     cl_hold::State hold; double *hold_xi = nullptr, *hold_u = nullptr; int *hold_policy = nullptr, *lg_hold = nullptr, *lg_hpol = nullptr;
@@ -151,7 +158,17 @@ constexpr bool var_hold(int VAR) { return VAR & VAR_HOLD; }
 // adv: slsqp_cl_set_adversary is on -- the stepped paths launch k_cl_adversary with aa in front of their plant launch; the persistent
 // kernels branch on the AdvArgs of their block inside the instantiations with the PP bit, so var carries that bit, and a handle without parameters of its
 // own passes the model's row of defaults as pa (cl_plant_one's is_model rule: the model's step, a model error of exactly zero).  pp stays the handle's own.
-struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; bool hold; bool fallback; bool adv; cl_adversary::Args aa; };
+// mn: slsqp_cl_set_meas_noise is on for the loop in progress -- the stepped paths launch k_cl_meas with ma in front of and behind
+// their plant launch; the persistent kernels branch on the cl_meas::Args of their block inside the instantiations with the PP bit, as for adv.
+struct ClOptions { bool ref, pp, bnd; RefArgs own_rf; int var; RefArgs rf; PlantArgs pa; bool hold; bool fallback; bool adv; cl_adversary::Args aa; bool mn; cl_meas::Args ma; };
+// what the two halves of the measurement rule read (no HIP call in here): the latched table, the true state and the logs
+static cl_meas::Args meas_args(const slsqp_handle *h) {
+    cl_meas::Args A;
+    memset(&A, 0, sizeof A);
+    A.rows = h->mn.rows; A.T = h->mn.T; A.stride = h->mn.stride; A.x_plant = h->x_plant;
+    if (h->log_steps > 0) { A.S = h->log_steps; A.lg_plant = h->lg_plant; A.lg_meas = h->lg_meas; }
+    return A;
+}
 // what the adversary reads at the plant step (no HIP call in here): the bounds in force -- the handle's table, or the model's g as one shared row --
 // and the reference, or one shared row of zeros
 static cl_adversary::Args adv_args(const slsqp_handle *h) {
@@ -171,13 +188,15 @@ static ClOptions cl_options(const slsqp_handle *h) {
     o.fallback = h->plan_fallback != 0;
     o.hold = h->solve_every > 1 || o.fallback;
     o.adv = h->adv_policy != cl_adversary::OFF;
-    const bool ppk = o.pp || o.adv;      // the PP bit of the persistent kernels
+    o.mn = h->mn.T > 0;
+    const bool ppk = o.pp || o.adv || o.mn;      // the PP bit of the persistent kernels
     o.var = ((o.ref || ppk || o.bnd || o.hold) ? VAR_REF : 0) | (ppk ? VAR_PP : 0) | (o.bnd ? VAR_BND : 0) | (o.hold ? VAR_HOLD : 0);
     if (o.ref) o.own_rf = RefArgs{h->ref_Y, h->ref_T, h->ref_stride};
     o.rf = (o.var && !o.ref) ? RefArgs{h->zero_ref, 1, 0} : o.own_rf;
     if (o.pp) o.pa = PlantArgs{h->pp_P, h->pp_stride, h->pp_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps};
-    else if (o.adv) o.pa = PlantArgs{h->adv_buf, 0, h->adv_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps};
+    else if (o.adv || o.mn) o.pa = PlantArgs{h->adv_buf, 0, h->adv_merr, h->log_steps > 0 ? h->lg_merr : nullptr, h->log_steps};
     if (o.adv) o.aa = adv_args(h);
+    if (o.mn) o.ma = meas_args(h);
     return o;
 }
 // the bounds' table (empty without bounds) and the MPC step whose window a batch-wide launch reads, of the reference too: `step`, or stepno[b]
@@ -403,6 +422,9 @@ extern "C" void slsqp_destroy(slsqp_handle *h) {
     if (h->stage) hipFree(h->stage);
     if (h->cl_W) hipFree(h->cl_W);
     opt_clear(&h->ref_Y); opt_clear(&h->pp_P); opt_clear(&h->bnd_rows); opt_clear(&h->adv_buf);
+    if (h->mn_next.rows && h->mn_next.rows != h->mn.rows) hipFree(h->mn_next.rows);
+    if (h->mn.rows) hipFree(h->mn.rows);
+    if (h->x_plant) hipFree(h->x_plant);
     if (h->hold_xi) hipFree(h->hold_xi);
     if (h->hold_policy) hipFree(h->hold_policy);
     if (h->plan_bk) hipFree(h->plan_bk);
@@ -946,6 +968,13 @@ using AdvArgs = cl_adversary::Args;
 constexpr size_t ADV_BLK_OFFSET = (CONV_BLK_OFFSET + sizeof(SlsConvArgs) + 15) & ~(size_t)15;
 static_assert(ADV_BLK_OFFSET + sizeof(AdvArgs) <= LOOP_BLK_BYTES && sizeof(AdvArgs) % 8 == 0, "slsqp_handle::loop_blk is 4096 bytes");
 __device__ __forceinline__ const AdvArgs *adv_blk(const LoopArgs *blk) { return (const AdvArgs *)((const unsigned char *)blk + ADV_BLK_OFFSET); }
+// What the same instantiations read around their plant step for slsqp_cl_set_meas_noise: the arguments of the measurement rule
+// (cl_meas.hpp), BEHIND the adversary's block -- nothing in front of it moves.  T = 0 (the zero bytes of a handle that never set the option): none of
+// its other fields is read.
+using MeasArgs = cl_meas::Args;
+constexpr size_t MEAS_BLK_OFFSET = (ADV_BLK_OFFSET + sizeof(AdvArgs) + 15) & ~(size_t)15;
+static_assert(MEAS_BLK_OFFSET + sizeof(MeasArgs) <= LOOP_BLK_BYTES && sizeof(MeasArgs) % 8 == 0, "slsqp_handle::loop_blk is 4096 bytes");
+__device__ __forceinline__ const MeasArgs *meas_blk(const LoopArgs *blk) { return (const MeasArgs *)((const unsigned char *)blk + MEAS_BLK_OFFSET); }
 // the two halves of an MPC step around the RTI chain, as functions of their own: what they keep in registers (dual numbers of the linearisation, the
 // plant's RK4 stages) stays out of the register allocation of the QP loops, and nothing of theirs is live across the chain
 // HOLD (k_cl_loop's hold variants): held != 0 is a hold step of the instance, which takes the shift alone -- no solver reset, so stale, itnum, q
@@ -1047,12 +1076,14 @@ __device__ CLW_FN int cl_step_end(const LoopArgs &L_, int b, int lane, const Pla
     CLSTAMP(9);
     if (lane == 0) {
         const double *w = L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr;
+        if constexpr (PP) cl_meas_lane<NX>(meas_blk(Lp), L.cl, b, s, false);      // slsqp_cl_set_meas_noise: the controller is done with its measurement; x_meas <- x_plant
         if constexpr (PP) w = cl_adversary_lane<NX>(adv_blk(Lp), L.cl, b, s, w);      // slsqp_cl_set_adversary: the sample is decided here, from x_meas as the plant step reads it
         if constexpr (HOLD) {
             ClArgs c = L.cl;
             if (held || fb) { c.N = 1; c.Un = args_here<true>(hp).a.u; }      // "the first nominal input" of instance b is u[b], as in k_cl_hold: the nominal itself stays the plan
             cl_plant_one<MODEL, PP>(c, b, w, pa, s);
         } else cl_plant_one<MODEL, PP>(L.cl, b, w, pa, s);
+        if constexpr (PP) cl_meas_lane<NX>(meas_blk(Lp), L.cl, b, s, true);      // x_plant <- x_meas, x_meas <- x_meas + n_{s+1}: the trigger's decision below reads the new measurement
         L.stepno[b] = s + 1;
         if (L.busy) { atomicAdd(L.busy, wall_clock64() - L.t_begin[b]); atomicAdd(L.busy + 2, 1ULL); }
     }
@@ -1230,8 +1261,10 @@ __device__ CLW_FN int cl_scp_step_end(const ScpLoopArgs &S_, int b, int lane, in
     }
     if (lane == 0) {
         const double *w = L.W_all ? L.W_all + (size_t)s * L.cl.B * NX : nullptr;
+        if constexpr (PP) cl_meas_lane<NX>(meas_blk(&Sp->L), L.cl, b, s, false);      // slsqp_cl_set_meas_noise, as in cl_step_end
         if constexpr (PP) w = cl_adversary_lane<NX>(adv_blk(&Sp->L), L.cl, b, s, w);      // slsqp_cl_set_adversary, as in cl_step_end
         cl_plant_one<MODEL, PP>(L.cl, b, w, pa, s);
+        if constexpr (PP) cl_meas_lane<NX>(meas_blk(&Sp->L), L.cl, b, s, true);
         L.stepno[b] = s + 1;
         if (L.busy) { atomicAdd(L.busy, wall_clock64() - L.t_begin[b]); atomicAdd(L.busy + 2, 1ULL); }
     }
@@ -1983,6 +2016,8 @@ extern "C" long long slsqp_result_bytes(slsqp_handle *h, const char *name) {
     if (!strcmp(name, "plant_params")) return h->model_id < 0 ? -1LL : (long long)sizeof(double) * plant_params::count(h->model_id);
     if (!strcmp(name, "model_err")) return (long long)sizeof(double) * h->d.nx;
     if (!strcmp(name, "w_applied")) return (long long)sizeof(double) * h->d.nx;
+    if (!strcmp(name, "x_plant")) return (long long)sizeof(double) * h->d.nx;
+    if (!strcmp(name, "meas_noise")) return (long long)sizeof(double) * h->d.nx * h->mn.T;
     if (!strcmp(name, "bounds_g")) return (long long)sizeof(double) * h->d.ni * (h->bnd_rows ? h->bnd_T : 1);
     if (!strcmp(name, "bounds_gf")) return (long long)sizeof(double) * h->d.ni_f * (h->bnd_rows ? h->bnd_T : 1);
     if (!strcmp(name, "hold_index") || !strcmp(name, "hold_policy")) return (long long)sizeof(int);
@@ -2183,9 +2218,11 @@ static int get_plan_named(slsqp_handle *h, const char *name, void *out, int loc)
 }
 
 static int get_adversary_named(slsqp_handle *h, const char *name, void *out, int loc);      // slsqp_cl_set_adversary, below
+static int get_meas_named(slsqp_handle *h, const char *name, void *out, int loc);      // slsqp_cl_set_meas_noise, below
 extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) {
     hipSetDevice(h->dev);
     if (const int r = get_adversary_named(h, name, out, loc)) return r < 0 ? -1 : 0;
+    if (const int r = get_meas_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_plant_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_bounds_named(h, name, out, loc)) return r < 0 ? -1 : 0;
     if (const int r = get_hold_named(h, name, out, loc)) return r < 0 ? -1 : 0;
@@ -2213,12 +2250,17 @@ extern "C" int slsqp_get(slsqp_handle *h, const char *name, void *out, int loc) 
 }
 
 // Overwrite a named array (the reference's callers poke the QP's bounds between solves: QP.update_ubg, qp_jit.py:578-586, used by
-// SCP_SLS_jit.py:86-99).  Writable: ubg, lbg, q, nominal_x, nominal_u, x_meas.
+// SCP_SLS_jit.py:86-99).  Writable: ubg, lbg, q, nominal_x, nominal_u, x_meas, x_plant.
 extern "C" int slsqp_set(slsqp_handle *h, const char *name, const void *src, int loc) {
     hipSetDevice(h->dev);
     static const char *ok[] = {"ubg", "lbg", "q", "nominal_x", "nominal_u", "x_meas"};
     bool allowed = false;
     for (const char *k : ok) allowed |= (strcmp(k, name) == 0);
+    if (!strcmp(name, "x_plant")) {      // the true state: an array of its own under slsqp_cl_set_meas_noise (x_meas then is the measurement alone), else x_meas itself
+        HIPCHK(hipMemcpyAsync(h->mn.T > 0 ? h->x_plant : h->xmeas, src, sizeof(double) * (size_t)h->B * h->d.nx, loc == SLSQP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+        return 0;
+    }
     auto it = h->named.find(name);
     if (!allowed || it == h->named.end()) return fail(std::string("slsqp_set: not a writable array: ") + name);
     const size_t bytes = it->second.second * (size_t)h->B;
@@ -2298,6 +2340,11 @@ extern "C" int slsqp_cl_init(slsqp_handle *h, const double *x_meas, const double
     const slsqp_dims &d = h->d;
     const size_t B = h->B;
     if (put(h, h->xmeas, x_meas, sizeof(double) * B * d.nx, loc)) return -1;
+    // slsqp_cl_set_meas_noise: the table the setter last accepted is in force from here on; `x_meas` is the TRUE state, x_plant <- x, x_meas <- x + n_0
+    // (the roll-out below and slsqp_nominal_solve then start from the measurement)
+    if (h->mn.rows && h->mn.rows != h->mn_next.rows) { HIPCHK(hipStreamSynchronize(h->st)); hipFree(h->mn.rows); }
+    h->mn.rows = h->mn_next.rows; h->mn.T = h->mn_next.T; h->mn.stride = h->mn_next.stride; h->mn.host = h->mn_next.host;
+    if (h->mn.T > 0) hipLaunchKernelGGL(k_cl_meas, dim3((h->B + 63) / 64), dim3(64), 0, h->st, meas_args(h), h->B, d.nx, h->xmeas, 1, -1, nullptr, nullptr);
     if (X_nom && U_nom) {
         if (put(h, h->Xn, X_nom, sizeof(double) * B * (d.N + 1) * d.nx, loc)) return -1;
         if (put(h, h->Un, U_nom, sizeof(double) * B * d.N * d.nu, loc)) return -1;
@@ -2388,9 +2435,9 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     HIPCHK(hipStreamSynchronize(h->st));
     h->log_steps = 0;
     free_all(h->log_owned);
-    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy", "log_tube_ratio", "log_solve_trigger", "log_plan_age", "log_w_applied"};
+    static const char *names[] = {"log_nominal_x", "log_nominal_u", "log_backoff_x", "log_backoff_u", "log_state", "log_u0", "log_success", "log_scp_iterations", "log_primal_infeasibility", "log_x0_viol", "log_model_error", "log_hold", "log_hold_policy", "log_tube_ratio", "log_solve_trigger", "log_plan_age", "log_w_applied", "log_plant_state", "log_measured_state"};
     for (const char *nm : names) h->named.erase(nm);
-    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_age = nullptr; h->lg_wadv = nullptr;
+    h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_age = nullptr; h->lg_wadv = nullptr; h->lg_plant = h->lg_meas = nullptr;
     h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr;
     const slsqp_dims &d = h->d;
     const size_t B = h->B, S = max_steps, nX = (size_t)(d.N + 1) * d.nx, nU = (size_t)d.N * d.nu;
@@ -2401,7 +2448,8 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     rc |= dalloc(ow, &h->lg_pinf, B * S); rc |= dalloc(ow, &h->lg_x0v, B * S * 2); rc |= dalloc(ow, &h->lg_merr, B * S * d.nx);
     rc |= dalloc(ow, &h->lg_hold, B * S * 2); h->lg_hpol = h->lg_hold ? h->lg_hold + B * S : nullptr;
     rc |= dalloc(ow, &h->lg_ratio, B * S); rc |= dalloc(ow, &h->lg_trig, B * S); rc |= dalloc(ow, &h->lg_age, B * S); rc |= dalloc(ow, &h->lg_wadv, B * S * d.nx);
-    if (rc) { free_all(ow); h->lg_wadv = nullptr; h->lg_age = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
+    rc |= dalloc(ow, &h->lg_plant, B * S * d.nx); rc |= dalloc(ow, &h->lg_meas, B * S * d.nx);
+    if (rc) { free_all(ow); h->lg_plant = h->lg_meas = nullptr; h->lg_wadv = nullptr; h->lg_age = nullptr; h->lg_ratio = nullptr; h->lg_trig = nullptr; h->lg_x0v = nullptr; h->lg_merr = nullptr; h->lg_hold = h->lg_hpol = nullptr; h->lg_x = h->lg_u = h->lg_bx = h->lg_bu = h->lg_state = h->lg_u0 = h->lg_pinf = nullptr; h->lg_succ = h->lg_it = nullptr; return -1; }
     h->log_steps = max_steps;
     auto reg = [&](const char *nm, void *p, size_t bytes) { h->named[nm] = {p, bytes}; };
     reg("log_nominal_x", h->lg_x, sizeof(double) * S * nX); reg("log_nominal_u", h->lg_u, sizeof(double) * S * nU);
@@ -2413,6 +2461,7 @@ extern "C" int slsqp_cl_log(slsqp_handle *h, int max_steps) {
     reg("log_tube_ratio", h->lg_ratio, sizeof(double) * S); reg("log_solve_trigger", h->lg_trig, sizeof(int) * S);      // an event-triggered slsqp_cl_run (slsqp_cl_set_hold_trigger): the ratio where it was evaluated, the reason code of cl_hold::decide; zeros from every other run
     reg("log_plan_age", h->lg_age, sizeof(int) * S);      // plan fallback (slsqp_cl_set_plan_fallback): the age every step left behind; zeros from a handle with the option off
     reg("log_w_applied", h->lg_wadv, sizeof(double) * S * d.nx);      // the sample every step's plant step used under slsqp_cl_set_adversary; zeros from a handle with the option off
+    reg("log_plant_state", h->lg_plant, sizeof(double) * S * d.nx); reg("log_measured_state", h->lg_meas, sizeof(double) * S * d.nx);      // slsqp_cl_set_meas_noise: the true state and the measurement at the top of every step; copies of log_state from a handle with the option off (slsqp_get)
     reg("log_model_error", h->lg_merr, sizeof(double) * S * d.nx);      // ddyn_p - ddyn of every step's plant step (slsqp_cl_set_plant_params; zeros without parameters)
     return 0;
 }
@@ -2433,6 +2482,12 @@ extern const char *const FALLBACK_NEEDS;
 static int launch_adversary(slsqp_handle *h, const ClOptions &op, const double *w, int step, const int *mask, const int *stepno, const double *W_all) {
     const int gb = (h->B + 63) / 64;
     return with_model(h, [&](auto M) { hipLaunchKernelGGL((k_cl_adversary<dyn::Dims<M()>::NX>), dim3(gb), dim3(64), 0, h->st, op.aa, h->B, h->xmeas, h->E, w, step, mask, stepno, W_all); });
+}
+// slsqp_cl_set_meas_noise on the stepped paths: k_cl_meas in front of (post = 0) and behind (post = 1) a plant launch, with the
+// step, or the mask / stepno, that launch takes.  Nothing is launched for a handle with the option off.
+static void launch_meas(slsqp_handle *h, const ClOptions &op, int post, int step, const int *mask, const int *stepno) {
+    if (!op.mn) return;
+    hipLaunchKernelGGL(k_cl_meas, dim3((h->B + 63) / 64), dim3(64), 0, h->st, op.ma, h->B, h->d.nx, h->xmeas, post, step, mask, stepno);
 }
 // One MPC step for the whole batch: [warm-start shift + solver reset] -> rti x (linearise, fast-SLS solve of x_nom0 - x_meas,
 // nominal += delta) -> u0 = first nominal input -> plant step x_meas <- ddyn(x_meas,u0) + E w.   w (B,nx) or NULL (no noise).
@@ -2496,19 +2551,23 @@ extern "C" int slsqp_cl_step(slsqp_handle *h, int rti, const double *w, int loc,
     }
     // plan fallback: one more launch, a wave per instance -- the plan of an instance that succeeded goes into its backup, one that
     // failed runs the backup's policy -- which writes the input to apply for every instance; the plant launch then takes that buffer as a one-stage plan
+    // (the policy reads x_meas as the controller saw it, so its launch stands in front of everything that belongs to the plant: under
+    // slsqp_cl_set_meas_noise k_cl_meas puts the truth there for the adversary and the plant step, and the next measurement behind them)
     ClArgs ap = op.fallback ? plant_args_on_u(h, a) : a;
+    if (op.fallback && with_model(h, [&](auto M) {
+            const bool log = h->log_steps > 0 && h->cl_steps < h->log_steps;
+            HoldArgs ha{a, 0, h->A, h->Bm, h->K, h->Kc, h->stale, h->scp_success, h->hold_xi, h->hold_u, h->hold_policy, log ? h->log_steps : 0, h->cl_steps,
+                        h->lg_state, h->lg_u0, h->lg_x0v, h->lg_it, h->lg_hold, h->lg_hpol};
+            hold_args_on_backup(h, ha);
+            hipLaunchKernelGGL((k_cl_plan_fallback<M()>), dim3(h->B), dim3(64), 0, h->st, ha, plan_args(h), 0);
+        })) return -1;
+    launch_meas(h, op, 0, h->cl_steps, nullptr, nullptr);
     if (op.adv) { if (launch_adversary(h, op, dw, h->cl_steps, nullptr, nullptr, nullptr)) return -1; ap.w = h->adv_w; }      // (x_meas stays as it is until the plant launch)
     if (with_model(h, [&](auto M) {
-            if (op.fallback) {
-                const bool log = h->log_steps > 0 && h->cl_steps < h->log_steps;
-                HoldArgs ha{a, 0, h->A, h->Bm, h->K, h->Kc, h->stale, h->scp_success, h->hold_xi, h->hold_u, h->hold_policy, log ? h->log_steps : 0, h->cl_steps,
-                            h->lg_state, h->lg_u0, h->lg_x0v, h->lg_it, h->lg_hold, h->lg_hpol};
-                hold_args_on_backup(h, ha);
-                hipLaunchKernelGGL((k_cl_plan_fallback<M()>), dim3(h->B), dim3(64), 0, h->st, ha, plan_args(h), 0);
-            }
             if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, ap, op.pa, h->cl_steps, nullptr, nullptr, nullptr);      // the plant has its own parameters
             else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, ap, 0, 1);
         })) return -1;
+    launch_meas(h, op, 1, h->cl_steps, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     if (finish_enqueued(h, false)) return -1;
     h->cl_steps++;
@@ -2549,6 +2608,18 @@ extern "C" int slsqp_cl_set_sls_converge(slsqp_handle *h, int on) {
     return 0;
 }
 extern "C" int slsqp_cl_get_sls_converge(slsqp_handle *h) { return h->sls_converge; }
+// the allocation [the model's plant parameters (np) | model_err (B, nx) | adv_w (B, nx)] the persistent kernels' PP variants take for a handle that
+// has an option of theirs on (adversary, measurement noise) and no plant parameters of its own; made by the first setter call that needs it
+static int ensure_model_row(slsqp_handle *h, const char *who) {
+    if (h->adv_buf) return 0;
+    const int np = plant_params::count(h->model_id);
+    const size_t nE = (size_t)h->B * h->d.nx;
+    std::vector<double> dflt((size_t)np);
+    for (int i = 0; i < np; i++) dflt[i] = plant_params::default_value(h->model_id, i);
+    if (opt_install(who, &h->adv_buf, dflt, 2 * nE)) return -1;      // (model_err and adv_w behind the row, zeroed)
+    h->adv_merr = h->adv_buf + np; h->adv_w = h->adv_merr + nE;
+    return 0;
+}
 // State-feedback disturbance adversary (cl_adversary.hpp): a property of the handle, default off.  With a policy on, every plant
 // step of slsqp_cl_step, slsqp_cl_hold_step, slsqp_cl_run and slsqp_cl_run_scp reads the sample the rule decides from the measured state, on the
 // channels of `mask` (NULL: every channel); the caller's W stays the sample of every other channel.  policy = 0 clears it.  A refused call -- the
@@ -2559,14 +2630,7 @@ extern "C" int slsqp_cl_set_adversary(slsqp_handle *h, int policy, double amp, c
     hipSetDevice(h->dev);
     HIPCHK(hipStreamSynchronize(h->st));
     if (policy == cl_adversary::OFF) { h->adv_policy = cl_adversary::OFF; return 0; }
-    if (!h->adv_buf) {
-        const int np = plant_params::count(h->model_id);
-        const size_t nE = (size_t)h->B * h->d.nx;
-        std::vector<double> dflt((size_t)np);
-        for (int i = 0; i < np; i++) dflt[i] = plant_params::default_value(h->model_id, i);
-        if (opt_install("slsqp_cl_set_adversary", &h->adv_buf, dflt, 2 * nE)) return -1;      // (model_err and adv_w behind the row, zeroed)
-        h->adv_merr = h->adv_buf + np; h->adv_w = h->adv_merr + nE;
-    }
+    if (ensure_model_row(h, "slsqp_cl_set_adversary")) return -1;
     h->adv_policy = policy; h->adv_amp = amp; h->adv_mask = cl_adversary::mask_bits(mask, h->d.nx);
     return 0;
 }
@@ -2584,6 +2648,56 @@ static int get_adversary_named(slsqp_handle *h, const char *name, void *out, int
     if (h->adv_w) HIPCHK(hipMemcpy(out, h->adv_w, sizeof(double) * n, loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
     else { const std::vector<double> z(n, 0.0); HIPCHK(hipMemcpy(out, z.data(), sizeof(double) * n, loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice)); }
     return 1;
+}
+
+// Measurement noise (cl_meas.hpp): a property of the handle, default off.  Nm (T,nx) shared by the batch or (B,T,nx), the
+// error of the measurement in state coordinates, row min(s, T - 1) for MPC step s counted from slsqp_cl_init; copied by the call.  T = 0 with
+// Nm = NULL clears it.  The table is latched by slsqp_cl_init: a call between two of them changes nothing in the loop in progress.  A refused call --
+// the message names the argument -- leaves the previous table in force.
+extern "C" int slsqp_cl_set_meas_noise(slsqp_handle *h, const double *Nm, int T, int per_instance, int loc) {
+    std::string why;
+    if (!cl_meas::check(Nm, T, per_instance, loc, h->model_id >= 0, h->B, h->d.nx, &why)) return fail("slsqp_cl_set_meas_noise: " + why);
+    hipSetDevice(h->dev);
+    slsqp_handle::MeasTab &nx_ = h->mn_next;
+    if (T == 0) {
+        if (nx_.rows && nx_.rows != h->mn.rows) hipFree(nx_.rows);      // (a table no slsqp_cl_init has latched; the latched one is the loop's until the next slsqp_cl_init)
+        nx_.rows = nullptr; nx_.T = 0; nx_.stride = 0; nx_.host.clear();
+        return 0;
+    }
+    const size_t n = (size_t)(per_instance ? h->B : 1) * (size_t)T * h->d.nx;
+    std::vector<double> host(n);
+    if (opt_fetch(host, Nm, loc)) return -1;
+    if (!cl_meas::check_entries(host.data(), T, per_instance, h->B, h->d.nx, &why)) return fail("slsqp_cl_set_meas_noise: " + why);
+    if (ensure_model_row(h, "slsqp_cl_set_meas_noise")) return -1;
+    if (!h->x_plant) {
+        HIPCHK(hipMalloc((void **)&h->x_plant, sizeof(double) * (size_t)h->B * h->d.nx + 64));
+        HIPCHK(hipMemset(h->x_plant, 0, sizeof(double) * (size_t)h->B * h->d.nx));
+    }
+    double *fresh = nullptr;      // (never the latched buffer: opt_install frees what the slot holds)
+    if (opt_install("slsqp_cl_set_meas_noise", &fresh, host, 0, &nx_.host)) return -1;
+    if (nx_.rows && nx_.rows != h->mn.rows) hipFree(nx_.rows);
+    nx_.rows = fresh; nx_.T = T; nx_.stride = per_instance ? (size_t)T * h->d.nx : 0;
+    return 0;
+}
+// slsqp_get names of the option: x_plant (B,nx), the true state (x_meas itself while the option is off); meas_noise (B,T,nx), the table in force (a
+// shared one repeated; nothing while the option is off); log_plant_state / log_measured_state on a handle with the option off: copies of log_state,
+// made here, then served like every log.  Returns 1 when `name` has been served, 0 when not (or not yet), -1 on error.
+static int get_meas_named(slsqp_handle *h, const char *name, void *out, int loc) {
+    const size_t n = (size_t)h->B * h->d.nx;
+    if (!strcmp(name, "x_plant")) {
+        HIPCHK(hipMemcpyAsync(out, h->mn.T > 0 ? h->x_plant : h->xmeas, sizeof(double) * n, loc == SLSQP_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+        return 1;
+    }
+    if (!strcmp(name, "meas_noise")) {
+        if (h->mn.T == 0) return 1;
+        const std::vector<double> v = opt_rows(h->B, &h->mn.host, h->mn.stride != 0, h->mn.T, h->d.nx, 0, h->d.nx, nullptr);
+        HIPCHK(hipMemcpy(out, v.data(), sizeof(double) * v.size(), loc == SLSQP_HOST ? hipMemcpyHostToHost : hipMemcpyHostToDevice));
+        return 1;
+    }
+    if (h->mn.T == 0 && h->lg_state && (!strcmp(name, "log_plant_state") || !strcmp(name, "log_measured_state")))
+        HIPCHK(hipMemcpyAsync(!strcmp(name, "log_plant_state") ? h->lg_plant : h->lg_meas, h->lg_state, sizeof(double) * n * h->log_steps, hipMemcpyDeviceToDevice, h->st));
+    return 0;
 }
 
 // One closed-loop step WITHOUT a solve: the one-stage shift slsqp_cl_step applies at its top, then k_cl_hold -- the tube policy
@@ -2645,7 +2759,9 @@ extern "C" int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc) {
     const double *dw = nullptr;
     if (w) { if (put(h, h->wbuf, w, sizeof(double) * (size_t)h->B * d.nx, loc)) return -1; dw = h->wbuf; }
     // slsqp_cl_set_adversary: k_cl_adversary goes first (neither the shift nor the policy touches x_meas), and every plant step below reads adv_w
-    if (op.adv && launch_adversary(h, op, dw, h->cl_steps, nullptr, nullptr, nullptr)) return -1;
+    // slsqp_cl_set_meas_noise: the policy reads the measurement and the adversary the truth, so the order is shift, policy (k_cl_hold_policy, or the
+    // fallback's launch), k_cl_meas, adversary, the plant launch on u, k_cl_meas
+    if (op.adv && !op.mn && launch_adversary(h, op, dw, h->cl_steps, nullptr, nullptr, nullptr)) return -1;
     const ClArgs a = cl_args(h, op.adv ? h->adv_w : dw);
     const bool log = h->log_steps > 0 && h->cl_steps < h->log_steps;
     HoldArgs ha{a, k, h->A, h->Bm, h->K, h->Kc, h->stale, h->scp_success, h->hold_xi, h->hold_u, h->hold_policy, log ? h->log_steps : 0, h->cl_steps,
@@ -2654,11 +2770,15 @@ extern "C" int slsqp_cl_hold_step(slsqp_handle *h, const double *w, int loc) {
     if (with_model(h, [&](auto M) {
             hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, a, 1, 0);
             if (log) hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, cl_log_args(h, nullptr, nullptr, h->cl_steps));      // nominal = the shifted plan, back-offs and success of the last solve; k_cl_hold writes the rest
-            if (op.fallback) {
-                hipLaunchKernelGGL((k_cl_plan_fallback<M()>), dim3(h->B), dim3(64), 0, h->st, ha, plan_args(h), k);
+            if (op.fallback || op.mn) {
+                if (op.fallback) hipLaunchKernelGGL((k_cl_plan_fallback<M()>), dim3(h->B), dim3(64), 0, h->st, ha, plan_args(h), k);
+                else hipLaunchKernelGGL((k_cl_hold_policy<M()>), dim3(h->B), dim3(64), 0, h->st, ha);
+                launch_meas(h, op, 0, h->cl_steps, nullptr, nullptr);
+                if (op.adv && op.mn) hipLaunchKernelGGL((k_cl_adversary<dyn::Dims<M()>::NX>), dim3(gb), dim3(64), 0, h->st, op.aa, h->B, h->xmeas, h->E, dw, h->cl_steps, (const int *)nullptr, (const int *)nullptr, (const double *)nullptr);
                 const ClArgs au = plant_args_on_u(h, a);
                 if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, au, op.pa, h->cl_steps, nullptr, nullptr, nullptr);
                 else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, au, 0, 1);
+                launch_meas(h, op, 1, h->cl_steps, nullptr, nullptr);
             } else with_flag(op.pp, [&](auto PP) { hipLaunchKernelGGL((k_cl_hold<M(), PP()>), dim3(h->B), dim3(64), 0, h->st, ha, op.pa); });
         })) return -1;
     if (log) h->named["log_x0_viol"] = {h->lg_x0v, sizeof(double) * 2 * (size_t)h->log_steps};
@@ -2828,6 +2948,18 @@ static int write_adv_block(slsqp_handle *h, bool on) {
     h->adv_blk_dev = on ? 1 : 0;
     return 0;
 }
+// the cl_meas::Args behind the adversary's block (slsqp_cl_set_meas_noise), written as write_adv_block writes its own
+static int write_meas_block(slsqp_handle *h, bool on) {
+    if (!on && !h->mn_blk_dev) return 0;
+    MeasArgs A;
+    memset(&A, 0, sizeof A);
+    if (on) A = meas_args(h);
+    h->mn_blk_host.resize(sizeof A);
+    memcpy(h->mn_blk_host.data(), &A, sizeof A);
+    HIPCHK(hipMemcpyAsync(h->loop_blk + MEAS_BLK_OFFSET, h->mn_blk_host.data(), sizeof A, hipMemcpyHostToDevice, h->st));
+    h->mn_blk_dev = on ? 1 : 0;
+    return 0;
+}
 // scp = false: k_cl_loop (one SCP iteration, one fast-SLS step per MPC step); true: k_cl_loop_scp with scp_rti (slsqp_cl_run_scp), sls_conv: its CONV
 // variant (fast-SLS converge mode, opts.max_sls_iter the cap; slsqp_cl_set_sls_converge)
 static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const slsqp_opts &o, int *rounds_out, bool scp = false, int scp_rti = 1, bool sls_conv = false) {
@@ -2846,6 +2978,7 @@ static int cl_run_persistent(slsqp_handle *h, int steps, const double *dW, const
     if (write_loop_block(h, S)) return -1;
     if (sls_conv && write_conv_block(h, make_conv_block(h))) return -1;
     if (write_adv_block(h, h->adv_policy != cl_adversary::OFF)) return -1;
+    if (write_meas_block(h, h->mn.T > 0)) return -1;
     const int M = scp ? 1 : h->solve_every;      // (slsqp_cl_run_scp has refused M > 1 for its own kernel)
     const bool fallback = !scp && h->plan_fallback;      // (slsqp_cl_run_scp has refused the option for its own kernel)
     if ((M > 1 || fallback) && ((fallback ? ensure_plan(h) : ensure_hold(h)) || write_hold_block(h, make_hold_block(h)) || write_plan_block(h, fallback))) return -1;
@@ -3011,12 +3144,14 @@ extern "C" int slsqp_cl_run(slsqp_handle *h, int steps, const double *W, int loc
         if (h->log_steps > 0) hipLaunchKernelGGL(k_cl_log, dim3(1024), dim3(256), 0, h->st, cl_log_args(h, h->cl_stepno, h->cl_done, 0));
         // slsqp_cl_set_adversary: every instance of the round's mask gets the sample of ITS step decided from its x_meas, and the plant launch reads adv_w
         ClArgs aw = a;
+        launch_meas(h, op, 0, 0, h->cl_done, h->cl_stepno);      // slsqp_cl_set_meas_noise: around the plant launch, for the instances of its mask at THEIR step
         if (op.adv) { if (launch_adversary(h, op, nullptr, 0, h->cl_done, h->cl_stepno, dW)) return -1; aw.w = h->adv_w; }
         const double *pW = op.adv ? nullptr : dW;
         if (with_model(h, [&](auto M) {
                 if (op.pp) hipLaunchKernelGGL((k_cl_shift_plant_pp<M()>), dim3(gb), dim3(64), 0, h->st, aw, op.pa, 0, h->cl_done, h->cl_stepno, pW);
                 else hipLaunchKernelGGL((k_cl_shift_plant<M()>), dim3(gb), dim3(64), 0, h->st, aw, 0, 1, h->cl_done, h->cl_stepno, pW);
             })) return -1;
+        launch_meas(h, op, 1, 0, h->cl_done, h->cl_stepno);
         hipLaunchKernelGGL(k_cl_advance, dim3(gbi), dim3(256), 0, h->st, B, h->cl_done, h->cl_stepno, h->call_ids, h->cl_begin);
         HIPCHK(hipGetLastError());
     }

@@ -21,6 +21,7 @@
 #include "dynamics.hpp"
 #include "wave_la.hpp"
 #include "cl_adversary.hpp"
+#include "cl_meas.hpp"
 
 namespace slsqp {
 
@@ -2498,6 +2499,28 @@ __device__ __forceinline__ const double *cl_adversary_lane(const cl_adversary::A
     if (A.policy == cl_adversary::OFF) return w;
     cl_adversary::decide(A, NX, b, s, cl.xmeas + (size_t)b * NX, cl.E, w ? w + (size_t)b * NX : nullptr);
     return A.adv_w;
+}
+// Measurement noise of a handle with slsqp_cl_set_meas_noise (cl_meas.hpp) on the stepped paths: one thread per instance runs
+// one half of the rule -- post = 0 directly in front of the adversary / plant launch of slsqp_cl_step, slsqp_cl_hold_step and the rounds of slsqp_cl_run
+// (x_meas <- x_plant, the log entries of the step), post = 1 directly behind the plant launch (x_plant <- x_meas, x_meas <- x_meas + n_{s+1}); slsqp_cl_init
+// launches post with step = -1.  step / mask / stepno: as k_cl_adversary's.
+__global__ __launch_bounds__(64) void k_cl_meas(cl_meas::Args A, int B, int nx, double *xmeas, int post, int step, const int *mask, const int *stepno) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (mask && !mask[b]) return;
+    if (stepno) step = stepno[b];
+    if (post) cl_meas::post(A, nx, b, step, xmeas + (size_t)b * nx);
+    else cl_meas::pre(A, nx, b, step, xmeas + (size_t)b * nx);
+}
+// The same two halves by the lane that runs the plant step of instance b inside a persistent closed-loop kernel (the instantiations with the PP bit):
+// Ap lies in the kernel's argument block.  A run-time branch on the block's T, uniform over the wave; off (the zero bytes of a handle that never set
+// the option included) touches nothing.
+template <int NX>
+__device__ __forceinline__ void cl_meas_lane(const cl_meas::Args *Ap, const ClArgs &cl, int b, int s, bool post) {
+    const cl_meas::Args &A = args_here<true>(Ap);
+    if (!cl_meas::on(A)) return;
+    if (post) cl_meas::post(A, NX, b, s, cl.xmeas + (size_t)b * NX);
+    else cl_meas::pre(A, NX, b, s, cl.xmeas + (size_t)b * NX);
 }
 // the same shift of ONE instance by one wave (k_cl_loop): the tail by lane 0, the copies by all lanes (read everything, then write)
 template <int MODEL>

@@ -132,6 +132,7 @@ class BatchedFastSLS:
         self.plant_params = None
         self.bounds = None
         self.adversary = None
+        self.meas_noise = None
         self.dims = L.Dims(nx, nu, model.nw, self.N, model.ni, model.ni_f)
         self.n = model.nz * self.N + nx
         self.mb = self.N * (nx + model.ni) + model.ni_f
@@ -328,6 +329,23 @@ class BatchedFastSLS:
         code, amp, mk = adversary_arguments(policy, amp, mask, self.m.nx)
         L.check(self.lib.slsqp_cl_set_adversary(self.h, code, amp, None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_ubyte))))
         self.adversary = None if code == 0 else (code, amp)
+
+    def set_meas_noise(self, Nm):
+        """Measurement noise of the closed-loop entry points (slsqp_cl_set_meas_noise): Nm (T,nx) shared by the batch or (B,T,nx) per instance, the
+        error of the measurement in state coordinates (monte_carlo.meas_noise_table builds it from a unit sample and E[0]); row min(s, T - 1) belongs
+        to MPC step s counted from the reset that starts a run, the last row is held (T = 1: a constant bias).  The controller then sees
+        x_meas = x_plant + n_s while the plant steps from x_plant: get("x_plant", (nx,)) is the true state, get("x_meas", (nx,)) the measurement.
+        None clears it (the default).  The table takes effect at the next slsqp_cl_init (ClosedLoopMPC.reset), never in the loop in progress.  A NaN or
+        infinite entry and a wrong shape raise and leave the table as it was.  self.meas_noise holds the table as set, or None."""
+        if Nm is None:
+            L.check(self.lib.slsqp_cl_set_meas_noise(self.h, None, 0, 0, L.HOST))
+            self.meas_noise = None
+            return
+        Nm = _c(np.asarray(Nm, dtype=float))
+        if Nm.ndim not in (2, 3) or Nm.shape[-1] != self.m.nx or Nm.shape[-2] < 1 or (Nm.ndim == 3 and Nm.shape[0] != self.B):
+            raise ValueError(f"meas_noise: the table must be (T,{self.m.nx}) or ({self.B},T,{self.m.nx}) with T >= 1, got {Nm.shape}")
+        L.check(self.lib.slsqp_cl_set_meas_noise(self.h, _ptr(Nm), int(Nm.shape[-2]), int(Nm.ndim == 3), L.HOST))
+        self.meas_noise = Nm
 
     def get_adversary(self):
         """(policy code, amp) as the handle holds them (slsqp_cl_get_adversary)."""

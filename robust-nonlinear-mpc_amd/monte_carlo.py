@@ -17,6 +17,21 @@ def disturbance_stream(seed, steps, nx):
     return np.stack([2.0 * rs.rand(nx) - 1.0 for _ in range(steps)])
 
 
+def measurement_stream(seed, rows, nw):
+    """(rows, nw) unit sample in [-1,1] for the measurement noise of seed `seed`: a stream of its own (the seed and a fixed tag seed the generator), so
+    disturbance_stream of the same seed is what it always was."""
+    rs = np.random.RandomState([int(seed) & 0xFFFFFFFF, 0x6D656173])
+    return 2.0 * rs.rand(int(rows), int(nw)) - 1.0
+
+
+def meas_noise_table(m, v, amp=1.0):
+    """The measurement-noise table of ClosedLoopMPC.set_meas_noise from a unit sample v (..., T, nw): amp v E[0]^T, the error in state coordinates.
+    At amp = 1 this is exactly the set the tubes' stage-0 column assumes for the initial condition (Phi_x[0,0] = E[0])."""
+    E = np.asarray(m.E, dtype=float)
+    E0 = E[0] if E.ndim == 3 else E
+    return float(amp) * (np.asarray(v, dtype=float) @ E0.T)
+
+
 def can_run_persistent(rti, rti_steps, opts=None, environ=os.environ, sls_converge=False):
     """Whether ClosedLoopMPC.run_decoupled takes this setting (slsqp_cl_run / slsqp_cl_run_scp): any number of SCP iterations `rti` (<= 0: SCP
     converge mode), a fixed number of fast-SLS steps `rti_steps` >= 1 (None / <= 0 is fast-SLS converge mode: inside the loop only with
@@ -49,11 +64,12 @@ PERSISTENT_DEFAULT = {"pendulum": False, "quadrotor": False}
 
 def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continuation=1, budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1,
                reference=None, plant_params=None, bounds=None, solve_every=1, hold_trigger=None, plan_fallback=False, persistent_converge=False,
-               adversary=None, adversary_amp=1.0, adversary_mask=None):
+               adversary=None, adversary_amp=1.0, adversary_mask=None, meas_noise=None):
     B = len(seeds)
     W = np.stack([disturbance_stream(s, steps, model.nx) for s in seeds], axis=1) if noise else None   # (steps, B, nx)
     cl = ClosedLoopMPC(model, N, B, device=device, x0_box_tol=x0_box_tol, solve_waves=solve_waves, reference=reference, plant_params=plant_params, bounds=bounds, solve_every=solve_every, hold_trigger=hold_trigger, plan_fallback=plan_fallback,
-                       adversary=adversary, adversary_amp=adversary_amp, adversary_mask=adversary_mask)
+                       adversary=adversary, adversary_amp=adversary_amp, adversary_mask=adversary_mask,
+                       meas_noise=None if meas_noise is None else meas_noise_table(model, np.stack([measurement_stream(s, steps + 1, model.nw) for s in seeds]), meas_noise))
     X0 = np.tile(np.asarray(x0, dtype=float), (B, 1))
     rti_steps = cl.f.opts.rti_steps if cl.f.opts.rti_steps > 0 else None
     want = ((cl.rti == 1 and rti_steps == 1) or PERSISTENT_DEFAULT.get(getattr(model, "name", None), False)) if persistent is None else bool(persistent)
@@ -77,7 +93,7 @@ def _run_slice(model, N, seeds, steps, x0, device, noise, solve_nominal, continu
 def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise=True, gather=True, solve_nominal=False, slices=1, continuation=1,
                     budget_ms=None, persistent=None, x0_box_tol=0.0, solve_waves=1, reference=None, plant_params=None, bounds=None,
                     solve_every=1, hold_trigger=None, plan_fallback=False, persistent_converge=False,
-                    adversary=None, adversary_amp=1.0, adversary_mask=None):
+                    adversary=None, adversary_amp=1.0, adversary_mask=None, meas_noise=None):
     """The rocket script's setting (rti = 1, one fast-SLS step) runs every slice's loop through slsqp_cl_run -- by default ONE persistent launch per slice in
     which no instance waits for another (budget_ms only matters for the round-based variant, ClosedLoopMPC.f.opts.cl_persistent = 0); budget_ms = 0 runs
     one slsqp_cl_step per step for the whole slice instead.  The results are the same bit for bit either way.
@@ -113,6 +129,10 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
     (ClosedLoopMPC's adversary, adversary_amp, adversary_mask: the same for every seed); the seed's own stream stays the sample of the channels outside
     the mask.  The result then holds `w_applied` (steps, seeds, nx) and `disturbance_used` (steps, seeds), computed from it.  None / "off" (default):
     today's loops, unchanged.
+    meas_noise: amp = every seed's controller is given x_meas = x_plant + amp E[0] v_s, v its own measurement_stream (steps + 1 rows), through
+    ClosedLoopMPC's meas_noise (meas_noise_table); amp = 1 is the set the stage-0 column of the tubes assumes.  The result's `state_trajectory` then is
+    the true trajectory, `measured_trajectory` what the controllers saw, `meas_noise` (seeds, steps + 1, nx) the tables.  None (default): today's loops,
+    unchanged.
     slices > 1: the rank's seeds are cut into that many independent slices, each with its own handle (HIP stream) and host thread
     (as in fast_sls.SlicedDeviceBatch): results are bit-identical, the slices' solver tails overlap each other's bulk launches."""
     import threading
@@ -172,6 +192,8 @@ def run_monte_carlo(model, N, seeds, steps, x0, rank=0, world=1, device=0, noise
                 kw["persistent_converge"] = True
             if adversary not in (None, "off", 0):
                 kw.update(adversary=adversary, adversary_amp=adversary_amp, adversary_mask=adversary_mask)
+            if meas_noise is not None:
+                kw["meas_noise"] = float(meas_noise)
             kw.update(options(k))
             parts[k] = _run_slice(model, N, mine[cuts[k][0]:cuts[k][1]], steps, x0, device, noise, solve_nominal, continuation, budget_ms, **kw)
         except Exception as e:
